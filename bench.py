@@ -1,16 +1,21 @@
 """bench.py -- cell-updates/s of the SW barotropic step on the 4096 x 4096 box (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 4096] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
 
 One process per GPU (launched by torch.distributed.run for N > 1); the box is split into one
 block per GPU with the reference's block grid (2x1, 2x2, 4x2) and halos are
 exchanged over RCCL inside libocn_sw.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR then
+writes the state the last timed step left (dump_outputs).  --full adds the legs that take runs of
+their own: cpu_baseline (N = 1) and the run-time parity check of the N > 1 path.
+
 value      = interior cells (nx-4)(ny-4) x K / t_loop, t_loop = max over ranks of the K timed steps
              (barrier + device sync on both sides), inputs resident in HBM.
 roofline   = the dominant stage kernel: algorithmic bytes per launch (SURVEY.md 8a B/cell x cells)
              / its mean launch time from HIP events on the context stream, vs 8.0 TB/s.
-cpu_baseline = the C restatement (oracle/, 1 core) on a bounded sample of the same workload.
+cpu_baseline = the C restatement (oracle/, 1 core) on a bounded sample of the same workload (--full).
 """
 from __future__ import annotations
 
@@ -444,6 +449,37 @@ def load_valu(amd, stage: str, launch_ms: float, box, blocks, live_clock=None):
         return None
 
 
+# what a caller of the timed path reads after its last step (ocn_ctx_complete has formed every level):
+# the barotropic state with its filtered previous level, the depths, the diagnostics of the last step
+DUMP_FIELDS = ["ssh", "sshp", "ubrtr", "ubrtrp", "vbrtr", "vbrtrp", "hhq", "hhu", "hhv", "hhh",
+               "vort", "str_t", "str_s", "RHSx_adv", "RHSy_adv", "RHSx_dif", "RHSy_dif"]
+DUMP_BUDGET = 48 << 20          # bytes over all files of one run (every rank's blocks together)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(model, dirname: str, names, nblocks: int):
+    """Write this process's blocks of the fields `names` as DIR/<name>.npy (one block: float64, the
+    block's whole array with its halo, Fortran order) or DIR/<name>_b<bm>_<bn>.npy (several blocks).
+    An array over its share of DUMP_BUDGET is written as a fixed sample instead: the elements at
+    DUMP_SEED's sorted random positions of the Fortran-order flattened array -- the same positions
+    for every array of that size and in every run.  Returns the bytes written."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // (8 * len(names) * nblocks)
+    picks, written = {}, 0
+    for b in model.blocks:
+        for nm in names:
+            a = model.download(b.k, nm).astype(np.float64, copy=False)
+            if a.size > share:
+                if a.size not in picks:
+                    picks[a.size] = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, share, replace=False))
+                a = a.reshape(-1, order="F")[picks[a.size]]
+            path = os.path.join(dirname, nm + (f"_b{b.bm}_{b.bn}" if nblocks > 1 else "") + ".npy")
+            np.save(path, a)
+            written += os.path.getsize(path)
+    return written
+
+
 def launch_ranks(n: int) -> int:
     """torch.distributed.run with n processes on this node (127.0.0.1 rendezvous), each running
     this script with the same arguments; returns its exit status.  The parent stays GPU-free."""
@@ -479,7 +515,12 @@ def main():
     ap.add_argument("--no-stage-timing", action="store_true",
                     help="no HIP events around the launches (diagnostic: the roofline's live launch time is then "
                          "not measured)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the cpu_baseline legs (N = 1), the run-time parity "
+                         "check of the N > 1 path (multi_gpu_parity_512)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last one left as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline legs")
     ap.add_argument("--stages", action="store_true", help="run the 11 reference stages instead of the fused step")
     ap.add_argument("--no-compact", action="store_true", help="fused step on the 2-D real(4) arrays")
     ap.add_argument("--no-march", action="store_true", help="one thread per point in every launch (no register march)")
@@ -517,6 +558,8 @@ def main():
                     help="block grid BXxBY (default: one block per GPU); with one GPU, several blocks on it "
                          "exercise the halo-exchange path without RCCL")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started directly (`python bench.py --gpus N`): launch the N ranks, one process per GPU,
@@ -572,7 +615,8 @@ def main():
         model.attach_comm(uid_for())
         if args.watchdog > 0:   # a rank stuck on a peer ends with a message, not a silent time-out
             model.set_watchdog(args.watchdog)
-        parity = multi_gpu_parity(amd, dist, rank, world, local_rank, bx, by, uid_for, args.watchdog)
+        if args.full:
+            parity = multi_gpu_parity(amd, dist, rank, world, local_rank, bx, by, uid_for, args.watchdog)
     model.set_fused(not args.stages)
     model.set_compact(not args.no_compact)
     model.set_march(not args.no_march)
@@ -632,6 +676,10 @@ def main():
     x4 = (("onepass2" in times) if times else model.x4_active) and bx * by > 1
     co = model.co_launched
     model_overlap = model.overlap_level
+    if args.dump_outputs:
+        names = DUMP_FIELDS + ([f"{p}_{k}" for k in range(1, sw.tracer_num + 1) for p in ("ff1", "ff1p")]
+                               if sw.use_tracers > 0 else [])
+        dump_outputs(model, args.dump_outputs, names, bx * by)
     rank_info = None
     if world > 1:
         t = torch.tensor([dt], device="cuda")
@@ -743,7 +791,8 @@ def main():
                                      "moved_B": round(kbytes[s] * local_cells / (v * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
                                  for s, v in stage_ms.items()}
         if world > 1:
-            out["multi_gpu_parity_512"] = parity
+            if args.full:
+                out["multi_gpu_parity_512"] = parity
             out["rccl"] = rccl_report(rank_info, args.steps)
             if roof:   # the dominant launch on every GPU (its own block's cells, its own launch time)
                 roof["per_gpu"] = [
@@ -751,7 +800,7 @@ def main():
                      "frac": round(kbytes[roof["kernel"]] * r["cells"] / (r["stage_ms"][roof["kernel"]] * 1e-3) / 1e9 /
                                    HBM_PEAK_GBS, 4)}
                     for r in rank_info if roof["kernel"] in r["stage_ms"]]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         elif world > 1:
             out["cpu_baseline"] = {"value": None, "reason": "timed at N=1 only (the same host CPU path; the "
@@ -760,7 +809,7 @@ def main():
     if world > 1:
         dist.destroy_process_group()
     if out is not None:
-        if world > 1 and parity is not True:
+        if world > 1 and args.full and parity is not True:
             # the N-rank path disagrees with the single-process block grid: no number
             print(json.dumps({"error": "multi_gpu_parity_512 failed", "multi_gpu_parity_512": parity}), flush=True)
             sys.exit(3)

@@ -183,3 +183,40 @@ def test_rccl_report_from_rank_records():
     r = bench.rccl_report([dict(q, overlap=ov) for q in recs], 20)
     assert r["overlap"] == {"level": 1, "decided": True, "measured_on": "x2 step", "seq_ms": 0.11,
                             "overlapped_ms": 0.12, "per_rank_level": [1, 1]}
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: a small array is written whole (float64, the block's shape); one over its share
+    of the budget as the elements at the same seeded positions of its Fortran-order flattening in
+    every run and for every field; the files stay within the budget."""
+    import numpy as np
+
+    class _Block:
+        def __init__(self, k, bm, bn):
+            self.k, self.bm, self.bn = k, bm, bn
+
+    class _Model:
+        def __init__(self, blocks, shape):
+            self.blocks, self.shape = blocks, shape
+
+        def download(self, k, name):
+            base = np.arange(self.shape[0] * self.shape[1], dtype=np.float64).reshape(self.shape, order="F")
+            return np.asfortranarray(base + 1e6 * k + (0.5 if name == "ubrtr" else 0.0))
+
+    one = _Model([_Block(0, 1, 1)], (7, 5))
+    n = bench.dump_outputs(one, str(tmp_path / "whole"), ["ssh", "ubrtr"], 1)
+    a = np.load(tmp_path / "whole" / "ssh.npy")
+    assert a.dtype == np.float64 and a.shape == (7, 5) and np.array_equal(a, one.download(0, "ssh"))
+    assert n == sum(os.path.getsize(tmp_path / "whole" / f) for f in os.listdir(tmp_path / "whole"))
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 8 * 2 * 2 * 100)   # 100 elements per array
+    two = _Model([_Block(0, 1, 1), _Block(1, 2, 1)], (37, 23))
+    for d in ("s1", "s2"):
+        n = bench.dump_outputs(two, str(tmp_path / d), ["ssh", "ubrtr"], 2)
+    assert sorted(os.listdir(tmp_path / "s1")) == ["ssh_b1_1.npy", "ssh_b2_1.npy", "ubrtr_b1_1.npy", "ubrtr_b2_1.npy"]
+    s = np.load(tmp_path / "s1" / "ssh_b1_1.npy")
+    assert s.shape == (100,) and np.all(np.diff(s) > 0) and len(set(s)) == 100   # positions: sorted, distinct
+    for f in os.listdir(tmp_path / "s1"):
+        assert np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f))
+    assert np.array_equal(np.load(tmp_path / "s1" / "ubrtr_b2_1.npy"), s + 1e6 + 0.5)   # the same positions
+    assert n <= bench.DUMP_BUDGET + 4 * 128   # + the .npy headers
