@@ -1923,15 +1923,25 @@ static std::vector<int> with_tracers(const ocn_ctx *c, const std::vector<int> &f
 static OnepassKC kc_of(const ocn_ctx *c, const LBlock &b) { return OnepassKC{c->kc_mode, c->d_fbz, b.kc}; }
 
 // The part of block b's interior the one-pass step covers when halos are exchanged: the interior
-// less w points on each side that has a neighbour block (E, W, N, S; diagonal neighbours only
-// feed the state at the halo corners, which the stencils read as the reference does).
+// less w points on each side that has a neighbour block -- E, W, N, S, or a diagonal one of that
+// side: a diagonal neighbour receives this block's interior corner point (CA's stored depths in
+// sync CA), so that point must lie in a frame band.  In a grid without holes a diagonal neighbour
+// comes with both side neighbours; where all-land blocks were dropped it may be the only one at
+// its corner, and the corner then stayed in the inner march, which stores no depths: the
+// neighbour's corner halo of hhu / hhv / hhh's p and n levels kept stale values after the
+// hybrid last step.
+static bool side_fed(const LBlock &b, int side)   // side: 1 E, 2 W, 3 N, 4 S (kDirDm / kDirDn)
+{
+    static const int diag[5][2] = {{0, 0}, {5, 6}, {7, 8}, {5, 7}, {6, 8}};   // E: NE SE, W: NW SW, N: NE NW, S: SE SW
+    return b.nbr_rank[side - 1] >= 0 || b.nbr_rank[diag[side][0] - 1] >= 0 || b.nbr_rank[diag[side][1] - 1] >= 0;
+}
 static Range onepass_inner(const LBlock &b, int w)
 {
     Range r{b.g.nx_start, b.g.nx_end, b.g.ny_start, b.g.ny_end};
-    if (b.nbr_rank[1] >= 0) r.m0 += w;   // kDirDm / kDirDn: d = 2 W, 1 E, 4 S, 3 N
-    if (b.nbr_rank[0] >= 0) r.m1 -= w;
-    if (b.nbr_rank[3] >= 0) r.n0 += w;
-    if (b.nbr_rank[2] >= 0) r.n1 -= w;
+    if (side_fed(b, 2)) r.m0 += w;
+    if (side_fed(b, 1)) r.m1 -= w;
+    if (side_fed(b, 4)) r.n0 += w;
+    if (side_fed(b, 3)) r.n1 -= w;
     return r;
 }
 
@@ -1975,10 +1985,10 @@ static int one_step_hybrid(ocn_ctx *c, double tau, const StepKind &k, bool last 
     auto ca_frames = [&](hipStream_t st) -> int {
         RC(each_block(c, st, [&](const LBlock &b) -> int {
             Range in = onepass_inner(b, 2);
-            if (b.nbr_rank[1] < 0) in.m0 = b.g.bnd_x1;   // no frame on the sides without a neighbour
-            if (b.nbr_rank[0] < 0) in.m1 = b.g.bnd_x2;
-            if (b.nbr_rank[3] < 0) in.n0 = b.g.bnd_y1;
-            if (b.nbr_rank[2] < 0) in.n1 = b.g.bnd_y2;
+            if (!side_fed(b, 2)) in.m0 = b.g.bnd_x1;   // no frame on the sides without a neighbour
+            if (!side_fed(b, 1)) in.m1 = b.g.bnd_x2;
+            if (!side_fed(b, 4)) in.n0 = b.g.bnd_y1;
+            if (!side_fed(b, 3)) in.n1 = b.g.bnd_y2;
             RC(launch_fused_ca(&b.g, b.ptr.data(), (int)b.ptr.size(), cp(b, t), OCN_PART_FRAME, sw, tau, !last, false,
                                st, &in));
             return OCN_OK;
