@@ -485,6 +485,84 @@ int ocn_ctx_stage_times(ocn_ctx *ctx, double *ms, int64_t *counts);
  * not hidden (0 when hidden). */
 int ocn_ctx_stage_stats(ocn_ctx *ctx, double *ms, int64_t *counts, double *ms_max);
 
+/* ---------------------------------------------------------------- ensembles
+ * Members of one small basin stepped together: N contexts of the same basin, mask and decomposition on
+ * one device, whose multi-step launches (OCN_OPT_MULTI) go as ONE launch per group of members, each
+ * member with a grid barrier of its own inside it -- a basin of the Black Sea's size fills a tenth of
+ * the device, and its step is bound by the barrier, which the members of a launch pay side by side.
+ * No counterpart in the reference (one process runs one model).
+ *
+ * ocn_ens_plan (pure, no device; the policy ocn_ens_step uses): how `members` members of block `geom`
+ * go into launches of at most `capacity` workgroups.  variant[i] >= 0 names member i's kernel variant
+ * (members of one launch share it); variant[i] < 0: not eligible, in no group.  A member at `rows`
+ * rows per wave tile has ceil(W / 60) * ceil(H / (4 rows)) tiles (W x H the block's interior).  Per
+ * variant, in ascending order of the id: the smallest rows in 1..16 at which all its members fit the
+ * capacity together, as one group; if none does, rows = 16 and groups of floor(capacity / tiles)
+ * members in member order.  A block with more tiles than the capacity at 16 rows is in no group.
+ * *count = the groups (all of them, also beyond cap); out[0 .. min(cap, *count)) is written.  A
+ * group's members are member[0 .. members), ascending; member j's first workgroup in the grid is
+ * first_tile[j] = j * tiles.  members is at most OCN_ENS_MAX_MEMBERS (OCN_ERR_ARG beyond). */
+#define OCN_ENS_MAX_MEMBERS 256
+typedef struct ocn_ens_group {
+    int32_t variant, rows, tiles, members;
+    int32_t member[OCN_ENS_MAX_MEMBERS];
+    int32_t first_tile[OCN_ENS_MAX_MEMBERS];
+} ocn_ens_group;
+int ocn_ens_plan(const ocn_block *geom, const int32_t *variant, int32_t members, int64_t capacity, ocn_ens_group *out,
+                 int32_t cap, int32_t *count);
+
+/* `members` (1..OCN_ENS_MAX_MEMBERS) contexts of the same basin, parameters, mask and decomposition on dec->device,
+ * sharing one compute stream.  dec->nranks must be 1 (OCN_ERR_ARG otherwise); any block grid and
+ * tracer count is accepted (such members are stepped one by one).  Each member owns its fields and
+ * its static tables (nothing is shared: a member costs what a context costs). */
+typedef struct ocn_ens ocn_ens;
+int ocn_ens_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_decomp *dec, const int32_t *mask,
+                   int32_t members, ocn_ens **out);
+/* Destroys the members too: their borrowed handles are invalid afterwards. */
+int ocn_ens_destroy(ocn_ens *ens);
+/* Number of members (-1: null). */
+int ocn_ens_size(const ocn_ens *ens);
+/* Member i as a BORROWED context: every ocn_ctx_* entry works on it (upload, download, field, options,
+ * topography, output_r4, init_state, ocn_ctx_step for that member alone, ...) except
+ * ocn_ctx_destroy, ocn_ctx_attach_comm and ocn_ctx_attach_loopback, which return OCN_ERR_ARG: the
+ * ensemble owns it.  ocn_ctx_stream returns the shared stream.  OCN_ERR_ARG on a bad index. */
+int ocn_ens_member(ocn_ens *ens, int32_t i, ocn_ctx **out);
+/* ocn_ctx_init_state on every member. */
+int ocn_ens_init_state(ocn_ens *ens);
+/* ocn_ctx_step(member, tau, nsteps, check_every) for every member, with exactly its results.  The
+ * members that would run their own multi-step launch in this call (an open sequence, OCN_OPT_MULTI's
+ * conditions, nsteps >= 2, a variant chosen on the host) are grouped by ocn_ens_plan over the
+ * capacity (below) and issued as one launch per group; every other member -- the first call after
+ * an init or upload, 1-step calls, blocks too large, block grids, tracers, OCN_OPT_MULTI off, a raw
+ * pointer handed out -- gets ocn_ctx_step.  Residency: every workgroup of a launch must be on the
+ * device at once, so a group has at most capacity / tiles members; the capacity is the occupancy of
+ * the multi-step kernels x the device's CUs, lowered by OCN_ENS_OPT_CAPACITY.  Asynchronous.  Returns
+ * the first error of any member. */
+int ocn_ens_step(ocn_ens *ens, double tau, int32_t nsteps, int32_t check_every);
+/* ocn_ctx_complete on every member. */
+int ocn_ens_complete(ocn_ens *ens);
+/* Waits for the shared stream once; status[i] (may be NULL) = what ocn_ctx_synchronize returns for
+ * member i: OCN_OK, OCN_ERR_BLOWUP (its check found |ssh| >= 1e4), OCN_ERR_HIP (its barrier timed
+ * out: its results are invalid).  A member's blow-up or timeout neither stops nor disturbs the
+ * others.  Returns the first status that is not OCN_OK. */
+int ocn_ens_synchronize(ocn_ens *ens, int32_t *status);
+/* The last ocn_ens_step: groups = batched launches issued, batched = members in them, rows / tiles =
+ * rows per wave tile and tiles per member of the largest group (most members; 0 with none),
+ * max_group = its members, capacity = the capacity in effect (workgroups). */
+typedef struct ocn_ens_info_t {
+    int32_t members, groups, batched, rows, tiles, max_group;
+    int64_t capacity;
+} ocn_ens_info_t;
+int ocn_ens_info(ocn_ens *ens, ocn_ens_info_t *out);
+/* OCN_ENS_OPT_CAPACITY: a cap on the workgroups of one ensemble launch (value >= 1; 0 = none).  It
+ * only ever lowers the device's capacity: for a host that shares the device, and for tests, which
+ * reach taller tiles and several groups on tiny blocks with it.
+ * OCN_ENS_OPT_MAX_GROUP (measurements; 0 = none): at most this many of the members planned in a call go
+ * to ocn_ens_plan together (in member order), so that several shorter launches can be timed against
+ * one taller one (scripts/ens_bench.py). */
+enum { OCN_ENS_OPT_CAPACITY = 1, OCN_ENS_OPT_MAX_GROUP = 2 };
+int ocn_ens_set_option(ocn_ens *ens, int32_t key, int64_t value);
+
 const char *ocn_last_error(void);
 int ocn_abi_version(void);
 /* Build id: a hash of the library's sources and compile flags (Makefile), e.g. to tie a

@@ -7,6 +7,7 @@ libocn_sw.so (C ABI: include/ocn_sw.h), hosts in Python (this package) and Fortr
 from ._lib import OcnError, OcnLibraryError, build, build_id, lib  # noqa: F401
 from .config import BasinConfig, ParallelConfig, SWConfig, box_config, read_mask  # noqa: F401
 from .model import OceanModel, make_unique_id, run_ranks  # noqa: F401
+from .ensemble import OceanEnsemble  # noqa: F401
 
-__all__ = ["OceanModel", "BasinConfig", "SWConfig", "ParallelConfig", "box_config", "read_mask",
+__all__ = ["OceanModel", "OceanEnsemble", "BasinConfig", "SWConfig", "ParallelConfig", "box_config", "read_mask",
            "make_unique_id", "run_ranks", "build", "lib", "OcnError", "OcnLibraryError"]

@@ -101,7 +101,13 @@ CTX_SYMBOLS = ["ocn_decompose", "ocn_halo_schedule", "ocn_ctx_create", "ocn_ctx_
                "ocn_ctx_download", "ocn_ctx_complete", "ocn_ctx_upload", "ocn_ctx_output_r4", "ocn_ctx_set_option", "ocn_ctx_get_option", "ocn_ctx_stage_times", "ocn_ctx_stage_stats",
                "ocn_ctx_comm_info", "ocn_ctx_overlap_info", "ocn_ctx_clock_info", "ocn_ctx_set_watchdog", "ocn_last_error", "ocn_abi_version",
                "ocn_build_id", "ocn_launch_count"]
-ALL_SYMBOLS = KERNEL_SYMBOLS + CTX_SYMBOLS
+ENS_SYMBOLS = ["ocn_ens_plan", "ocn_ens_create", "ocn_ens_destroy", "ocn_ens_size", "ocn_ens_member",
+               "ocn_ens_init_state", "ocn_ens_step", "ocn_ens_complete", "ocn_ens_synchronize", "ocn_ens_info",
+               "ocn_ens_set_option"]
+ALL_SYMBOLS = KERNEL_SYMBOLS + CTX_SYMBOLS + ENS_SYMBOLS
+ENS_MAX_MEMBERS = 256          # OCN_ENS_MAX_MEMBERS
+ENS_OPT_CAPACITY = 1
+ENS_OPT_MAX_GROUP = 2
 
 
 class OcnLibraryError(RuntimeError):
@@ -162,6 +168,16 @@ class OcnOverlapInfo(C.Structure):
 
 class OcnClockInfo(C.Structure):
     _fields_ = [("launches", C.c_int64), ("clock_ghz", C.c_double), ("sampled_ms", C.c_double)]
+
+
+class OcnEnsGroup(C.Structure):
+    _fields_ = [("variant", C.c_int32), ("rows", C.c_int32), ("tiles", C.c_int32), ("members", C.c_int32),
+                ("member", C.c_int32 * ENS_MAX_MEMBERS), ("first_tile", C.c_int32 * ENS_MAX_MEMBERS)]
+
+
+class OcnEnsInfo(C.Structure):
+    _fields_ = [("members", C.c_int32), ("groups", C.c_int32), ("batched", C.c_int32), ("rows", C.c_int32),
+                ("tiles", C.c_int32), ("max_group", C.c_int32), ("capacity", C.c_int64)]
 
 
 HALO_LOCAL, HALO_SEND, HALO_RECV = 0, 1, 2
@@ -233,6 +249,17 @@ def lib() -> C.CDLL:
                                 C.c_int32, C.POINTER(C.c_int32)]
     L.ocn_halo_schedule.argtypes = [C.POINTER(OcnBasin), C.POINTER(OcnDecomp), C.c_void_p, C.POINTER(C.c_int32),
                                     C.c_int32, C.POINTER(OcnHaloMsg), C.c_int32, C.POINTER(C.c_int32)]
+    L.ocn_ens_plan.argtypes = [C.POINTER(OcnBlock), C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.POINTER(OcnEnsGroup),
+                               C.c_int32, C.POINTER(C.c_int32)]
+    L.ocn_ens_create.argtypes = [C.POINTER(OcnBasin), C.POINTER(OcnSwParams), C.POINTER(OcnDecomp), C.c_void_p,
+                                 C.c_int32, C.POINTER(C.c_void_p)]
+    for nm in ("ocn_ens_destroy", "ocn_ens_size", "ocn_ens_init_state", "ocn_ens_complete"):
+        getattr(L, nm).argtypes = [C.c_void_p]
+    L.ocn_ens_member.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+    L.ocn_ens_step.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_int32]
+    L.ocn_ens_synchronize.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.ocn_ens_info.argtypes = [C.c_void_p, C.POINTER(OcnEnsInfo)]
+    L.ocn_ens_set_option.argtypes = [C.c_void_p, C.c_int32, C.c_int64]
     _lib = L
     return L
 

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "ocn_internal.h"
+#include "ocn_ens_plan.h"
 
 namespace ocn {
 
@@ -467,6 +468,12 @@ struct ocn_ctx {
     int32_t *d_flags = nullptr;
     bool batch = true;           // OCN_OPT_BATCH
     ocn::Batcher batcher;
+    // a member of an ensemble (ocn_ens_create): the ensemble owns the context and its compute stream,
+    // which the members share.  ens_collect (inside ocn_ens_step): step_impl plans a multi-step launch
+    // as ever but leaves it to the ensemble, which issues it with the other members' (ens_pending, ens_k)
+    ocn_ens *ens = nullptr;
+    bool ens_collect = false, ens_pending = false;
+    ocn::StepKind ens_k{};
 };
 
 // v on the device with its chunk table (one entry per kSegChunk elements of each segment), in one
@@ -3055,8 +3062,10 @@ int ocn_abi_version(void) { return OCN_ABI_VERSION; }
 const char *ocn_build_id(void) { return OCN_BUILD_ID; }
 int64_t ocn_launch_count(void) { return (int64_t)g_launches.load(std::memory_order_relaxed); }
 
-int ocn_ctx_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_decomp *dec, const int32_t *mask,
-                   ocn_ctx **out)
+static int ctx_destroy(ocn_ctx *c);
+// shared: the compute stream of the ensemble `ens` the context becomes a member of (null: its own)
+static int ctx_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_decomp *dec, const int32_t *mask,
+                      hipStream_t shared, ocn_ens *ens, ocn_ctx **out)
 {
     if (!basin || !sw || !dec || !out) return set_error(OCN_ERR_ARG, "null argument");
     if (basin->nx < 5 || basin->ny < 5) return set_error(OCN_ERR_ARG, "nx, ny must be >= 5");
@@ -3067,9 +3076,11 @@ int ocn_ctx_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_de
     ocn_ctx *c = new ocn_ctx();
     c->basin = *basin; c->sw = *sw; c->dec = *dec;
     c->bnx = dec->bnx; c->bny = dec->bny;
+    c->ens = ens;
     set_mask(c, mask);
     int rc = check_hip(hipSetDevice(dec->device), "hipSetDevice");
-    if (!rc) rc = check_hip(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "hipStreamCreate");
+    if (shared) c->stream = shared;
+    else if (!rc) rc = check_hip(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "hipStreamCreate");
     // the comm stream at the highest priority: the side chains' short frame launches and the
     // exchanges take wave slots as they free up instead of queueing behind the inner marches
     if (!rc) {
@@ -3087,9 +3098,15 @@ int ocn_ctx_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_de
     if (!rc) rc = allocate(c);
     if (!rc) rc = prebuild_plans(c);
     if (!rc) rc = check_hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-    if (rc) { ocn_ctx_destroy(c); return rc; }
+    if (rc) { ctx_destroy(c); return rc; }
     *out = c;
     return OCN_OK;
+}
+
+int ocn_ctx_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_decomp *dec, const int32_t *mask,
+                   ocn_ctx **out)
+{
+    return ctx_create(basin, sw, dec, mask, nullptr, nullptr, out);
 }
 
 // host-only context (decomposition only, no device) for the query entry points
@@ -3151,6 +3168,12 @@ int ocn_halo_schedule(const ocn_basin *basin, const ocn_decomp *dec, const int32
 
 int ocn_ctx_destroy(ocn_ctx *c)
 {
+    if (c && c->ens) return set_error(OCN_ERR_ARG, "a member of an ensemble is destroyed by ocn_ens_destroy");
+    return ctx_destroy(c);
+}
+
+static int ctx_destroy(ocn_ctx *c)
+{
     if (!c) return OCN_OK;
     if (c->wd.joinable()) {   // the watchdog first: nothing is watched from here on
         {
@@ -3190,7 +3213,7 @@ int ocn_ctx_destroy(ocn_ctx *c)
     if (c->ev_fb) (void)hipEventDestroy(c->ev_fb);
     if (c->h_fbz) (void)hipHostFree(c->h_fbz);
     if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    if (c->stream && !c->ens) (void)hipStreamDestroy(c->stream);   // (a member's: the ensemble's)
     delete c;
     return OCN_OK;
 }
@@ -3244,6 +3267,7 @@ int ocn_comm_unique_id(void *out_id, int32_t nbytes)
 int ocn_ctx_attach_comm(ocn_ctx *c, const void *unique_id, int32_t nbytes)
 {
     if (!c || !unique_id || nbytes < (int32_t)sizeof(ncclUniqueId)) return set_error(OCN_ERR_ARG, "bad unique id");
+    if (c->ens) return set_error(OCN_ERR_ARG, "a member of an ensemble takes no communicator");
     HIPCHK(hipSetDevice(c->dec.device));
     ncclUniqueId id;
     std::memcpy(&id, unique_id, sizeof(id));
@@ -3258,6 +3282,7 @@ int ocn_ctx_attach_loopback(ocn_ctx *const *ctxs, int32_t n)
     if (!ctxs || n < 1 || n > 64) return set_error(OCN_ERR_ARG, "loopback: 1..64 contexts");
     for (int i = 0; i < n; ++i) {
         const ocn_ctx *c = ctxs[i];
+        if (c && c->ens) return set_error(OCN_ERR_ARG, "loopback: a member of an ensemble takes no transport");
         if (!c || c->dec.nranks != n || c->dec.rank != i || c->dec.device != ctxs[0]->dec.device)
             return set_error(OCN_ERR_ARG, "loopback: context i must be rank i of nranks = n, all on one device");
         if (c->comm || c->lb || c->initialized)
@@ -3804,7 +3829,9 @@ static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every
                     k.check = check_every == 1;
                     k.flip = k.one = k.next_one = k.a_done = true;
                     k.multi = nsteps;
-                    rc = run_step(c, tau, k);
+                    // (inside ocn_ens_step: planned here, issued with the other members' launches)
+                    if (c->ens_collect) { c->ens_k = k; c->ens_pending = true; }
+                    else rc = run_step(c, tau, k);
                     c->open_pair = false;
                     c->multi_used = true;
                 } else {
@@ -4266,6 +4293,274 @@ int ocn_ctx_get_option(const ocn_ctx *c, int32_t key, int64_t *value)
     case OCN_OPT_CO_LAUNCH: *value = c->co_used ? 2 : c->co_launch; return OCN_OK;
     case OCN_OPT_XCHG_DELAY: *value = c->xdelay_us; return OCN_OK;
     default: return set_error(OCN_ERR_ARG, "unknown option");
+    }
+}
+
+// ------------------------------------------------------------------ ensembles (ocn_sw.h)
+struct ocn_ens {
+    std::vector<ocn_ctx *> m;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    unsigned *d_bar = nullptr;     // kMultiBarBytes of barrier words per member
+    void *d_tab = nullptr;         // the launches' member table (sw_kernels.hip EnsEntry), tab_bytes
+    size_t tab_bytes = 0;
+    // the table's pinned host copies: a call's launches fill disjoint parts of one, the next call takes
+    // the other; ev[i]: the stream has read copy i (awaited before it is written again)
+    void *h_tab[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool ev_set[2] = {false, false};
+    int slot = 0;
+    int64_t cap_opt = 0;           // OCN_ENS_OPT_CAPACITY (0: none)
+    int64_t max_group = 0;         // OCN_ENS_OPT_MAX_GROUP (0: none)
+    ocn_ens_info_t last{};
+};
+
+// ocn_ens_plan's policy: ocn_ens_plan.h (pure host code, also built stand-alone)
+static int ens_plan(const ocn_block *g, const int32_t *variant, int members, int64_t capacity,
+                    std::vector<ocn_ens_group> &out)
+{
+    const char *err = nullptr;
+    const int rc = ens_plan_groups(g, variant, members, capacity, out, &err);
+    return rc ? set_error(rc, std::string("ensemble plan: ") + err) : OCN_OK;
+}
+
+int ocn_ens_plan(const ocn_block *geom, const int32_t *variant, int32_t members, int64_t capacity, ocn_ens_group *out,
+                 int32_t cap, int32_t *count)
+{
+    std::vector<ocn_ens_group> gs;
+    RC(ens_plan(geom, variant, members, capacity, gs));
+    if (count) *count = (int32_t)gs.size();
+    for (size_t i = 0; i < gs.size() && (int32_t)i < cap && out; ++i) out[i] = gs[i];
+    return OCN_OK;
+}
+
+int ocn_ens_destroy(ocn_ens *e)
+{
+    if (!e) return OCN_OK;
+    (void)hipSetDevice(e->device);
+    if (e->stream) (void)hipStreamSynchronize(e->stream);
+    for (ocn_ctx *c : e->m) (void)ctx_destroy(c);
+    for (int i = 0; i < 2; ++i) {
+        if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
+        if (e->h_tab[i]) (void)hipHostFree(e->h_tab[i]);
+    }
+    if (e->d_tab) (void)hipFree(e->d_tab);
+    if (e->d_bar) (void)hipFree(e->d_bar);
+    if (e->stream) (void)hipStreamDestroy(e->stream);
+    delete e;
+    return OCN_OK;
+}
+
+int ocn_ens_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_decomp *dec, const int32_t *mask,
+                   int32_t members, ocn_ens **out)
+{
+    if (!basin || !sw || !dec || !out) return set_error(OCN_ERR_ARG, "null argument");
+    if (members < 1 || members > OCN_ENS_MAX_MEMBERS)
+        return set_error(OCN_ERR_ARG, "ensemble: 1.." + std::to_string(OCN_ENS_MAX_MEMBERS) + " members");
+    if (dec->nranks != 1) return set_error(OCN_ERR_ARG, "ensemble: one rank (dec->nranks = 1)");
+    ocn_ens *e = new ocn_ens();
+    e->device = dec->device;
+    int rc = check_hip(hipSetDevice(dec->device), "hipSetDevice");
+    if (!rc) rc = check_hip(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate");
+    for (int i = 0; i < members && !rc; ++i) {
+        ocn_ctx *c = nullptr;
+        rc = ctx_create(basin, sw, dec, mask, e->stream, e, &c);
+        if (!rc) e->m.push_back(c);
+    }
+    e->tab_bytes = (size_t)members * onepass_multi_b_entry_bytes();
+    if (!rc) rc = check_hip(hipMalloc((void **)&e->d_bar, (size_t)members * kMultiBarBytes), "hipMalloc");
+    if (!rc) rc = check_hip(hipMalloc(&e->d_tab, e->tab_bytes), "hipMalloc");
+    for (int i = 0; i < 2 && !rc; ++i) {
+        rc = check_hip(hipHostMalloc(&e->h_tab[i], e->tab_bytes, hipHostMallocDefault), "hipHostMalloc");
+        if (!rc) rc = check_hip(hipEventCreateWithFlags(&e->ev[i], hipEventDisableTiming), "hipEventCreate");
+    }
+    if (rc) { ocn_ens_destroy(e); return rc; }
+    e->last.members = members;
+    *out = e;
+    return OCN_OK;
+}
+
+int ocn_ens_size(const ocn_ens *e) { return e ? (int)e->m.size() : -1; }
+
+int ocn_ens_member(ocn_ens *e, int32_t i, ocn_ctx **out)
+{
+    if (!e || !out || i < 0 || i >= (int32_t)e->m.size()) return set_error(OCN_ERR_ARG, "ensemble: bad member index");
+    *out = e->m[(size_t)i];
+    return OCN_OK;
+}
+
+int ocn_ens_init_state(ocn_ens *e)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    for (ocn_ctx *c : e->m) RC(ocn_ctx_init_state(c));
+    return OCN_OK;
+}
+
+int ocn_ens_complete(ocn_ens *e)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    int first = OCN_OK;
+    for (ocn_ctx *c : e->m)
+        if (const int rc = ocn_ctx_complete(c); rc && !first) first = rc;
+    return first;
+}
+
+static int64_t ens_capacity(const ocn_ens *e)
+{
+    const int64_t dev = onepass_multi_b_capacity();
+    return e->cap_opt > 0 ? std::min(dev, e->cap_opt) : dev;
+}
+
+// a member's planned multi-step launch did not go out: its call fails as step_impl's would
+static int ens_fail(ocn_ctx *c, int rc)
+{
+    c->open = false; c->deferred = 0; c->open_pair = false;
+    return fail_fatal(c, finish_call(c, rc));
+}
+
+int ocn_ens_step(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    const int M = (int)e->m.size();
+    e->last = ocn_ens_info_t{};
+    e->last.members = M;
+    int first = OCN_OK;
+    auto note = [&](int rc) { if (rc && !first) first = rc; };
+    // every member plans its call as ocn_ctx_step does and runs whatever is not a multi-step launch
+    std::vector<int32_t> variant((size_t)M, -1);
+    for (int i = 0; i < M; ++i) {
+        ocn_ctx *c = e->m[(size_t)i];
+        c->ens_pending = false;
+        c->ens_collect = true;
+        note(guarded(c, "ocn_ens_step", [&] { return step_entry(c, tau, nsteps, check_every); }));
+        c->ens_collect = false;
+        // (batched: the library's fused path with the sw switches the launch needs; else its own launch)
+        if (c->ens_pending && c->fused && c->sw.full_free_surface == 1 && c->sw.trans_terms > 0 && c->sw.ksw_lat > 0)
+            variant[(size_t)i] = onepass_multi_variant(c->kc_mode, tau, c->ens_k.check);
+    }
+    HIPCHK(hipSetDevice(e->device));
+    e->last.capacity = ens_capacity(e);
+    std::vector<ocn_ens_group> groups;
+    if (e->last.capacity >= 1 && e->max_group < 1) {
+        note(ens_plan(&e->m[0]->blocks[0].g, variant.data(), M, e->last.capacity, groups));
+    } else if (e->last.capacity >= 1) {   // OCN_ENS_OPT_MAX_GROUP: the plan of every max_group planned members
+        std::vector<ocn_ens_group> part;
+        std::vector<int32_t> v((size_t)M, -1);
+        int n = 0;
+        for (int i = 0; i < M; ++i) {
+            if (variant[(size_t)i] >= 0) { v[(size_t)i] = variant[(size_t)i]; ++n; }
+            if (n && (n == e->max_group || i == M - 1)) {
+                note(ens_plan(&e->m[0]->blocks[0].g, v.data(), M, e->last.capacity, part));
+                groups.insert(groups.end(), part.begin(), part.end());
+                std::fill(v.begin(), v.end(), -1);
+                n = 0;
+            }
+        }
+    }
+    std::vector<char> done((size_t)M, 0);
+    if (!groups.empty()) {
+        const int sl = e->slot;
+        e->slot ^= 1;
+        if (e->ev_set[sl]) HIPCHK(hipEventSynchronize(e->ev[sl]));
+        HIPCHK(hipMemsetAsync(e->d_bar, 0, (size_t)M * kMultiBarBytes, e->stream));
+        const size_t eb = onepass_multi_b_entry_bytes();
+        size_t off = 0;
+        for (const ocn_ens_group &q : groups) {
+            std::vector<Compact> cps((size_t)q.members);
+            std::vector<EnsMember> ms((size_t)q.members);
+            std::vector<ocn_ctx::Rec> recs((size_t)q.members);
+            int rc = OCN_OK;
+            for (int j = 0; j < q.members; ++j) {
+                ocn_ctx *c = e->m[(size_t)q.member[j]];
+                const LBlock &b = c->blocks[0];
+                cps[(size_t)j] = Compact{b.bits, b.rows, c->march};
+                const OnepassKC kc = kc_of(c, b);
+                ms[(size_t)j] = EnsMember{&b.g, b.ptr.data(), (int)b.ptr.size(), &cps[(size_t)j],
+                                          c->ens_k.check ? c->d_nbad : nullptr,
+                                          {(double *)b.sshp_alt, (double *)b.up_alt, (double *)b.vp_alt},
+                                          e->d_bar + (size_t)q.member[j] * (kMultiBarBytes / sizeof(unsigned)),
+                                          c->d_nbad + 61, kc.kc, c->multi_spin};
+                if (!c->fused) c->hn_fresh = false;
+                if (!rc) rc = timer_begin(c, OCN_TIMER_ONEPASS_MULTI, recs[(size_t)j]);
+            }
+            if (!rc)
+                rc = launch_onepass_multi_b(ms.data(), q.members, q.variant, q.rows, e->m[(size_t)q.member[0]]->sw, tau,
+                                            nsteps, e->d_tab, (char *)e->h_tab[sl] + off, eb * (size_t)q.members,
+                                            (long)e->last.capacity, e->stream);
+            off += eb * (size_t)q.members;
+            for (int j = 0; j < q.members; ++j) {
+                ocn_ctx *c = e->m[(size_t)q.member[j]];
+                done[(size_t)q.member[j]] = 1;
+                c->ens_pending = false;
+                if (!rc) {   // the host side of one_step_multi
+                    const int rt = timer_end(c, recs[(size_t)j]);
+                    if (c->ens_k.multi & 1) {
+                        swap_alt3(c);
+                        swap_roles(c);
+                    }
+                    if (rt) note(ens_fail(c, rt));
+                } else {
+                    note(ens_fail(c, rc));
+                }
+            }
+            if (!rc) {
+                ++e->last.groups;
+                e->last.batched += q.members;
+                if (q.members > e->last.max_group) {
+                    e->last.max_group = q.members; e->last.rows = q.rows; e->last.tiles = q.tiles;
+                }
+            }
+        }
+        HIPCHK(hipEventRecord(e->ev[sl], e->stream));
+        e->ev_set[sl] = true;
+    }
+    // planned members in no group (no variant the launch takes, or too many tiles for the capacity in
+    // effect): their own multi-step launch, as ocn_ctx_step issues it
+    for (int i = 0; i < M; ++i) {
+        ocn_ctx *c = e->m[(size_t)i];
+        if (!c->ens_pending || done[(size_t)i]) continue;
+        c->ens_pending = false;
+        if (const int rc = run_step(c, tau, c->ens_k)) note(ens_fail(c, rc));
+    }
+    return first;
+}
+
+int ocn_ens_synchronize(ocn_ens *e, int32_t *status)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    int first = OCN_OK;
+    std::string msg;
+    for (size_t i = 0; i < e->m.size(); ++i) {   // (the first member's wait is the wait: one stream)
+        const int rc = ocn_ctx_synchronize(e->m[i]);
+        if (status) status[i] = rc;
+        if (rc && !first) { first = rc; msg = "member " + std::to_string(i) + ": " + ocn_last_error(); }
+    }
+    return first ? set_error(first, msg) : OCN_OK;
+}
+
+int ocn_ens_info(ocn_ens *e, ocn_ens_info_t *out)
+{
+    if (!e || !out) return set_error(OCN_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(e->device));
+    *out = e->last;
+    out->members = (int32_t)e->m.size();
+    out->capacity = ens_capacity(e);
+    return OCN_OK;
+}
+
+int ocn_ens_set_option(ocn_ens *e, int32_t key, int64_t value)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    switch (key) {
+    case OCN_ENS_OPT_CAPACITY:
+        if (value < 0) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_CAPACITY: >= 0");
+        e->cap_opt = value;
+        return OCN_OK;
+    case OCN_ENS_OPT_MAX_GROUP:
+        if (value < 0) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_MAX_GROUP: >= 0");
+        e->max_group = value;
+        return OCN_OK;
+    default: return set_error(OCN_ERR_ARG, "unknown ensemble option");
     }
 }
 

@@ -188,6 +188,33 @@ int onepass_multi_fits(const ocn_block *b);
 int launch_onepass_multi(const ocn_block *b, void *const *ptr, int nptr, const Compact *cp, const ocn_sw_params &sw,
                          double tau, int nsteps, int32_t *nbad, double *sshp_alt, double *up_alt, double *vp_alt,
                          unsigned *ctr, int32_t *err, hipStream_t s, const OnepassKC &kc, int spin = kMultiSpin);
+// The multi-step launch for several members of an ensemble at once (sw_kernels.hip k_march_multi_b):
+// n members of one block geometry and one variant (onepass_multi_variant: the known-constant, h_r-read
+// or general body, tau a power of two or not, with or without the per-step check; -1 where the host has
+// not chosen one), `rows` rows per wave tile, each member's tiles one after the other in the grid.  A
+// member brings its field table, compact tables, blow-up counter, second buffers, its own
+// kMultiBarBytes of barrier words (zeroed on the stream first), its own timeout flag and spin bound.
+// d_tab / h_tab: device and pinned host memory for the members' table (tab_bytes each, at least
+// n x onepass_multi_b_entry_bytes()); the host copy is read when the stream reaches the copy.
+// capacity: workgroups that may be resident (at most onepass_multi_b_capacity(), the occupancy of
+// every variant of both multi-step kernels x the device's CUs): n x tiles above it is an error.
+struct EnsMember {
+    const ocn_block *b;
+    void *const *ptr;
+    int nptr;
+    const Compact *cp;
+    int32_t *nbad;
+    double *alt[3];
+    unsigned *ctr;
+    int32_t *err;
+    const double *kc;
+    int spin;
+};
+int onepass_multi_variant(int kc_mode, double tau, bool check);
+size_t onepass_multi_b_entry_bytes();
+long onepass_multi_b_capacity();
+int launch_onepass_multi_b(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
+                           int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, hipStream_t s);
 // the known-constant precondition of launch_onepass over r (sw_kernels.hip FallbackCheck: the
 // fallback points and the forcing hold +0.0, h_r and mu are uniform): ORs 1 into *flag where it
 // does not hold; writes h_r and mu at (r.m0, r.n0) to kc[0], kc[1]

@@ -3136,6 +3136,190 @@ int launch_onepass_multi(const ocn_block *b, void *const *ptr, int nptr, const C
 #undef OCN_MULTI
 }
 
+// ------------------------------------------------------------------ ensembles: members per launch
+// k_march_multi_b: the multi-step launch for several members of an ensemble (ocn_ens_step) at once.
+// The grid is the members' tile sets one after the other; the members of a launch share the block
+// geometry and the tile height, so each has `tiles` workgroups and workgroup w is tile w % tiles of
+// member w / tiles (workgroup-uniform).  A member's two bodies, its rect, its barrier words, its
+// timeout flag and its spin bound are one EnsEntry of a table in device memory: a MarchStep body is
+// 640 B, an entry 1352 B, so no more than three members fit the 4 KB of kernel arguments by value and
+// an ensemble of 64 would need 22 chunked launches -- one table read with scalar loads instead (the
+// constant address space: the table is written by a copy ordered before the launch and never by
+// the kernel, so the loads are uniform and go through the scalar cache as kernel arguments do).
+// Each member's barrier is its own: grid_barrier's arithmetic with the member's tile count and the
+// workgroup's tile index within the member in place of gridDim.x and blockIdx.x, on the member's own
+// kMultiBarBytes of words.  A member whose barrier gives up ORs 1 into its own flag and its
+// workgroups end; the other members' workgroups never look at those words.  Every workgroup of the
+// launch must be resident at once (members x tiles <= the capacity, checked by the host): a member's
+// workgroups wait for each other only, but they may be anywhere in the grid.
+template <class Body> struct EnsEntry {
+    Body b[2];
+    MarchRect R;
+    unsigned *bar;
+    int32_t *err;
+    int spin, pad;
+};
+
+__device__ __forceinline__ bool member_barrier(unsigned *bar, unsigned n, unsigned tile, unsigned epoch, int32_t *err,
+                                               int spin)
+{
+    __shared__ int ok_s;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's write-through stores reached memory
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned g = tile & 7u, ng = (n - g + 7u) / 8u, groups = n < 8u ? n : 8u;
+        const unsigned t = __hip_atomic_fetch_add(bar + 32 * (1 + g), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        int k = 0;
+        if (t + 1 == ng * epoch) {   // the group's last arrival of this epoch
+            __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < groups * epoch && ++k < spin)
+                __builtin_amdgcn_s_sleep(1);
+            __hip_atomic_store(bar + 32 * (9 + g), epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            while (__hip_atomic_load(bar + 32 * (9 + g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < epoch &&
+                   ++k < spin)
+                __builtin_amdgcn_s_sleep(1);
+        }
+        const bool ok = k < spin;
+        if (!ok) atomicOr(err, 1);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // drop stale lines: the next step's loads
+        ok_s = ok;
+    }
+    __syncthreads();
+    return ok_s != 0;
+}
+
+template <class Body>
+__global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_b(const EnsEntry<Body> *__restrict__ tab, int tiles,
+                                                                         int nsteps)
+{
+    typedef const EnsEntry<Body> __attribute__((address_space(4))) *ConstTab;
+    const int mem = __builtin_amdgcn_readfirstlane((int)blockIdx.x / tiles);
+    const int tile = (int)blockIdx.x - mem * tiles;
+    ConstTab e = (ConstTab)tab + mem;
+    const MarchRect R = *(const MarchRect *)&e->R;
+    unsigned *const bar = e->bar;
+    int32_t *const err = e->err;
+    const int spin = e->spin;
+    if constexpr (HasPrologue<Body>::v) ((const Body *)&e->b[0])->prologue(R, tile / R.ntx);   // the same rows every step
+    for (int s = 0; s < nsteps; ++s) {
+        march_tile<Body, false>(R, tile, *(const Body *)&e->b[__builtin_amdgcn_readfirstlane(s & 1)]);
+        if (s + 1 < nsteps && !member_barrier(bar, (unsigned)tiles, (unsigned)tile, (unsigned)(s + 1), err, spin)) return;
+    }
+}
+
+// the variant of a member's launch as the planner's id: 2 x (0 known-constant, 1 h_r-read, 2 general)
+// + (tau a power of two), + 6 with the per-step check; -1: no variant chosen on the host
+int onepass_multi_variant(int kc_mode, double tau, bool check)
+{
+    int ex;
+    const int p2 = std::frexp(tau, &ex) == 0.5 && ex > -1020 && ex < 1020;
+    const int v = kc_mode == OCN_KC_KNOWN ? 0 : kc_mode == OCN_KC_KNOWN_HR ? 1 : kc_mode == OCN_KC_GENERAL ? 2 : -1;
+    return v < 0 ? -1 : 2 * v + p2 + (check ? 6 : 0);
+}
+
+template <class T> struct BodyTag { using type = T; };
+template <class F> static auto multi_b_dispatch(int variant, F &&f)
+{
+    switch (variant % 6) {
+    case 0: return f(BodyTag<MultiBody<false, true, false>>{});
+    case 1: return f(BodyTag<MultiBody<true, true, false>>{});
+    case 2: return f(BodyTag<MultiBody<false, true, true>>{});
+    case 3: return f(BodyTag<MultiBody<true, true, true>>{});
+    case 4: return f(BodyTag<MultiBody<false, false, false>>{});
+    default: return f(BodyTag<MultiBody<true, false, false>>{});
+    }
+}
+
+size_t onepass_multi_b_entry_bytes()
+{
+    size_t n = 0;
+    for (int v = 0; v < 6; ++v)
+        n = std::max(n, multi_b_dispatch(v, [](auto b) { return sizeof(EnsEntry<typename decltype(b)::type>); }));
+    return n;
+}
+
+// the resident capacity of the ensemble launch in workgroups: as multi_capacity, over both kernels
+long onepass_multi_b_capacity()
+{
+    static std::mutex mu;
+    static std::map<int, long> cap;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    long c = multi_capacity();
+    std::lock_guard<std::mutex> g(mu);
+    const auto it = cap.find(dev);
+    if (it != cap.end()) return it->second;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) c = 0;
+    for (int v = 0; v < 6; ++v)
+        multi_b_dispatch(v, [&](auto b) {
+            int per = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_march_multi_b<typename decltype(b)::type>, 256, 0) != hipSuccess)
+                per = 0;
+            c = std::min(c, (long)per * cus);
+            return 0;
+        });
+    return cap[dev] = c;
+}
+
+int launch_onepass_multi_b(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
+                           int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, hipStream_t s)
+{
+    if (!m || n < 1 || variant < 0 || variant >= 12 || rows < 1 || rows > 16 || nsteps < 1 || !d_tab || !h_tab)
+        return set_error(OCN_ERR_ARG, "ensemble launch: members, a variant, 1..16 rows, a table");
+    if (sw.full_free_surface != 1 || sw.trans_terms <= 0 || sw.ksw_lat <= 0)
+        return set_error(OCN_ERR_ARG, "ensemble launch: full_free_surface = 1, trans_terms and ksw_lat on");
+    if (batching(s)) return batch_violation();
+    const bool check = variant >= 6;
+    return multi_b_dispatch(variant, [&](auto proto) -> int {
+        using Body = typename decltype(proto)::type;
+        using Entry = EnsEntry<Body>;
+        if (sizeof(Entry) * (size_t)n > tab_bytes) return set_error(OCN_ERR_ARG, "ensemble launch: table too small");
+        Entry *tab = (Entry *)h_tab;
+        int tiles = 0;
+        for (int i = 0; i < n; ++i) {
+            const EnsMember &e = m[i];
+            if (!e.b || !e.ptr || !e.cp || !e.cp->march || !e.alt[0] || !e.alt[1] || !e.alt[2] || !e.ctr || !e.err ||
+                (check && !e.nbad) || (variant % 6 < 4 && !e.kc))
+                return set_error(OCN_ERR_ARG, "ensemble launch: a member's tables, second buffers, barrier words");
+            RC_K(check_block(e.b));
+            const Range r = range_interior(e.b);
+            if (range_empty(r)) return set_error(OCN_ERR_ARG, "ensemble launch: empty block");
+            // the odd steps' table, as launch_onepass_multi builds it
+            std::vector<void *> odd(e.ptr, e.ptr + e.nptr);
+            for (const auto &pr : {std::make_pair(OCN_SSH, OCN_SSHN), std::make_pair(OCN_UBRTR, OCN_UBRTRN),
+                                   std::make_pair(OCN_VBRTR, OCN_VBRTRN)})
+                std::swap(odd[ocn_field_slot(pr.first)], odd[ocn_field_slot(pr.second)]);
+            double *alt[3] = {e.alt[0], e.alt[1], e.alt[2]};
+            const int ids[3] = {OCN_SSHP, OCN_UBRTRP, OCN_VBRTRP};
+            for (int j = 0; j < 3; ++j) std::swap(odd[ocn_field_slot(ids[j])], *(void **)&alt[j]);
+            const Tab<true> t0 = make_tab<true>(e.ptr, e.nptr, e.cp->bits, e.cp->rows, block_rows(e.b), 0);
+            const Tab<true> t1 = make_tab<true>(odd.data(), e.nptr, e.cp->bits, e.cp->rows, block_rows(e.b), 0);
+            int32_t *const nbad = check ? e.nbad : nullptr;
+            const Body k0{*e.b, t0, sw, tau, nbad, e.alt[0], e.alt[1], e.alt[2], e.kc, nullptr, 0, 0u};
+            const Body k1{*e.b, t1, sw, tau, nbad, alt[0], alt[1], alt[2], e.kc, nullptr, 0, 0u};
+            std::memcpy((void *)&tab[i].b[0], &k0, sizeof(Body));
+            std::memcpy((void *)&tab[i].b[1], &k1, sizeof(Body));
+            tab[i].R = march_rect<Body>(e.b, r, rows, true);
+            tab[i].bar = e.ctr;
+            tab[i].err = e.err;
+            tab[i].spin = e.spin < 1 ? 1 : e.spin;
+            tab[i].pad = 0;
+            if (tab[i].R.tiles != multi_tiles(r, rows) || (i && tab[i].R.tiles != tiles))
+                return set_error(OCN_ERR_ARG, "ensemble launch: the members' tile counts differ");
+            tiles = tab[i].R.tiles;
+        }
+        // residency from the grid size alone, as the single-member launch: every workgroup at once
+        if ((long)n * tiles > capacity || capacity > onepass_multi_b_capacity())
+            return set_error(OCN_ERR_ARG, "ensemble launch: grid larger than the resident capacity");
+        RC_K(check_hip(hipMemcpyAsync(d_tab, h_tab, sizeof(Entry) * (size_t)n, hipMemcpyHostToDevice, s),
+                       "ensemble launch: member table"));
+        count_launch();
+        k_march_multi_b<Body><<<dim3((unsigned)(n * tiles)), dim3(256), 0, s>>>((const Entry *)d_tab, tiles, nsteps);
+        return check_hip(hipGetLastError(), "ensemble launch");
+    });
+}
+
 // Rows per workgroup tile of the two-step launch: the fewest iterations in total, counting
 // ceil(waves / slots) rounds of rows + 8 iterations each (MarchStep::march); mult = blocks of this
 // size in one launch (a batch: one_step_x4 on several blocks of a device)

@@ -1,0 +1,153 @@
+"""OceanEnsemble: members of one small basin stepped together (libocn_sw ocn_ens_*).
+
+A basin of the Black Sea's size fills a tenth of an MI355X, and its multi-step launch is bound by the
+grid barrier between the steps.  An ensemble's members -- the same basin, mask and decomposition,
+different initial state, forcing or bathymetry -- go as one launch per group of members, each member
+with a barrier of its own inside it.  The reference runs one model per process and has no counterpart.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, lib
+from .config import BasinConfig, ParallelConfig, SWConfig
+from .model import BlockInfo, OceanModel
+
+
+class _Member(OceanModel):
+    """An OceanModel over a handle borrowed from an ensemble: every method works; close() leaves the
+    context to the ensemble."""
+
+    def __init__(self, ctx, basin, sw, par, device):   # noqa: super().__init__ creates a context of its own
+        L = lib()
+        self.basin, self.sw, self.par = basin, sw, par
+        self.rank, self.nranks, self.device = 0, 1, device
+        self.field_names = _lib.R4_NAMES + _lib.R8_NAMES + (_lib.tracer_names(sw.tracer_num) if sw.use_tracers > 0 else [])
+        self._mask = None
+        self.ctx = ctx
+        if basin.topography is not None:
+            t = np.asfortranarray(basin.topography, dtype=np.float32)
+            if t.shape != (basin.nx - 4, basin.ny - 4):
+                raise ValueError(f"topography shape {t.shape} != (nx-4, ny-4) = {(basin.nx - 4, basin.ny - 4)}")
+            self._topo = t
+            check(L.ocn_ctx_set_topography(self.ctx, t.ctypes.data_as(C.c_void_p), t.size), "ocn_ctx_set_topography")
+        self.blocks = []
+        for k in range(L.ocn_ctx_block_count(self.ctx)):
+            bi = _lib.OcnBlockInfo()
+            check(L.ocn_ctx_block_info(self.ctx, k, C.byref(bi)), "ocn_ctx_block_info")
+            g = bi.geom
+            self.blocks.append(BlockInfo(k, bi.bm, bi.bn, g.nx_start, g.nx_end, g.ny_start, g.ny_end, g.bnd_x1,
+                                         g.bnd_x2, g.bnd_y1, g.bnd_y2, g.pitch, tuple(bi.nbr_rank),
+                                         tuple(bi.nbr_k)))
+
+    def close(self):
+        self.ctx = None
+
+
+def plan(block: _lib.OcnBlock, variants, capacity: int) -> list[dict]:
+    """ocn_ens_plan (pure, no device): the launch groups of members with the given variant ids
+    (negative: not eligible) on `block` within `capacity` workgroups."""
+    v = (C.c_int32 * len(variants))(*[int(x) for x in variants])
+    n = C.c_int32(0)
+    check(lib().ocn_ens_plan(C.byref(block), v, len(variants), int(capacity), None, 0, C.byref(n)), "ocn_ens_plan")
+    out = (_lib.OcnEnsGroup * max(n.value, 1))()
+    check(lib().ocn_ens_plan(C.byref(block), v, len(variants), int(capacity), out, n.value, C.byref(n)), "ocn_ens_plan")
+    return [{"variant": int(g.variant), "rows": int(g.rows), "tiles": int(g.tiles),
+             "members": [int(g.member[j]) for j in range(g.members)],
+             "first_tile": [int(g.first_tile[j]) for j in range(g.members)]} for g in out[:n.value]]
+
+
+class OceanEnsemble:
+    """``OceanEnsemble(basin, sw, par, members, device=0)``: `members` models of one basin on one GPU.
+
+    ``.members`` are OceanModel objects over the ensemble's contexts (upload, download, options,
+    even ``step`` for one member alone); ``step`` steps them all, the members that would each run a
+    multi-step launch in one launch per group."""
+
+    def __init__(self, basin: BasinConfig, sw: SWConfig = SWConfig(), par: ParallelConfig = ParallelConfig(),
+                 members: int = 1, device: int = 0):
+        L = lib()
+        self.basin, self.sw, self.par, self.device = basin, sw, par, device
+        cb = _lib.OcnBasin(basin.nx, basin.ny, basin.dxst, basin.dyst, basin.rlon, basin.rlat, basin.curve_grid,
+                           basin.rotation_on_lon, basin.rotation_on_lat)
+        cs = _lib.OcnSwParams(sw.full_free_surface, sw.trans_terms, sw.ksw_lat, sw.time_smooth, sw.lvisc_2,
+                              sw.use_tracers, sw.tracer_num)
+        cd = _lib.OcnDecomp(par.bppnx, par.bppny, 1, 0, device)
+        mptr = None
+        if basin.mask is not None:
+            self._mask = np.asfortranarray(basin.mask.astype(np.int32))
+            if self._mask.shape != (basin.nx, basin.ny):
+                raise ValueError(f"mask shape {self._mask.shape} != (nx, ny) = {(basin.nx, basin.ny)}")
+            mptr = self._mask.ctypes.data_as(C.c_void_p)
+        h = C.c_void_p()
+        self.ens = None
+        check(L.ocn_ens_create(C.byref(cb), C.byref(cs), C.byref(cd), mptr, int(members), C.byref(h)), "ocn_ens_create")
+        self.ens = h
+        self.members: list[OceanModel] = []
+        for i in range(L.ocn_ens_size(self.ens)):
+            c = C.c_void_p()
+            check(L.ocn_ens_member(self.ens, i, C.byref(c)), "ocn_ens_member")
+            self.members.append(_Member(c, basin, sw, par, device))
+
+    def close(self):
+        if getattr(self, "ens", None):
+            for m in self.members:
+                m.close()
+            lib().ocn_ens_destroy(self.ens)
+            self.ens = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return len(self.members)
+
+    def init(self):
+        check(lib().ocn_ens_init_state(self.ens), "ocn_ens_init_state")
+        return self
+
+    def step(self, nsteps: int = 1, tau: float = 1.0, check_every: int = 1):
+        check(lib().ocn_ens_step(self.ens, tau, nsteps, check_every), "ocn_ens_step")
+        return self
+
+    def complete(self):
+        check(lib().ocn_ens_complete(self.ens), "ocn_ens_complete")
+        return self
+
+    def synchronize(self, raise_on_error: bool = False) -> list[int]:
+        """Wait once; the members' statuses (OCN_OK, OCN_ERR_BLOWUP, OCN_ERR_HIP).  One member's blow-up
+        does not disturb the others, so by default nothing is raised."""
+        st = (C.c_int32 * len(self.members))()
+        rc = lib().ocn_ens_synchronize(self.ens, st)
+        if raise_on_error:
+            check(rc, "ocn_ens_synchronize")
+        return [int(x) for x in st]
+
+    def set_capacity(self, workgroups: int = 0):
+        """A cap on the workgroups of one ensemble launch (0: none); only ever lowers the device's."""
+        check(lib().ocn_ens_set_option(self.ens, _lib.ENS_OPT_CAPACITY, int(workgroups)), "ocn_ens_set_option")
+        return self
+
+    def set_max_group(self, members: int = 0):
+        """Measurements: at most this many planned members are planned together (0: all), so several
+        shorter launches can be timed against one taller one."""
+        check(lib().ocn_ens_set_option(self.ens, _lib.ENS_OPT_MAX_GROUP, int(members)), "ocn_ens_set_option")
+        return self
+
+    def info(self) -> dict:
+        """The last step(): batched launches (groups), members in them (batched), rows per wave tile, tiles
+        per member and members of the largest group, and the capacity in effect."""
+        i = _lib.OcnEnsInfo()
+        check(lib().ocn_ens_info(self.ens, C.byref(i)), "ocn_ens_info")
+        return {"members": int(i.members), "groups": int(i.groups), "batched": int(i.batched), "rows": int(i.rows),
+                "tiles": int(i.tiles), "max_group": int(i.max_group), "capacity": int(i.capacity)}
+
+    @property
+    def interior_cells(self) -> int:
+        return sum(m.interior_cells for m in self.members)
