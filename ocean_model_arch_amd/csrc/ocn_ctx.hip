@@ -1919,6 +1919,17 @@ static bool flip_eligible(ocn_ctx *c)
     return c->flip && c->fused && c->compact && c->march;
 }
 
+// The reuse steps (sw_stencils.h) leave hh_update's n-level depths unexchanged: a9 then forms the
+// p levels on the halo ring from stale values, which is harmless only because uv_trans's exchange of
+// hhu_p / hhv_p / hhh_p rewrites them before the call ends.  With trans_terms = 0 the reference makes
+// no such exchange and a9's ring values stay in the arrays, so with neighbours (other blocks or
+// ranks: the same answer on every rank) each step is a standard fused step with hh_update and its
+// exchange -- no reuse steps and no role-flip steps (whose fused hh_init + A is a reuse step's).
+static bool reuse_allowed(const ocn_ctx *c)
+{
+    return c->sw.trans_terms > 0 || !(has_exchange(c) || has_comm(c));
+}
+
 // tracer steps (run_tracer_step, below): the pending one of the current state, and the tracer fields
 // the exchanges of a one-pass call carry with the state
 static int run_tracer_step(ocn_ctx *c, double tau);
@@ -2613,7 +2624,7 @@ static int one_step_fused(ocn_ctx *c, double tau, const StepKind &k)
     const bool full_c2 = last || sw.use_tracers > 0;   // tracers read hh_init's hhq_p every step
     // sw_stencils.h "reuse" steps: hun/hvn/hhn are hh_init's hu/hv/hh of the previous step.  Not
     // on the first step of a call (the host may have changed ssh since) nor on the last one.
-    const bool reuse = sw.full_free_surface == 1 && !first && !last;
+    const bool reuse = sw.full_free_surface == 1 && !first && !last && reuse_allowed(c);
     const std::vector<int> &sync_a = reuse ? c->sync_a_reuse : c->sync_a;
     if (flip) {
         if (last) return set_error(OCN_ERR_STATE, "role-flip step on a last step");
@@ -3877,7 +3888,7 @@ static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every
                         (has_exchange(c) ? x2_ok && c->last_hybrid
                                          : !c->ring_sea && (c->last_hybrid || (c->blocks.size() == 1 && !has_comm(c)))));
     auto decide = [&](int n) {
-        flip_call = n >= 2 && eligible && c->coherent;
+        flip_call = n >= 2 && eligible && c->coherent && (c->sw.full_free_surface != 1 || reuse_allowed(c));
         // role-flip calls with full_free_surface = 1 fuse each step's hh_init with the next step's A;
         // their reuse steps recompute hhq / hhu_p / hhv_p in fused B, which then filters sshp into
         // the second buffer (the ring launch completes it on the halo ring)

@@ -7,8 +7,10 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 E2E_CASES = ["box40x32_b2x2_s5", "box70x54_b1x1_s20", "box70x54_b3x2_s20",
-             "box48x40_flags000_s10", "box48x40_cart_s10", "bs_b1x1_s60", "bs_b4x2_s60"]
-TRACER_E2E_CASES = ["box40x32_tr2_s5", "box70x54_b3x2_tr_s20", "bs_b4x2_tr_s60"]
+             "box48x40_flags000_s10", "box48x40_cart_s10", "bs_b1x1_s60", "bs_b4x2_s60",
+             # a rough coast (tests/shapes.py mask kind "rough"), exactly one flag off in each
+             "coast40x32_ffs0_s5", "coast40x32_trans0_s5", "coast40x32_ksw0_s5"]
+TRACER_E2E_CASES = ["box40x32_tr2_s5", "box70x54_b3x2_tr_s20", "bs_b4x2_tr_s60", "coast40x32_b2x2_tr_s5"]
 # the shipped run length (ocean_run.par: 604 steps), Black Sea, 1 block / 4x2 blocks + 1 tracer
 LONG_CASES = ["bs_b1x1_s604", "bs_b4x2_tr_s604"]
 # step 0: init_grid_data + init_ocean_data only (the initial state)

@@ -299,6 +299,15 @@ CASES = {
     "box70x54_topo_b1x1_s20": (dict(BOX, nx=70, ny=54, topo="wave"), SW_DEFAULT, (1, 1), 20, True),
     "box70x54_topo_b3x2_s20": (dict(BOX, nx=70, ny=54, topo="wave"), SW_DEFAULT, (3, 2), 20, False),
     "bs_topo_b4x2_s60": (dict(BS, topo="wave"), SW_DEFAULT, (4, 2), 60, False),
+    # a rough coast (tests/shapes.py mask kind "rough" on the 36 x 28 interior, written as the run's mask
+    # file): pins the oracle at one-point seas and islands and at each single flag off
+    # ("r8": the full arrays of the real(8) fields but the tracer step's scratch fluxes; those and the static
+    # real(4) masks and metrics as digests only, which keeps the file within the size of
+    # e2e_box40x32_b2x2_s5.npz with the tracer's fields in it -- every test compares the digests)
+    "coast40x32_b2x2_tr_s5": (dict(BOX, nx=40, ny=32, mask="rough"), dict(SW_DEFAULT, tr=1, trn=1), (2, 2), 5, "r8"),
+    "coast40x32_ffs0_s5": (dict(BOX, nx=40, ny=32, mask="rough"), dict(SW_DEFAULT, ffs=0), (1, 1), 5, True),
+    "coast40x32_trans0_s5": (dict(BOX, nx=40, ny=32, mask="rough"), dict(SW_DEFAULT, trans=0), (1, 1), 5, True),
+    "coast40x32_ksw0_s5": (dict(BOX, nx=40, ny=32, mask="rough"), dict(SW_DEFAULT, ksw=0), (1, 1), 5, True),
 }
 PROGNOSTIC = ["ssh", "sshp", "ubrtr", "ubrtrp", "vbrtr", "vbrtrp", "ff1_1", "ff1p_1"]
 
@@ -336,10 +345,32 @@ def digest_dump(path):
     return out
 
 
+def shape_mask(kind, nx, ny):
+    """A mask kind of tests/shapes.py on the (nx - 4) x (ny - 4) interior: int32 (nx, ny), 1 = land."""
+    from tests import shapes as S
+    assert kind in S.MASK_KINDS, kind
+    return S.mask_of(S.Shape(nx - 4, ny - 4, mask=kind))
+
+
+def write_mask_file(path, m, note):
+    """The reference's text format (tools/io.f90:61-70): a comment line, then ny rows of nx digits, the
+    top row (n = ny) first."""
+    with open(path, "w") as f:
+        f.write(note + "\n")
+        for n in range(m.shape[1] - 1, -1, -1):
+            f.write("".join(str(int(v)) for v in m[:, n]) + "\n")
+
+
 def gen_e2e(name, basin, sw, bxy, steps, full):
     d = tempfile.mkdtemp()
     topo = None
+    mask_name = "none" if basin["mask"] == "none" else "BS"
     try:
+        if basin["mask"] != "none" and not os.path.isabs(basin["mask"]):   # a generated mask kind
+            mask_name = basin["mask"]
+            write_mask_file(os.path.join(d, "mask.txt"), shape_mask(mask_name, basin["nx"], basin["ny"]),
+                            f"mask kind {mask_name} of tests/shapes.py")
+            basin = dict(basin, mask=os.path.join(d, "mask.txt"))
         if basin.get("topo", "none") != "none":
             topo = topography(basin["nx"], basin["ny"])
             topo.ravel(order="F").tofile(os.path.join(d, "topo.dat"))
@@ -354,16 +385,18 @@ def gen_e2e(name, basin, sw, bxy, steps, full):
             blocks = digest_dump(os.path.join(d, "dump.bin"))
         else:
             blocks = read_dump(os.path.join(d, "dump.bin"))
+        m = None
+        if basin["mask"] != "none":
+            from oracle.oracle import read_mask_file
+            m = read_mask_file(basin["mask"], basin["nx"], basin["ny"])
     finally:
         shutil.rmtree(d)
     out = {"meta/basin": np.array(repr({k: v for k, v in basin.items() if k not in ("mask", "topo")} |
-                                         {"mask": "BS" if basin["mask"] != "none" else "none"})),
+                                         {"mask": mask_name})),
            "meta/sw": np.array(repr(sw)), "meta/bxy": np.array(bxy, np.int32), "meta/steps": np.int32(steps)}
     if topo is not None:
         out["in/topo"] = topo
-    if basin["mask"] != "none":
-        from oracle.oracle import read_mask_file
-        m = read_mask_file(basin["mask"], basin["nx"], basin["ny"])
+    if m is not None:
         out["in/mask_packed"] = np.packbits(m.ravel(order="F").astype(np.uint8))
     for info, f in blocks:
         key = f"{info['bm']}_{info['bn']}"
@@ -371,7 +404,7 @@ def gen_e2e(name, basin, sw, bxy, steps, full):
                                        np.int32)
         for nm, a in f.items():
             out[f"b{key}/sha/{nm}"] = np.array(a if isinstance(a, str) else digest(a))
-            if full is True or (full is False and nm in PROGNOSTIC):
+            if full is True or (full == "r8" and nm not in R4_FIELDS + ["flux_x", "flux_y"]) or (full is False and nm in PROGNOSTIC):
                 out[f"b{key}/{nm}"] = a
     path = os.path.join(HERE, f"e2e_{name}.npz")
     np.savez_compressed(path, **out)

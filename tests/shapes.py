@@ -3,8 +3,8 @@ bitwise comparison -- shared by tests/test_shapes_cpu.py (oracle only) and tests
 
 A Shape is an interior W x H (BasinConfig(nx=W+4, ny=H+4)), a block grid, a tracer count and a
 mask kind (None: the closed box; "drop": the centre and the (1, 1) corner block of the grid all land,
-which the decomposition drops).  The CPU oracle (oracle/oracle.py, pinned bit for bit to the compiled
-reference by tests/test_oracle_pinned.py) is the reference.
+which the decomposition drops; the coast kinds of MASK_KINDS below).  The CPU oracle (oracle/oracle.py,
+pinned bit for bit to the compiled reference by tests/test_oracle_pinned.py) is the reference.
 
 Inputs are cut from GLOBAL (nx, ny) arrays of numpy.random.default_rng(seed).uniform(-1, 1), one
 seed per field: block (bm, bn) gets [bnd_x1-1:bnd_x2, bnd_y1-1:bnd_y2], so the halos of neighbouring
@@ -20,6 +20,41 @@ Classes:
            tests cover
   hr       hhq_rest += 5 (1 + r) where hhq_rest > 0 (the h_r-read variant)
   general  noise + hr + mu = 50 (1 + r), RHSx = 2e-7 r on lcu, RHSy = 2e-7 r on lcv
+  still    still water with velocities below udiv's range (tests/test_gpu_coast.py only): ssh = sshn =
+           sshp = 0, ubrtr = ubrtrn = ubrtrp = 1e-290 (1 + 0.5 r) on lcu, vbrtr likewise on lcv.  The
+           state stays below 2^-900 over the sweep's runs (tests/test_shapes_cpu.py asserts it after
+           every step), so every row with a wet velocity point takes BOTH IEEE re-runs of
+           sw_kernels.hip MarchStep::iteration in every step of every call -- established by reading
+           derive<E> and step<E>, not by a counter:
+             derive<true>: its dividends up(n+1), vp(n+1), up(n+2) are the velocities themselves, nonzero
+               and below 2^-900; the depth averages sh, a_u0 .. a_v1 stay normal (h_r = 100);
+             step<true>: a_ssh = u hu dyh - (its left lane's) + v hv dxh - (the row before's), about
+               1e-290 x 100 x 250 = 2.5e-286 < 2^-900 wherever the fluxes do not cancel exactly; uv_diff2's
+               a1 .. a4 are +-0 (mu = 0: every term is mu x ...), which exp_check passes.
+           The general variant cannot be kept tiny with a forcing of 2e-7, and still + hr was not needed:
+           the h_r-read variant runs the same derive / step code (its template flag changes where h_r
+           comes from, not a dividend), so neither combination is a class of its own.
+  abyss    still, deeper: velocities of 2e-305 (1 + 0.5 r) and a uniform mu = 5e3 (still a known-constant
+           variant: sw_kernels.hip FallbackCheck only asks that mu be one value, so pairs, x4 and the
+           ensemble launch stay available).  Why it exists: udiv's residual fma(q, d, -x) is exact down
+           to about |x| = 2^-969, far below the 2^-900 the range check uses, so at still's 1e-290 the
+           fast path and the IEEE re-run give the same bits and a re-run that does nothing goes
+           unnoticed (measured: a library whose derive<true> re-run never runs passed every still
+           case).  At 2e-305 the quotients are still normal but the residual is a subnormal of a few
+           bits: about 1 quotient in 1000 differs from IEEE division without the re-run (checked on the
+           host over these magnitudes and the metrics' divisors).  mu = 5e3 (mu dt / dx^2 about 0.08:
+           stable, the state stays between 1e-305 and 4e-305 over the runs) makes a5's quotients feed
+           back into the velocities in EVERY step -- with mu = 0 they reach only str_t / str_s of a
+           call's last step -- and puts uv_diff2's dividends a1 .. a4 (step<true>) out of range too.
+
+Coast mask kinds (MASK_KINDS; each keeps the 2-point land frame; i, j are the 0-based interior indices):
+  rough       land with probability 0.15 per interior point (default_rng, a fixed seed per W x H):
+              one-point seas, one-point islands, diagonal touches
+  checker     land where i + j is odd: every sea point isolated, no u, v or vorticity point wet
+  diag        land where (i - j) % 7 == 0: diagonal walls across every tile edge, every h-point corner
+              configuration
+  comb        land where i is odd and j % 5 != 0: channels one point wide, joined every fifth row
+  rough_drop  rough plus the two all-land blocks of "drop"
 """
 import functools
 from typing import NamedTuple, Optional, Tuple
@@ -29,6 +64,11 @@ import numpy as np
 from tests.test_gpu_parity import bits_equal
 
 CLASSES = ("plain", "noise", "hr", "general")
+COAST_CLASSES = CLASSES + ("still", "abyss")   # still, abyss: the coastline sweep only
+MASK_KINDS = ("rough", "checker", "diag", "comb", "rough_drop")
+# rough's seed is 1000 W + H + ROUGH_SEED_BUMP.get((W, H), 0): bumped where the plain seed leaves a tile
+# edge of tests/test_shapes_cpu.py without a land / sea change or an h-point class empty
+ROUGH_SEED_BUMP = {(361, 12): 1}   # (seed 361012 has no land / sea change across columns 116 / 117)
 SEEDS = {"ssh": 101, "ubrtr": 102, "vbrtr": 103, "hhq_rest": 104, "mu": 105, "RHSx": 106, "RHSy": 107}
 SKIP = ("lu1", "rlh_c")   # oracle scratch, not fields of the model
 
@@ -58,6 +98,30 @@ TRACER_GRIDS = [s._replace(tracers=t) for s in (Shape(13, 11, (3, 3)), Shape(17,
 RANK_GRIDS = [Shape(7, 9, (3, 2)), Shape(9, 8, (2, 2)), Shape(17, 19, (2, 2))]
 SINGLE_STEPS, GRID_STEPS = 8, 7   # the longest run of the sweep on a shape (calls [2, 6] / [2, 5])
 
+# ---------------------------------------------------------------- the coastline sweep's shapes
+# (tests/test_gpu_coast.py; the smallest shapes of the sweep above at which each tile edge exists)
+COAST_SINGLE = [Shape(w, h, mask=k) for w, h in [(5, 4), (61, 9), (61, 33), (117, 31), (121, 65), (233, 129)]
+                for k in ("rough", "checker", "diag", "comb")]
+COAST_DROPPED = Shape(36, 36, (3, 3), 0, "rough_drop")
+COAST_GRIDS = [Shape(w, h, g, 0, k) for w, h, g in [(13, 11, (3, 3)), (17, 19, (2, 2)), (27, 27, (3, 3)),
+                                                    (122, 10, (2, 1)), (361, 12, (2, 1))]
+               for k in ("rough", "diag")] + [COAST_DROPPED]
+COAST_TRACER_GRIDS = [s._replace(tracers=t) for s in (Shape(17, 19, (2, 2), 0, "rough"), COAST_DROPPED) for t in (1, 2)]
+COAST_RANK_GRIDS = [Shape(9, 8, (2, 2), 0, "rough"), Shape(17, 19, (2, 2), 0, "rough")]
+COAST_ENSEMBLES = [Shape(w, h, mask=k) for w, h in [(61, 9), (121, 65)] for k in ("rough", "comb")]
+COAST_ENSEMBLE_CLASSES = ["plain", "noise", "still", "hr", "general", "noise"]
+COAST_FLAG_SHAPES = [Shape(61, 33, mask="rough"), Shape(17, 19, (2, 2), 1, "rough")]
+FLAG_SETTINGS = [(a, b, c) for a in (1, 0) for b in (1, 0) for c in (1, 0)]   # (full_free_surface, trans_terms, ksw_lat)
+STILL_SHAPES = [(61, 33), (121, 65), (17, 19), (36, 36)]   # W x H of the shapes that also run still and abyss
+COAST_ENSEMBLE_DEEP = ["abyss", "noise", "abyss"]   # a second ensemble: one known-constant group
+
+
+def coast_classes(shape):
+    """The input classes the coastline sweep runs on a shape: noise and general on one block, noise, hr
+    and general on a grid, and still and abyss on STILL_SHAPES."""
+    base = ("noise", "general") if shape.grid == (1, 1) else ("noise", "hr", "general")
+    return base + (("still", "abyss") if (shape.W, shape.H) in STILL_SHAPES else ())
+
 
 def block_sizes(shape):
     """(widths, heights) of the grid's blocks (decomposition.f90:448-482)."""
@@ -65,22 +129,60 @@ def block_sizes(shape):
     return uniform_sizes(shape.W, shape.grid[0]), uniform_sizes(shape.H, shape.grid[1])
 
 
-def dropped_blocks(shape):
-    return [] if shape.mask != "drop" else [((shape.grid[0] + 1) // 2, (shape.grid[1] + 1) // 2), (1, 1)]
+def _frame(shape):
+    m = np.zeros((shape.W + 4, shape.H + 4), dtype=np.int32, order="F")
+    m[:2, :] = 1; m[-2:, :] = 1; m[:, :2] = 1; m[:, -2:] = 1
+    return m
+
+
+def _block_origin(shape, bm, bn):
+    xs, ys = block_sizes(shape)
+    return 2 + sum(xs[:bm - 1]), 2 + sum(ys[:bn - 1]), xs[bm - 1], ys[bn - 1]
+
+
+@functools.lru_cache(maxsize=None)
+def _mask(shape):
+    W, H = shape.W, shape.H
+    m = _frame(shape)
+    i, j = np.meshgrid(np.arange(W), np.arange(H), indexing="ij")
+    kind = shape.mask
+    if kind in ("rough", "rough_drop"):
+        seed = 1000 * W + H + ROUGH_SEED_BUMP.get((W, H), 0)
+        land = np.random.default_rng(seed).random((W, H)) < 0.15
+    elif kind == "checker":
+        land = (i + j) % 2 == 1
+    elif kind == "diag":
+        land = (i - j) % 7 == 0
+    elif kind == "comb":
+        land = (i % 2 == 1) & (j % 5 != 0)
+    else:
+        assert kind == "drop", kind
+        land = np.zeros((W, H), dtype=bool)
+    m[2:-2, 2:-2] = land
+    if kind in ("drop", "rough_drop"):
+        for bm, bn in [((shape.grid[0] + 1) // 2, (shape.grid[1] + 1) // 2), (1, 1)]:
+            x0, y0, w, h = _block_origin(shape, bm, bn)
+            m[x0:x0 + w, y0:y0 + h] = 1
+    m.setflags(write=False)
+    return m
 
 
 def mask_of(shape):
-    """None (the box), or the box with the dropped blocks' interiors all land."""
+    """None (the box), or the int32 (W + 4, H + 4) mask of the shape's kind (1 = land)."""
+    return None if shape.mask is None else _mask(shape).copy(order="F")
+
+
+def dropped_blocks(shape):
+    """The blocks the decomposition drops: those whose interior is all land in the mask itself."""
     if shape.mask is None:
-        return None
-    assert shape.mask == "drop", shape.mask
-    m = np.zeros((shape.W + 4, shape.H + 4), dtype=np.int32, order="F")
-    m[:2, :] = 1; m[-2:, :] = 1; m[:, :2] = 1; m[:, -2:] = 1
-    xs, ys = block_sizes(shape)
-    for bm, bn in dropped_blocks(shape):
-        x0, y0 = 2 + sum(xs[:bm - 1]), 2 + sum(ys[:bn - 1])
-        m[x0:x0 + xs[bm - 1], y0:y0 + ys[bn - 1]] = 1
-    return m
+        return []
+    m, out = _mask(shape), []
+    for bm in range(1, shape.grid[0] + 1):
+        for bn in range(1, shape.grid[1] + 1):
+            x0, y0, w, h = _block_origin(shape, bm, bn)
+            if m[x0:x0 + w, y0:y0 + h].all():
+                out.append((bm, bn))
+    return out
 
 
 def min_block(shape):
@@ -105,16 +207,25 @@ def expect_x4(shape, cls, x4, peers=False):
 
 
 # ---------------------------------------------------------------- oracle twin, inputs, reference
-def oracle_model(shape):
+def sw_kwargs(shape, flags=(1, 1, 1)):
+    """SWConfig's keywords (the oracle's and the library's alike) for the shape's tracers and the
+    (full_free_surface, trans_terms, ksw_lat) setting."""
+    kw = dict(use_tracers=1, tracer_num=shape.tracers) if shape.tracers else {}
+    if tuple(flags) != (1, 1, 1):
+        kw.update(full_free_surface=flags[0], trans_terms=flags[1], ksw_lat=flags[2])
+    return kw
+
+
+def oracle_model(shape, flags=(1, 1, 1)):
     """An initialised oracle.OracleModel on the shape's box, block grid and tracer count."""
     from oracle import oracle as O
-    sw = O.SWConfig(use_tracers=1, tracer_num=shape.tracers) if shape.tracers else O.SWConfig()
+    sw = O.SWConfig(**sw_kwargs(shape, flags))
     return O.OracleModel(O.BasinConfig(nx=shape.W + 4, ny=shape.H + 4, mask=mask_of(shape)), sw, *shape.grid).init()
 
 
 def uploads(cls, om):
     """{(bm, bn): {field: array}} for input class cls, from the initial state of oracle model om."""
-    assert cls in CLASSES, cls
+    assert cls in COAST_CLASSES, cls
     if cls == "plain":
         return {}
     nx, ny = om.basin.nx, om.basin.ny
@@ -135,6 +246,17 @@ def uploads(cls, om):
                 a[sel] += amp * cut(nm)[sel]
                 u[nm] = a
                 u[other] = a.copy(order="F")
+        if cls in ("still", "abyss"):
+            for nm in ("ssh", "sshn", "sshp"):
+                u[nm] = np.zeros_like(f[nm], order="F")
+            for nm, msk in (("ubrtr", "lcu"), ("vbrtr", "lcv")):
+                a = np.zeros_like(f[nm], order="F")
+                sel = f[msk] > 0.5
+                a[sel] = (1.0e-290 if cls == "still" else 2.0e-305) * (1.0 + 0.5 * cut(nm)[sel])
+                for role in (nm, nm + "n", nm + "p"):
+                    u[role] = a.copy(order="F")
+        if cls == "abyss":
+            u["mu"] = np.full_like(f["mu"], 5.0e3, order="F")
         if cls in ("hr", "general"):
             a = f["hhq_rest"].copy(order="F")
             sel = a > 0.0
@@ -151,16 +273,16 @@ def uploads(cls, om):
     return out
 
 
-@functools.lru_cache(maxsize=8)
+@functools.lru_cache(maxsize=16)
 def uploads_for(shape, cls):
     return uploads(cls, oracle_model(shape))
 
 
-@functools.lru_cache(maxsize=8)
-def reference(shape, cls, steps):
+@functools.lru_cache(maxsize=16)
+def reference(shape, cls, steps, flags=(1, 1, 1)):
     """{(bm, bn): {field: array}} of the oracle after `steps` steps (tau = 1) from the class's inputs.
-    Computed once per (shape, class, steps) and shared; callers must not write into it."""
-    om = oracle_model(shape)
+    Computed once per (shape, class, steps, flags) and shared; callers must not write into it."""
+    om = oracle_model(shape, flags)
     for k, b in enumerate(om.blocks):
         for nm, a in uploads_for(shape, cls).get((b.bm, b.bn), {}).items():
             om.f[k][nm][...] = a

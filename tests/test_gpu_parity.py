@@ -225,7 +225,10 @@ def test_end_to_end_matches_reference(amd, name, mode):
     assert not bad, f"{name}: fields differ from the reference: {bad}"
     if mode in ("compact", "nox2", "noonepass", "nolast", "norecompute", "serial", "overlap2", "nobatch"):   # tracer runs included
         assert flip_used, f"{name}: role-flip steps not used"
-    full_sw = case["sw"]["trans_terms"] > 0 and case["sw"]["ksw_lat"] > 0 and not case["sw"].get("use_tracers", 0)
+    # (one-pass steps need all three terms on: ocn_ctx.hip decide -- coast40x32_ffs0_s5 is the first case
+    # with only full_free_surface off)
+    full_sw = case["sw"]["full_free_surface"] > 0 and case["sw"]["trans_terms"] > 0 and case["sw"]["ksw_lat"] > 0 and \
+        not case["sw"].get("use_tracers", 0)
     one_block = tuple(case["bxy"]) == (1, 1)
     if mode == "compact" and one_block and full_sw:
         assert one_used, f"{name}: one-pass steps not used"

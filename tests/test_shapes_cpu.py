@@ -5,6 +5,10 @@ call sequence without a FloatingPointError (check_ssh_err), keep every field fin
 and end with a nonzero ubrtr at every interior lcu point of every block -- rough data that moved
 everywhere, so a wrong column or row in a kernel cannot reproduce the reference's bits by symmetry
 or by leaving zeros.  The comparison helper must name exactly the block and field of a one-ulp change.
+
+The same for the coastline sweep (tests/test_gpu_coast.py): every (shape, mask, class) it runs is finite
+and trips no check_ssh_err; the still class stays below udiv's range after every step; every mask kind
+has what it promises (tests/shapes.py MASK_KINDS) and a land / sea change across the tiles' column edges.
 """
 import numpy as np
 import pytest
@@ -108,3 +112,98 @@ def test_comparison_names_the_block_and_field_of_a_one_ulp_change():
     assert r0 == 0.0 and not np.signbit(r0)
     copy[(3, 1)]["RHSx_dif"][0, 0] = -0.0
     assert S.mismatches(ref, get) == ["(3,1):RHSx_dif"]
+
+
+# ---------------------------------------------------------------- the coastline sweep's inputs
+COAST = [(s, S.SINGLE_STEPS) for s in S.COAST_SINGLE] + \
+        [(s, S.GRID_STEPS) for s in S.COAST_GRIDS + S.COAST_TRACER_GRIDS + S.COAST_RANK_GRIDS]
+COAST_ALL = [(s, n, c) for s, n in COAST for c in S.coast_classes(s)] + \
+            [(s, S.GRID_STEPS, c) for s in S.COAST_ENSEMBLES for c in ("plain", "noise", "still", "hr", "general", "abyss")]
+UDIV_MIN = 2.0 ** -900   # sw_kernels.hip kUdivMinExp: a nonzero dividend below it sends its row to the IEEE re-run
+
+
+def _sea_corners(mask):
+    """The number of sea corners (0 .. 4) of every h-point of a global mask (1 = land)."""
+    sea = 1 - mask
+    return sea[:-1, :-1] + sea[1:, :-1] + sea[:-1, 1:] + sea[1:, 1:]
+
+
+@pytest.mark.parametrize("shape,steps,cls", COAST_ALL, ids=[f"{s.id}-{c}" for s, _, c in COAST_ALL])
+def test_coast_inputs_are_sound(shape, steps, cls):
+    if cls not in ("still", "abyss"):
+        ref = S.reference(shape, cls, steps)   # raises FloatingPointError on a blow-up (check_ssh_err)
+        assert len(ref) == shape.grid[0] * shape.grid[1] - len(S.dropped_blocks(shape))
+        for (bm, bn), f in ref.items():
+            for nm, a in f.items():
+                assert np.isfinite(a).all(), f"({bm},{bn}):{nm} not finite"
+        return
+    # still, abyss: after EVERY step 0 < max |u|, |v| < 2^-900 on the wet points (no wet point: all zero), the
+    # number of nonzero velocity points unchanged, ssh below the range too
+    om = S.oracle_model(shape)
+    for k, b in enumerate(om.blocks):
+        for nm, a in S.uploads_for(shape, cls).get((b.bm, b.bn), {}).items():
+            om.f[k][nm][...] = a
+    count0 = None
+    for step in range(steps + 1):
+        if step:
+            om.step(1.0)
+        count = 0
+        for f in om.f:
+            for nm, msk in (("ubrtr", "lcu"), ("vbrtr", "lcv")):
+                a, wet = np.abs(f[nm]), f[msk] > 0.5
+                assert np.isfinite(f[nm]).all() and (a[~wet] == 0.0).all(), (step, nm)
+                if wet.any():
+                    assert 0.0 < a[wet].max() < UDIV_MIN, (step, nm, a[wet].max())
+                count += int((a != 0.0).sum())
+            assert np.abs(f["ssh"]).max() < UDIV_MIN, (step, np.abs(f["ssh"]).max())
+        count0 = count if count0 is None else count0
+        assert count == count0, (step, count, count0)
+    wet_any = any((f[m] > 0.5).any() for f in om.f for m in ("lcu", "lcv"))
+    assert wet_any == (shape.mask != "checker")
+
+
+COAST_MASKS = sorted({s._replace(tracers=0) for s, _ in COAST} | set(S.COAST_ENSEMBLES) | set(S.COAST_FLAG_SHAPES),
+                     key=lambda s: s.id)
+
+
+@pytest.mark.parametrize("shape", COAST_MASKS, ids=[s.id for s in COAST_MASKS])
+def test_coast_masks_have_what_their_kind_promises(shape):
+    shape = shape._replace(tracers=0)
+    m = S.mask_of(shape)
+    assert m.shape == (shape.W + 4, shape.H + 4) and m.dtype == np.int32
+    assert m[:2].all() and m[-2:].all() and m[:, :2].all() and m[:, -2:].all()   # the 2-point land frame
+    assert not m[2:-2, 2:-2].all()
+    corners = _sea_corners(m)
+    sea = 1 - m
+    if shape.mask in ("rough", "diag", "rough_drop"):
+        assert all((corners == k).any() for k in (1, 2, 3, 4)), [(k, int((corners == k).sum())) for k in range(5)]
+    if shape.mask == "checker":   # no u, v or vorticity point wet; every sea point isolated
+        assert not (sea[:-1] * sea[1:]).any() and not (sea[:, :-1] * sea[:, 1:]).any() and not (corners == 4).any()
+        om = S.oracle_model(shape)
+        assert all(f[nm].sum() == 0.0 for f in om.f for nm in ("lcu", "lcv", "luu")) and om.f[0]["lu"].sum() > 0
+    if shape.mask == "comb":   # channels one point wide: a sea point with land on both sides in x
+        inner = sea[1:-1] * (1 - sea[:-2]) * (1 - sea[2:])
+        assert inner.any() and not (corners == 4).any()
+        if shape.H >= 6:   # ... joined by a full row every fifth row
+            assert sea[2:-2, 2].all() and sea[2:-2, 7].all()
+    want = [(1, 1), (2, 2)] if shape.mask == "rough_drop" else []
+    assert sorted(S.dropped_blocks(shape)) == want
+    # a land / sea change across the output-column edges of the one-pass / x2 and the pair / x4 tiles
+    # (interior columns, 1-based: array index + 1), tests/test_gpu_shapes.py's docstring
+    if shape.W > 61:
+        for a in (59, 60, 63, 116):
+            assert (m[a + 1, 2:-2] != m[a + 2, 2:-2]).any(), f"no land / sea change across columns {a} / {a + 1}"
+
+
+def test_coast_dropped_blocks_come_from_the_mask():
+    """dropped_blocks reads the mask, not the kind's name: the paths expected of rough_drop are those of
+    drop, and a kind without all-land blocks drops none."""
+    assert sorted(S.dropped_blocks(S.DROPPED)) == sorted(S.dropped_blocks(S.COAST_DROPPED)) == [(1, 1), (2, 2)]
+    assert S.min_block(S.COAST_DROPPED) == (12, 12) and S.expect_x2(S.COAST_DROPPED)
+    assert S.expect_x4(S.COAST_DROPPED, "still", 1) and not S.expect_x4(S.COAST_DROPPED, "general", 1)
+    om = S.oracle_model(S.COAST_DROPPED)
+    assert {(b.bm, b.bn) for b in om.blocks} == {(bm, bn) for bm in (1, 2, 3) for bn in (1, 2, 3)} - {(1, 1), (2, 2)}
+    assert S.dropped_blocks(S.Shape(13, 11, (3, 3), 0, "diag")) == []
+    # the masks are functions of (W, H): the same array again, and a caller's copy
+    a, b = S.mask_of(S.COAST_DROPPED), S.mask_of(S.COAST_DROPPED)
+    assert a is not b and np.array_equal(a, b)
