@@ -4,12 +4,12 @@
 ! exactly the init sequence of model.f90:47-91 (mpp_init, basin.par/sw.par/parallel.par,
 ! read_global_mask, domain init, init_grid_data, init_ocean_data) and then NSTEPS model steps
 ! (model.f90:146-160: expl_shallow_water(tau), control/shallow_water/shallow_water.f90:22,
-! then expl_tracer(tau), control/tracer.f90:33), with tau = 1 s (ocean_run.par line 2).
+! then expl_tracer(tau), control/tracer.f90:33), with tau = 1 s (ocean_run.par line 2) unless TAU is given.
 ! Afterwards every field the step touches is dumped, per block, with its bounds, as raw
 ! little-endian stream records into DUMPFILE (header: block count, tracer count).
 !
 ! usage (in a directory holding basin.par, sw.par, parallel.par):
-!     ref_driver NSTEPS DUMPFILE
+!     ref_driver NSTEPS DUMPFILE [TAU]
 program ref_driver
     use kind_module, only: wp8 => SHR_KIND_R8, wp4 => SHR_KIND_R4
     use mpp_module
@@ -50,6 +50,9 @@ program ref_driver
     call init_ocean_data()
 
     tau = 1.0d0
+    if (command_argument_count() >= 3) then
+        call get_command_argument(3, arg); read(arg, *) tau
+    endif
     !$omp parallel default(shared) private(step)
     do step = 1, nsteps
         call expl_shallow_water(tau)

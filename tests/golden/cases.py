@@ -24,7 +24,14 @@ FULLSIZE_RANK_CASES = ["box2048_b2x2_s10", "box4096_b4x2_s12"]
 SHIPPED_CASES = ["box1521x1111_b1x1_s604", "box1521x1111_b2x2_s604"]
 # a non-uniform rest depth read from a basin.par topography file (control/init_data.f90:115-120)
 TOPO_CASES = ["box70x54_topo_b1x1_s20", "box70x54_topo_b3x2_s20", "bs_topo_b4x2_s60"]
-KERNEL_GEOMS = ["b66x50", "b1x1", "b130x7"]
+# the parameter sets of tests/shapes.py PARAMS on the rough-coast 40 x 32 basin (gen_golden.py param_cases):
+# 5 steps at the set's own tau (meta/tau), every array kept; coarse and equator on 2 x 2 blocks, one tracer
+# in tau075_ts03
+PARAM_CASES = ["coast40x32_tau03_s5", "coast40x32_tau075_ts03_s5", "coast40x32_tau2_s5", "coast40x32_tau025_ts0_s5",
+               "coast40x32_tau3_ts1_s5", "coast40x32_cart_s5", "coast40x32_south_s5", "coast40x32_b2x2_equator_s5",
+               "coast40x32_b2x2_coarse_s5", "coast40x32_polar_s5", "coast40x32_rot_s5"]
+# b34x9: generated with tau = 0.3, time_smooth = 0.3 (the others: 1.0, 0.5)
+KERNEL_GEOMS = ["b66x50", "b1x1", "b130x7", "b34x9"]
 KERNEL_NAMES = ["sw_update_ssh", "sw_update_uv", "sw_next_step", "uv_trans_vort", "uv_trans",
                 "uv_diff2", "stress_components", "hh_init", "hh_update", "hh_shift"]
 TRACER_KERNEL_NAMES = ["tran_diff_fluxes", "tran_diff_tracer", "tracer_next_step"]
@@ -35,12 +42,14 @@ def _f(s):
 
 
 def load_e2e(name):
-    """-> dict(basin=..., sw=..., bxy=(bx, by), steps=N, mask=int32 (nx,ny) or None, z=npz)."""
+    """-> dict(basin=..., sw=..., bxy=(bx, by), steps=N, tau=the run's tau (1.0 where the fixture records
+    none), mask=int32 (nx,ny) or None, z=npz); basin holds the rotation (0.0 where none is recorded)."""
     z = np.load(os.path.join(HERE, f"e2e_{name}.npz"))
     b = ast.literal_eval(str(z["meta/basin"]))
     sw = ast.literal_eval(str(z["meta/sw"]))
     basin = dict(nx=int(b["nx"]), ny=int(b["ny"]), dxst=_f(b["dxst"]), dyst=_f(b["dyst"]),
-                 rlon=_f(b["rlon"]), rlat=_f(b["rlat"]), curve_grid=int(b["curve"]))
+                 rlon=_f(b["rlon"]), rlat=_f(b["rlat"]), curve_grid=int(b["curve"]),
+                 rotation_on_lon=_f(b.get("rot_lon", 0.0)), rotation_on_lat=_f(b.get("rot_lat", 0.0)))
     mask = None
     if "in/mask_packed" in z.files:
         n = basin["nx"] * basin["ny"]
@@ -52,7 +61,7 @@ def load_e2e(name):
         swc.update(use_tracers=int(sw["tr"]), tracer_num=int(sw["trn"]))
     topo = z["in/topo"] if "in/topo" in z.files else None
     return dict(basin=basin, sw=swc, bxy=tuple(int(v) for v in z["meta/bxy"]), steps=int(z["meta/steps"]),
-                mask=mask, topography=topo, z=z)
+                tau=float(z["meta/tau"]) if "meta/tau" in z.files else 1.0, mask=mask, topography=topo, z=z)
 
 
 def e2e_blocks(z):

@@ -1,8 +1,12 @@
 """Generate the golden fixtures in tests/golden/ from the COMPILED REFERENCE.
 
-Run in the build container only (needs /root/reference and `make -f oracle/ref.mk`):
+Needs the compiled reference under oracle/_ref, which __graft_entry__.build() (or `make -f
+oracle/ref.mk`) makes where the reference's sources are present:
 
-    python tests/golden/gen_golden.py
+    python tests/golden/gen_golden.py                 everything
+    python tests/golden/gen_golden.py params          the parameter cases (cases.PARAM_CASES: param_cases()
+                                                      below, one per set of tests/shapes.py PARAMS)
+    python tests/golden/gen_golden.py kernels_b34x9   one kernel geometry
 
 Two kinds of fixtures:
 
@@ -123,7 +127,10 @@ KERNELS = {
 }
 
 # Block geometries for the kernel fixtures: (nxs, nxe, nys, nye) with arrays start-2..end+2
-GEOMS = {"b66x50": (3, 68, 3, 52), "b1x1": (3, 3, 3, 3), "b130x7": (3, 132, 3, 9)}
+GEOMS = {"b66x50": (3, 68, 3, 52), "b1x1": (3, 3, 3, 3), "b130x7": (3, 132, 3, 9), "b34x9": (3, 36, 3, 11)}
+# (tau, time_smooth) of a geometry's fixture; 1.0, 0.5 where not listed.  b34x9: neither a power of two, so
+# a / tau is a division and the filter's products round
+GEOM_SCALARS = {"b34x9": (0.3, 0.3)}
 
 
 def random_state(rng: np.random.Generator, shape, ref) -> dict[str, np.ndarray]:
@@ -175,12 +182,13 @@ def gen_kernels(ref, tag, geom, seed):
     shape = (bx2 - bx1 + 1, by2 - by1 + 1)
     rng = np.random.default_rng(seed)
     state = random_state(rng, shape, ref)
+    tau, ts = GEOM_SCALARS.get(tag, (1.0, 0.5))
     out = {"geom": np.array([nxs, nxe, nys, nye, bx1, bx2, by1, by2], np.int32),
-           "tau": np.float64(1.0), "time_smooth": np.float64(0.5), "full_free_surface": np.int32(1),
+           "tau": np.float64(tau), "time_smooth": np.float64(ts), "full_free_surface": np.int32(1),
            "factor_mu": np.float64(0.7)}
     for nm, a in state.items():
         out["in/" + nm] = a
-    C.c_double.in_dll(ref, "_QMconfig_sw_moduleEtime_smooth").value = 0.5
+    C.c_double.in_dll(ref, "_QMconfig_sw_moduleEtime_smooth").value = ts
     C.c_int.in_dll(ref, "_QMconfig_sw_moduleEfull_free_surface").value = 1
     for kname, (sym, scalars, args) in KERNELS.items():
         work = {nm: a.copy(order="F") for nm, a in state.items()}
@@ -216,8 +224,8 @@ BASIN_TMPL = """{nx} : nx
 0 : xgr_type
 0 : ygr_type
 {curve} : curve_grid
-0.0d0 : rotation_on_lon
-0.0d0 : rotation_on_lat
+{rot_lon} : rotation_on_lon
+{rot_lat} : rotation_on_lat
 90.0d0 : x_pole
 60.0d0 : y_pole
 90.0d0 : p_pole
@@ -309,6 +317,35 @@ CASES = {
     "coast40x32_trans0_s5": (dict(BOX, nx=40, ny=32, mask="rough"), dict(SW_DEFAULT, trans=0), (1, 1), 5, True),
     "coast40x32_ksw0_s5": (dict(BOX, nx=40, ny=32, mask="rough"), dict(SW_DEFAULT, ksw=0), (1, 1), 5, True),
 }
+
+
+def param_cases():
+    """The parameter sets of tests/shapes.py PARAMS on the rough-coast 40 x 32 basin, 5 steps at the set's
+    own tau, every array kept: name -> (basin, sw, (bppnx, bppny), steps, keep, tau).  One block, but coarse
+    and equator on 2 x 2 blocks (rows that differ, and a sign change of rlh_s, across a block boundary);
+    tau075_ts03 carries a tracer.  The names are tests/golden/cases.py PARAM_CASES."""
+    from tests import shapes as S
+    out = {}
+    for pname, (_, swk, tau) in S.PARAMS.items():
+        bk = S.basin_kwargs(S.Shape(36, 28, mask="rough"), pname)
+        basin = dict(BOX, nx=40, ny=32, mask="rough")
+        for key, par in (("dxst", "dxst"), ("dyst", "dyst"), ("rlon", "rlon"), ("rlat", "rlat"),
+                         ("rot_lon", "rotation_on_lon"), ("rot_lat", "rotation_on_lat")):
+            if par in bk:
+                basin[key] = repr(float(bk[par]))   # repr: the same double again when read back
+        if "curve_grid" in bk:
+            basin["curve"] = bk["curve_grid"]
+        sw = dict(SW_DEFAULT)
+        if "time_smooth" in swk:
+            sw["ts"] = repr(float(swk["time_smooth"]))
+        grid = (2, 2) if pname in ("coarse", "equator") else (1, 1)
+        if pname == "tau075_ts03":
+            sw.update(tr=1, trn=1)
+        name = "coast40x32_" + ("b2x2_" if grid != (1, 1) else "") + pname + "_s5"
+        out[name] = (basin, sw, grid, 5, "r8" if grid != (1, 1) else True, tau)
+    return out
+
+
 PROGNOSTIC = ["ssh", "sshp", "ubrtr", "ubrtrp", "vbrtr", "vbrtrp", "ff1_1", "ff1p_1"]
 
 
@@ -361,7 +398,10 @@ def write_mask_file(path, m, note):
             f.write("".join(str(int(v)) for v in m[:, n]) + "\n")
 
 
-def gen_e2e(name, basin, sw, bxy, steps, full):
+def gen_e2e(name, basin, sw, bxy, steps, full, tau=None):
+    """tau None: the driver's default of 1 s and no meta/tau in the fixture (the fixtures made before the
+    parameter cases stay byte for byte what they were)."""
+    basin = dict(dict(rot_lon="0.0d0", rot_lat="0.0d0"), **basin)
     d = tempfile.mkdtemp()
     topo = None
     mask_name = "none" if basin["mask"] == "none" else "BS"
@@ -379,7 +419,8 @@ def gen_e2e(name, basin, sw, bxy, steps, full):
         open(os.path.join(d, "sw.par"), "w").write(SW_TMPL.format(**dict(dict(tr=0, trn=1), **sw)))
         open(os.path.join(d, "parallel.par"), "w").write(PAR_TMPL.format(bx=bxy[0], by=bxy[1]))
         env = dict(os.environ, OMP_NUM_THREADS="1")
-        subprocess.check_call([REFDRV, str(steps), "dump.bin"], cwd=d, env=env,
+        subprocess.check_call([REFDRV, str(steps), "dump.bin"] + ([repr(float(tau))] if tau is not None else []),
+                              cwd=d, env=env,
                               stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         if full == "sha":
             blocks = digest_dump(os.path.join(d, "dump.bin"))
@@ -391,9 +432,11 @@ def gen_e2e(name, basin, sw, bxy, steps, full):
             m = read_mask_file(basin["mask"], basin["nx"], basin["ny"])
     finally:
         shutil.rmtree(d)
-    out = {"meta/basin": np.array(repr({k: v for k, v in basin.items() if k not in ("mask", "topo")} |
-                                         {"mask": mask_name})),
+    skip = ("mask", "topo") + (("rot_lon", "rot_lat") if tau is None else ())
+    out = {"meta/basin": np.array(repr({k: v for k, v in basin.items() if k not in skip} | {"mask": mask_name})),
            "meta/sw": np.array(repr(sw)), "meta/bxy": np.array(bxy, np.int32), "meta/steps": np.int32(steps)}
+    if tau is not None:
+        out["meta/tau"] = np.float64(tau)
     if topo is not None:
         out["in/topo"] = topo
     if m is not None:
@@ -412,15 +455,19 @@ def gen_e2e(name, basin, sw, bxy, steps, full):
 
 
 def main(which):
-    """which: nothing = everything; otherwise "kernels" and/or e2e case names."""
+    """which: nothing = everything; otherwise "kernels" (every geometry) or "kernels_<tag>", e2e case
+    names, and "params" (every parameter case)."""
     subprocess.check_call(["make", "-s", "-f", os.path.join(REPO, "oracle", "ref.mk")], cwd=REPO)
     ref = C.CDLL(REFLIB)
-    if not which or "kernels" in which:
-        for i, (tag, geom) in enumerate(GEOMS.items()):
+    for i, (tag, geom) in enumerate(GEOMS.items()):
+        if not which or "kernels" in which or "kernels_" + tag in which:
             gen_kernels(ref, tag, geom, 1234 + i)
     for name, (basin, sw, bxy, steps, full) in CASES.items():
         if not which or name in which:
             gen_e2e(name, basin, sw, bxy, steps, full)
+    for name, (basin, sw, bxy, steps, full, tau) in param_cases().items():
+        if not which or "params" in which or name in which:
+            gen_e2e(name, basin, sw, bxy, steps, full, tau)
 
 
 if __name__ == "__main__":

@@ -6,6 +6,10 @@ mask kind (None: the closed box; "drop": the centre and the (1, 1) corner block 
 which the decomposition drops; the coast kinds of MASK_KINDS below).  The CPU oracle (oracle/oracle.py,
 pinned bit for bit to the compiled reference by tests/test_oracle_pinned.py) is the reference.
 
+A parameter set (PARAMS below: a name -> basin keywords, SW keywords, tau) moves a run off tau = 1,
+time_smooth = 0.5 and the default grid; oracle_model, sw_kwargs, basin_kwargs, uploads_for and reference take
+its name, and None (the default) is the run every sweep before tests/test_gpu_params.py makes.
+
 Inputs are cut from GLOBAL (nx, ny) arrays of numpy.random.default_rng(seed).uniform(-1, 1), one
 seed per field: block (bm, bn) gets [bnd_x1-1:bnd_x2, bnd_y1-1:bnd_y2], so the halos of neighbouring
 blocks agree (the library's own checks keep the x2 / x4 steps off for uploads whose halos do not).
@@ -116,6 +120,48 @@ STILL_SHAPES = [(61, 33), (121, 65), (17, 19), (36, 36)]   # W x H of the shapes
 COAST_ENSEMBLE_DEEP = ["abyss", "noise", "abyss"]   # a second ensemble: one known-constant group
 
 
+# ---------------------------------------------------------------- the parameter sweep
+# (tests/test_gpu_params.py; tests/test_params_cpu.py asserts what each set promises)
+# name -> (BasinConfig keywords, SWConfig keywords, tau).  What each reaches in sw_kernels.hip:
+#   tau03, tau075_ts03  tau is no power of two: MarchStep<P2 = false>, qtau = a / tau, an IEEE division;
+#                       time_smooth 0.3: filter weights whose products round
+#   tau2, tau025_ts0    a power of two other than 1: P2 = true with inv_tau != 1 (at tau = 1, a * inv_tau,
+#                       a * tau and a are the same bits); the filter off
+#   tau3_ts1            the filter at full weight
+#   cart                curve_grid 0: no cos(lat) scaling, one Coriolis value
+#   south, equator      rlh_s negative / of both signs in one block and across a block boundary
+#   coarse              half-degree steps from 30 N: adjacent rows' dx, dxh, dxt, dxb differ by percents,
+#                       so a lane that takes row n +- 1's metric or reciprocal changes high bits -- on the
+#                       ext rows x2 / x4 steps form for their halo as well; tau 30 keeps the Courant number
+#   polar               80 N: dx about 43 m, large reciprocals
+#   rot                 a rotated sphere: rlh_s varies along a row, the compact tables must be refused
+EQUATOR = object()   # basin_kwargs: the rlat that puts the interior's middle row at latitude 0
+PARAMS = {
+    "tau03": ({}, {}, 0.3),
+    "tau075_ts03": ({}, dict(time_smooth=0.3), 0.75),
+    "tau2": ({}, {}, 2.0),
+    "tau025_ts0": ({}, dict(time_smooth=0.0), 0.25),
+    "tau3_ts1": ({}, dict(time_smooth=1.0), 3.0),
+    "cart": (dict(curve_grid=0), {}, 0.75),
+    "south": (dict(rlat=-44.8), {}, 0.75),
+    "equator": (dict(rlat=EQUATOR), {}, 0.75),
+    "coarse": (dict(dxst=0.5, dyst=0.4, rlat=30.0), {}, 30.0),
+    "polar": (dict(rlat=80.0), {}, 0.3),
+    "rot": (dict(rotation_on_lon=10.0, rotation_on_lat=20.0), {}, 0.75),
+}
+CORE_PARAMS = ["tau03", "tau075_ts03", "tau2", "coarse", "equator"]
+OTHER_PARAMS = ["tau025_ts0", "tau3_ts1", "cart", "south", "polar"]
+PARAM_SINGLE = [Shape(121, 65, mask="rough"), Shape(61, 9, mask="comb")]
+PARAM_GRIDS = [Shape(17, 19, (2, 2), 0, "rough"), Shape(27, 27, (3, 3), 0, "rough"), Shape(361, 12, (2, 1), 0, "diag")]
+PARAM_TRACER_GRIDS = [Shape(17, 19, (2, 2), 1, "rough"), Shape(36, 36, (3, 3), 2, "rough_drop")]
+PARAM_RANK_GRIDS = [Shape(9, 8, (2, 2), 0, "rough"), Shape(17, 19, (2, 2), 0, "rough")]
+PARAM_ENSEMBLE = Shape(61, 9, mask="rough")
+PARAM_ROT = [Shape(61, 33, mask="rough"), Shape(17, 19, (2, 2), 1, "rough")]
+PARAM_DEEP = ["tau03", "tau075_ts03"]   # abyss: the IEEE re-runs and a / tau in one row
+# tau changes across the P2 / non-P2 variant boundary: (steps, tau) per call
+TAU_CALLS = ((3, 1.0), (2, 0.3), (1, 0.3), (3, 2.0), (2, 0.75))
+
+
 def coast_classes(shape):
     """The input classes the coastline sweep runs on a shape: noise and general on one block, noise, hr
     and general on a grid, and still and abyss on STILL_SHAPES."""
@@ -207,20 +253,40 @@ def expect_x4(shape, cls, x4, peers=False):
 
 
 # ---------------------------------------------------------------- oracle twin, inputs, reference
-def sw_kwargs(shape, flags=(1, 1, 1)):
-    """SWConfig's keywords (the oracle's and the library's alike) for the shape's tracers and the
-    (full_free_surface, trans_terms, ksw_lat) setting."""
+def sw_kwargs(shape, flags=(1, 1, 1), params=None):
+    """SWConfig's keywords (the oracle's and the library's alike) for the shape's tracers, the
+    (full_free_surface, trans_terms, ksw_lat) setting and the parameter set (a name of PARAMS)."""
     kw = dict(use_tracers=1, tracer_num=shape.tracers) if shape.tracers else {}
     if tuple(flags) != (1, 1, 1):
         kw.update(full_free_surface=flags[0], trans_terms=flags[1], ksw_lat=flags[2])
+    if params is not None:
+        kw.update(PARAMS[params][1])
     return kw
 
 
-def oracle_model(shape, flags=(1, 1, 1)):
-    """An initialised oracle.OracleModel on the shape's box, block grid and tracer count."""
+def basin_kwargs(shape, params=None):
+    """BasinConfig's keywords (the oracle's and the library's alike) but the mask: the shape's nx, ny and
+    the parameter set's grid.  EQUATOR stands for the rlat at which the interior's middle row (0-based
+    interior row (H - 1) // 2) lies at latitude 0: yt = rlat + j dyst is then -(j dyst) + j dyst = 0."""
+    kw = dict(nx=shape.W + 4, ny=shape.H + 4)
+    if params is not None:
+        kw.update(PARAMS[params][0])
+        if kw.get("rlat") is EQUATOR:
+            from oracle import oracle as O
+            kw["rlat"] = -(((shape.H - 1) // 2) * kw.get("dyst", O.BasinConfig(nx=5, ny=5).dyst))
+    return kw
+
+
+def tau_of(params=None):
+    return 1.0 if params is None else PARAMS[params][2]
+
+
+def oracle_model(shape, flags=(1, 1, 1), params=None):
+    """An initialised oracle.OracleModel on the shape's box, block grid and tracer count, with the
+    parameter set's grid and SW keywords."""
     from oracle import oracle as O
-    sw = O.SWConfig(**sw_kwargs(shape, flags))
-    return O.OracleModel(O.BasinConfig(nx=shape.W + 4, ny=shape.H + 4, mask=mask_of(shape)), sw, *shape.grid).init()
+    sw = O.SWConfig(**sw_kwargs(shape, flags, params))
+    return O.OracleModel(O.BasinConfig(mask=mask_of(shape), **basin_kwargs(shape, params)), sw, *shape.grid).init()
 
 
 def uploads(cls, om):
@@ -274,20 +340,42 @@ def uploads(cls, om):
 
 
 @functools.lru_cache(maxsize=16)
-def uploads_for(shape, cls):
-    return uploads(cls, oracle_model(shape))
+def uploads_for(shape, cls, params=None):
+    return uploads(cls, oracle_model(shape, params=params))
+
+
+def loaded_oracle(shape, cls, flags=(1, 1, 1), params=None):
+    """oracle_model with the class's uploads written into its fields."""
+    om = oracle_model(shape, flags, params)
+    for k, b in enumerate(om.blocks):
+        for nm, a in uploads_for(shape, cls, params).get((b.bm, b.bn), {}).items():
+            om.f[k][nm][...] = a
+    return om
 
 
 @functools.lru_cache(maxsize=16)
-def reference(shape, cls, steps, flags=(1, 1, 1)):
-    """{(bm, bn): {field: array}} of the oracle after `steps` steps (tau = 1) from the class's inputs.
-    Computed once per (shape, class, steps, flags) and shared; callers must not write into it."""
-    om = oracle_model(shape, flags)
-    for k, b in enumerate(om.blocks):
-        for nm, a in uploads_for(shape, cls).get((b.bm, b.bn), {}).items():
-            om.f[k][nm][...] = a
-    om.run(steps)
+def reference(shape, cls, steps, flags=(1, 1, 1), params=None):
+    """{(bm, bn): {field: array}} of the oracle after `steps` steps from the class's inputs, at tau = 1
+    or, with a parameter set, at its tau, grid and SW keywords.  Computed once per (shape, class, steps,
+    flags, params) and shared; callers must not write into it."""
+    om = loaded_oracle(shape, cls, flags, params)
+    om.run(steps, tau_of(params))
     return {(b.bm, b.bn): om.f[k] for k, b in enumerate(om.blocks)}
+
+
+@functools.lru_cache(maxsize=8)
+def reference_calls(shape, cls, calls):
+    """The oracle driven through calls = ((steps, tau), ...) from the class's inputs: a list, per call, of
+    {(bm, bn): {field: array}} -- ssh alone after every call but the last, every field after the last.
+    Shared; callers must not write into it."""
+    om = loaded_oracle(shape, cls)
+    out = []
+    for i, (n, tau) in enumerate(calls):
+        om.run(n, tau)
+        last = i == len(calls) - 1
+        out.append({(b.bm, b.bn): (om.f[k] if last else {"ssh": om.f[k]["ssh"].copy(order="F")})
+                    for k, b in enumerate(om.blocks)})
+    return out
 
 
 # ---------------------------------------------------------------- comparison

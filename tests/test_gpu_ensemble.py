@@ -31,31 +31,32 @@ def amd():
 
 # ---------------------------------------------------------------- inputs and references per member
 @functools.lru_cache(maxsize=64)
-def member_uploads(shape, cls, off):
+def member_uploads(shape, cls, off, params=None):
     """The class's uploads (tests/shapes.py uploads) with every field's seed moved by `off`."""
     seeds = S.SEEDS
     S.SEEDS = {nm: s + off for nm, s in seeds.items()}
     try:
-        return S.uploads(cls, S.oracle_model(shape))
+        return S.uploads(cls, S.oracle_model(shape, params=params))
     finally:
         S.SEEDS = seeds
 
 
 @functools.lru_cache(maxsize=64)
-def member_reference(shape, cls, off, steps):
-    """{(bm, bn): {field: array}} of the oracle after `steps` steps from the member's inputs; computed
-    once per key, never written by the callers."""
-    om = S.oracle_model(shape)
+def member_reference(shape, cls, off, steps, params=None):
+    """{(bm, bn): {field: array}} of the oracle after `steps` steps from the member's inputs (at the
+    parameter set's tau, grid and SW keywords; None: the defaults, tau = 1); computed once per key, never
+    written by the callers."""
+    om = S.oracle_model(shape, params=params)
     for k, b in enumerate(om.blocks):
-        for nm, a in member_uploads(shape, cls, off).get((b.bm, b.bn), {}).items():
+        for nm, a in member_uploads(shape, cls, off, params).get((b.bm, b.bn), {}).items():
             om.f[k][nm][...] = a
-    om.run(steps)
+    om.run(steps, S.tau_of(params))
     return {(b.bm, b.bn): om.f[k] for k, b in enumerate(om.blocks)}
 
 
-def _ensemble(amd, shape, members):
-    sw = amd.SWConfig(use_tracers=1, tracer_num=shape.tracers) if shape.tracers else amd.SWConfig()
-    return amd.OceanEnsemble(amd.BasinConfig(nx=shape.W + 4, ny=shape.H + 4, mask=S.mask_of(shape)), sw,
+def _ensemble(amd, shape, members, params=None):
+    sw = amd.SWConfig(**S.sw_kwargs(shape, params=params))
+    return amd.OceanEnsemble(amd.BasinConfig(mask=S.mask_of(shape), **S.basin_kwargs(shape, params)), sw,
                              amd.ParallelConfig(*shape.grid), members=members)
 
 
@@ -65,23 +66,25 @@ def _upload(m, ups):
             m.upload(b.k, nm, a)
 
 
-def _start(amd, shape, classes):
-    """An initialised ensemble with member i's inputs of class classes[i] (seed offset 1000 i)."""
-    e = _ensemble(amd, shape, len(classes))
+def _start(amd, shape, classes, params=None):
+    """An initialised ensemble with member i's inputs of class classes[i] (seed offset 1000 i); params: a
+    parameter set of tests/shapes.py PARAMS."""
+    e = _ensemble(amd, shape, len(classes), params)
     e.init()
     for i, (m, cls) in enumerate(zip(e.members, classes)):
-        _upload(m, member_uploads(shape, cls, 1000 * i))
+        _upload(m, member_uploads(shape, cls, 1000 * i, params))
     return e
 
 
-def _calls(e, calls, check_every=1):
-    """The calls (a synchronize() after the first: the known-constant verdicts reach the host); the
-    info and the launches issued per call; then complete() and the statuses."""
+def _calls(e, calls, check_every=1, params=None):
+    """The calls at the parameter set's tau (a synchronize() after the first: the known-constant verdicts
+    reach the host); the info and the launches issued per call; then complete() and the statuses."""
+    tau = S.tau_of(params)
     import ocean_model_arch_amd as amd
     infos, launches = [], []
     for i, n in enumerate(calls):
         l0 = amd._lib.launch_count()
-        e.step(n, tau=1.0, check_every=check_every)
+        e.step(n, tau=tau, check_every=check_every)
         launches.append(amd._lib.launch_count() - l0)
         infos.append(e.info())
         if i == 0:
@@ -90,12 +93,12 @@ def _calls(e, calls, check_every=1):
     return infos, launches, e.synchronize()
 
 
-def _bad(e, shape, classes, steps):
+def _bad(e, shape, classes, steps, params=None):
     """Every field of every member against its own oracle run: ["member i (bm,bn):field", ...]."""
     steps = steps if isinstance(steps, (list, tuple)) else [steps] * len(classes)
     bad = []
     for i, (m, cls) in enumerate(zip(e.members, classes)):
-        ref = member_reference(shape, cls, 1000 * i, steps[i])
+        ref = member_reference(shape, cls, 1000 * i, steps[i], params)
         get = S.model_getter([m])
         assert get.blocks == set(ref)
         bad += [f"member {i} {x}" for x in S.mismatches(ref, get)]

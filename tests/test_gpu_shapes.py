@@ -30,9 +30,11 @@ def amd():
     return amd
 
 
-def _model(amd, shape, rank=0, nranks=1, multi=None, pair=None, x4=None, overlap=None, kc=None):
-    sw = amd.SWConfig(use_tracers=1, tracer_num=shape.tracers) if shape.tracers else amd.SWConfig()
-    m = amd.OceanModel(amd.BasinConfig(nx=shape.W + 4, ny=shape.H + 4, mask=S.mask_of(shape)), sw,
+def _model(amd, shape, rank=0, nranks=1, multi=None, pair=None, x4=None, overlap=None, kc=None, params=None,
+           flags=(1, 1, 1)):
+    """params: a parameter set of tests/shapes.py PARAMS (its grid and SW keywords; None: the defaults)."""
+    sw = amd.SWConfig(**S.sw_kwargs(shape, flags, params))
+    m = amd.OceanModel(amd.BasinConfig(mask=S.mask_of(shape), **S.basin_kwargs(shape, params)), sw,
                        amd.ParallelConfig(*shape.grid), rank=rank, nranks=nranks)
     if multi is not None:
         m.set_multi(multi)
@@ -47,17 +49,18 @@ def _model(amd, shape, rank=0, nranks=1, multi=None, pair=None, x4=None, overlap
     return m
 
 
-def _drive(m, shape, cls, calls, nsync=1):
-    """init, the class's uploads to m's blocks, the calls (synchronize() after each of the first nsync);
-    returns the path flags after each call."""
+def _drive(m, shape, cls, calls, nsync=1, params=None):
+    """init, the class's uploads to m's blocks, the calls at the parameter set's tau (1.0 without one;
+    synchronize() after each of the first nsync); returns the path flags after each call."""
     m.init()
-    ups = S.uploads_for(shape, cls)
+    ups = S.uploads_for(shape, cls, params)
+    tau = S.tau_of(params)
     for b in m.blocks:
         for nm, a in ups.get((b.bm, b.bn), {}).items():
             m.upload(b.k, nm, a)
     flags = []
     for i, n in enumerate(calls):
-        m.step(n, tau=1.0, check_every=1)
+        m.step(n, tau=tau, check_every=1)
         if i < nsync:
             m.synchronize()   # the known-constant verdict reaches the host
         flags.append({"one": m.onepass_active, "multi": m.multi_active, "pair": m.pair_active,
@@ -66,12 +69,12 @@ def _drive(m, shape, cls, calls, nsync=1):
     return flags
 
 
-def _run(amd, shape, cls, calls, **opts):
-    m = _model(amd, shape, **opts)
+def _run(amd, shape, cls, calls, params=None, **opts):
+    m = _model(amd, shape, params=params, **opts)
     try:
-        flags = _drive(m, shape, cls, calls)
+        flags = _drive(m, shape, cls, calls, params=params)
         get = S.model_getter([m])
-        ref = S.reference(shape, cls, sum(calls))
+        ref = S.reference(shape, cls, sum(calls), params=params)
         assert get.blocks == set(ref), (get.blocks, set(ref))
         bad = S.mismatches(ref, get)
     finally:
@@ -118,10 +121,10 @@ OVERLAP2 = ["7x9_b3x2", "10x6_b5x3", "13x11_b3x3", "9x8_b2x2", "16x16_b2x2", "17
 GRID_CASES = [(s, x4, ov) for s in S.GRIDS for ov in (1, 2) if ov == 1 or s.id in OVERLAP2 for x4 in (0, 1)]
 
 
-def _grid_failures(amd, shape, x4, overlap, classes=S.CLASSES):
+def _grid_failures(amd, shape, x4, overlap, classes=S.CLASSES, params=None):
     failures = []
     for cls in classes:
-        bad, flags = _run(amd, shape, cls, [2, 5], x4=x4, overlap=overlap)
+        bad, flags = _run(amd, shape, cls, [2, 5], x4=x4, overlap=overlap, params=params)
         if bad:
             failures.append(f"{cls}: fields differ from the oracle: {bad}")
         want = {"x2": S.expect_x2(shape), "x4": S.expect_x4(shape, cls, x4)}

@@ -87,18 +87,21 @@ def _sha(a):
 def build_oracle_model(case):
     b = case["basin"]
     basin = O.BasinConfig(nx=b["nx"], ny=b["ny"], dxst=b["dxst"], dyst=b["dyst"], rlon=b["rlon"],
-                          rlat=b["rlat"], curve_grid=b["curve_grid"], mask=case["mask"],
-                            topography=case.get("topography"))
+                          rlat=b["rlat"], curve_grid=b["curve_grid"], rotation_on_lon=b["rotation_on_lon"],
+                          rotation_on_lat=b["rotation_on_lat"], mask=case["mask"], topography=case.get("topography"))
     sw = O.SWConfig(**case["sw"])
     return O.OracleModel(basin, sw, *case["bxy"])
 
 
 @pytest.mark.parametrize("name", cases.E2E_CASES + cases.TRACER_E2E_CASES + cases.LONG_CASES + cases.INIT_CASES
-                         + cases.FULLSIZE_CASES + cases.TOPO_CASES + ["box2048_b2x2_s10"])
+                         + cases.FULLSIZE_CASES + cases.TOPO_CASES + ["box2048_b2x2_s10"] + cases.PARAM_CASES)
 def test_oracle_end_to_end_matches_reference(name):
+    """PARAM_CASES: the parameter sets of tests/shapes.py PARAMS (a tau that is no power of two, filter
+    weights 0, 0.3 and 1, the cartesian, southern, equatorial, coarse, polar and rotated grids), each run at
+    the tau its fixture records -- the oracle is the judge of tests/test_gpu_params.py there."""
     case = cases.load_e2e(name)
     z = case["z"]
-    m = build_oracle_model(case).init().run(case["steps"])
+    m = build_oracle_model(case).init().run(case["steps"], case["tau"])
     blocks = cases.e2e_blocks(z)
     assert len(blocks) == len(m.blocks)
     checked = set()

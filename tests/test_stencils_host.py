@@ -140,7 +140,7 @@ def compact_tables(hst, om):
     return out
 
 
-def host_step(hst, om, mode, nbad, last=True, tabs=None, first=True):
+def host_step(hst, om, mode, nbad, last=True, tabs=None, first=True, tau=1.0):
     sw_o = om.sw
     sw = SwParams(sw_o.full_free_surface, sw_o.trans_terms, sw_o.ksw_lat, sw_o.time_smooth, sw_o.lvisc_2)
     ntr = sw_o.tracer_num if sw_o.use_tracers > 0 else 0
@@ -153,12 +153,12 @@ def host_step(hst, om, mode, nbad, last=True, tabs=None, first=True):
             for st, sync in ((0, ["flux_x", "flux_y"]), (1, [f"ff1n_{t}"]), (2, [])):
                 for k, (b, tb) in enumerate(blocks):
                     bits, rows = (tabs[k][0].ctypes.data, tabs[k][1].ctypes.data) if compact else (None, None)
-                    oob = hst.hst_tracer(st, C.byref(b), tb, len(tb), bits, rows, t, 1.0, sw_o.time_smooth, 1.0)
+                    oob = hst.hst_tracer(st, C.byref(b), tb, len(tb), bits, rows, t, tau, sw_o.time_smooth, 1.0)
                     assert oob == 0, f"tracer stage {st}: {oob} out-of-bounds accesses"
                 for f in sync:
                     om.sync(f)
 
-    def each(stage, tau=1.0, full=1, part=0):
+    def each(stage, full=1, part=0):
         for k, (b, t) in enumerate(blocks):
             bits, rows = (tabs[k][0].ctypes.data, tabs[k][1].ctypes.data) if compact else (None, None)
             oob = hst.hst_stage(stage, C.byref(b), t, len(t), bits, rows, C.byref(sw), tau, C.byref(nbad), full, part)
@@ -225,24 +225,38 @@ def host_step(hst, om, mode, nbad, last=True, tabs=None, first=True):
     tracers()
 
 
-@pytest.mark.parametrize("mode", ["compact", "fused", "stages", "overlap_early", "overlap_late"])
-@pytest.mark.parametrize("name", cases.E2E_CASES + cases.TRACER_E2E_CASES)
+def _case_model(case):
+    b = case["basin"]
+    return O.OracleModel(O.BasinConfig(nx=b["nx"], ny=b["ny"], dxst=b["dxst"], dyst=b["dyst"], rlon=b["rlon"],
+                                       rlat=b["rlat"], curve_grid=b["curve_grid"],
+                                       rotation_on_lon=b["rotation_on_lon"], rotation_on_lat=b["rotation_on_lat"],
+                                       mask=case["mask"]),
+                         O.SWConfig(**case["sw"]), *case["bxy"]).init()
+
+
+ROT_CASE = "coast40x32_rot_s5"   # rlh_s varies along its rows: no compact tables (test_compact_tables_refuse_...)
+COMPACT_MODES = ("compact", "overlap_early", "overlap_late")
+HOST_STEP_CASES = [(n, md) for n in cases.E2E_CASES + cases.TRACER_E2E_CASES + cases.PARAM_CASES
+                   for md in ("compact", "fused", "stages", "overlap_early", "overlap_late")
+                   if not (n == ROT_CASE and md in COMPACT_MODES)]
+
+
+@pytest.mark.parametrize("name,mode", HOST_STEP_CASES, ids=[f"{n}-{md}" for n, md in HOST_STEP_CASES])
 def test_host_step_matches_reference(hst, name, mode):
     """The whole run as one ocn_ctx_step call: hh_init's time-invariant stores are skipped on
     every step but the last (fused modes); "compact" reads masks / metrics from the compact
-    tables, which must be exact for these grids (no curvilinear metrics)."""
+    tables, which must be exact for these grids (no curvilinear metrics).  Every case runs at the
+    tau and time_smooth its fixture records (cases.PARAM_CASES: a / tau as a division, filter weights
+    0, 0.3 and 1, rows whose metrics differ, both signs of rlh_s)."""
     case = cases.load_e2e(name)
-    b = case["basin"]
-    om = O.OracleModel(O.BasinConfig(nx=b["nx"], ny=b["ny"], dxst=b["dxst"], dyst=b["dyst"], rlon=b["rlon"],
-                                     rlat=b["rlat"], curve_grid=b["curve_grid"], mask=case["mask"]),
-                       O.SWConfig(**case["sw"]), *case["bxy"]).init()
+    om = _case_model(case)
     nbad = C.c_int32(0)
     tabs = None
-    if mode in ("compact", "overlap_early", "overlap_late"):
+    if mode in COMPACT_MODES:
         tabs = compact_tables(hst, om)
         assert all(t[2] & 3 == 0 for t in tabs), [t[2] for t in tabs]   # 4 = sea on the halo ring: fine
     for s in range(case["steps"]):
-        host_step(hst, om, mode, nbad, last=s == case["steps"] - 1, tabs=tabs, first=s == 0)
+        host_step(hst, om, mode, nbad, last=s == case["steps"] - 1, tabs=tabs, first=s == 0, tau=case["tau"])
     assert nbad.value == 0
     z = case["z"]
     bad = []
@@ -252,6 +266,15 @@ def test_host_step_matches_reference(hst, name, mode):
             if key in z.files and _sha(a) != str(z[key]):
                 bad.append(f"({blkk.bm},{blkk.bn}):{nm}")
     assert not bad, f"{name}: {bad}"
+
+
+def test_compact_tables_refuse_the_rotated_grid(hst):
+    """rotation_on_lat != 0: rlh_s depends on the longitude, so a row of it is no single value and
+    Prepare must flag the metrics (2) on every parameter-sweep shape of the set."""
+    om = _case_model(cases.load_e2e(ROT_CASE))
+    rl = om.f[0]["rlh_s"]
+    assert (rl[2:-2, 2:-2] != rl[2:3, 2:-2]).any()
+    assert all(t[2] & 2 for t in compact_tables(hst, om))
 
 
 @pytest.mark.parametrize("what,flag", [("none", 0), ("metric", 2), ("mask", 1)])
@@ -313,19 +336,16 @@ def _own_bits(om, b):
 
 
 @pytest.mark.parametrize("compact", [False, True])
-@pytest.mark.parametrize("name", cases.TRACER_E2E_CASES)
+@pytest.mark.parametrize("name", cases.TRACER_E2E_CASES + ["coast40x32_tau075_ts03_s5"])
 def test_tracer_step_matches_expl_tracer(hst, name, compact):
     """The tracer step (sw_stencils.h TracerStep, one launch per tracer in one-pass sequences) on the
     state a step leaves, against the oracle's expl_tracer (control/tracer.f90:33-62: the three stages
     with hh_init's stored depths and their exchanges) on the same state: its ffn and filtered ffp at
     every interior sea point bit for bit, after a few steps (a moving state, nonzero fluxes)."""
     case = cases.load_e2e(name)
-    b = case["basin"]
-    om = O.OracleModel(O.BasinConfig(nx=b["nx"], ny=b["ny"], dxst=b["dxst"], dyst=b["dyst"], rlon=b["rlon"],
-                                     rlat=b["rlat"], curve_grid=b["curve_grid"], mask=case["mask"]),
-                       O.SWConfig(**case["sw"]), *case["bxy"]).init()
-    om.run(3)
-    tau, ts = 1.0, om.sw.time_smooth
+    om = _case_model(case)
+    tau, ts = case["tau"], om.sw.time_smooth
+    om.run(3, tau)
     # step 4's shallow-water part (model.f90:146), then expl_tracer on copies
     ntr = om.sw.tracer_num
     expl = om.expl_tracer
