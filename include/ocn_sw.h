@@ -563,6 +563,48 @@ int ocn_ens_info(ocn_ens *ens, ocn_ens_info_t *out);
 enum { OCN_ENS_OPT_CAPACITY = 1, OCN_ENS_OPT_MAX_GROUP = 2 };
 int ocn_ens_set_option(ocn_ens *ens, int32_t key, int64_t value);
 
+/* Statistics over the members, formed on the device (the members' fields lie side by side in device
+ * memory with one geometry and one pitch: N reads and one write per point instead of N downloads).
+ * No counterpart in the reference.
+ *
+ * ocn_ens_stats: the per-point statistics `what` (OCN_ENS_STAT_* bits) of real(8) field `field_id` of
+ * local block k over the members in use (use[i] != 0, i < ocn_ens_size; NULL = all), at every point of
+ * A(bnd_x1:bnd_x2, bnd_y1:bnd_y2) -- interior and halo, land and sea, whatever they hold -- all from ONE
+ * launch.  With the members in use in member order u0 < u1 < ... < u(n-1) and x_i member u_i's value:
+ *   MEAN    s = x0; s = s + x_i for i = 1 .. n-1 in that order; mean = s / (double)n
+ *   VAR     d_i = x_i - mean; q = d0 d0; q = q + d_i d_i for i = 1 .. n-1 (the product rounded, then the
+ *           sum); var = q / (double)(n-1)
+ *   SPREAD  sqrt(var) (formed from the variance whether or not VAR is asked for)
+ *   MIN     c = x0; for i = 1 .. n-1: if (x_i < c || c != c) c = x_i        MAX: the same with >
+ *           (a tie, +-0 included, keeps the earlier member's bits; a NaN is dropped as soon as a later
+ *           member has a number; all NaN gives NaN)
+ * in IEEE double arithmetic without contraction: bitwise reproducible.  It first forms the pending call
+ * tail of every member in use (as every entry that looks at fields does; a member not in use is not
+ * touched), then launches on the ensemble's stream into buffers the ensemble owns (one per statistic and
+ * block, in the members' layout, allocated at first use, freed by ocn_ens_destroy).  Each member's array
+ * is the one its field table names at the time of the call.  No pointer is handed out: the members'
+ * options, known-constant verdicts and raw-pointer state stay as they were, and the next ocn_ens_step
+ * opens its sequences again as after ocn_ens_complete.  Asynchronous.  OCN_ERR_ARG -- nothing launched,
+ * earlier results kept -- for a null ensemble, a bad k, a real(4) field or one the members do not have,
+ * `what` 0 or with unknown bits, no member in use, VAR / SPREAD with fewer than two members in use.
+ *
+ * ocn_ens_stats_download: the whole array of one statistic (one OCN_ENS_STAT_* bit) of block k, in
+ * ocn_ctx_download's layout.  ocn_ens_stats_output_r4: its packed interior as real(4) with `undef` where
+ * member 0's lu says land, in ocn_ctx_output_r4's layout.  Both synchronous; OCN_ERR_STATE for a
+ * statistic the last ocn_ens_stats on that block did not form.
+ *
+ * ocn_ens_extrema: per member (out: ocn_ens_size entries), over the interior sea points
+ * (nx_start..nx_end x ny_start..ny_end with |lu| >= 0.5, the member's own lu) of real(8) field `field_id`
+ * on all local blocks: min / max over the finite values (+Inf / -Inf with none; the sign of a zero is
+ * unspecified), nonfinite = the NaN and +-Inf among them, count = the sea points.  Completes every
+ * member; two launches for the whole ensemble; synchronous. */
+enum { OCN_ENS_STAT_MEAN = 1, OCN_ENS_STAT_VAR = 2, OCN_ENS_STAT_SPREAD = 4, OCN_ENS_STAT_MIN = 8, OCN_ENS_STAT_MAX = 16 };
+int ocn_ens_stats(ocn_ens *ens, int32_t k, int32_t field_id, const uint8_t *use, int32_t what);
+int ocn_ens_stats_download(ocn_ens *ens, int32_t k, int32_t stat, double *host);
+int ocn_ens_stats_output_r4(ocn_ens *ens, int32_t k, int32_t stat, float undef, float *host);
+typedef struct ocn_ens_extrema_t { double min, max; int64_t nonfinite, count; } ocn_ens_extrema_t;
+int ocn_ens_extrema(ocn_ens *ens, int32_t field_id, ocn_ens_extrema_t *out);
+
 const char *ocn_last_error(void);
 int ocn_abi_version(void);
 /* Build id: a hash of the library's sources and compile flags (Makefile), e.g. to tie a

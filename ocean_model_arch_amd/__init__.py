@@ -8,6 +8,7 @@ from ._lib import OcnError, OcnLibraryError, build, build_id, lib  # noqa: F401
 from .config import BasinConfig, ParallelConfig, SWConfig, box_config, read_mask  # noqa: F401
 from .model import OceanModel, make_unique_id, run_ranks  # noqa: F401
 from .ensemble import OceanEnsemble  # noqa: F401
+from .output import ensemble_output  # noqa: F401
 
-__all__ = ["OceanModel", "OceanEnsemble", "BasinConfig", "SWConfig", "ParallelConfig", "box_config", "read_mask",
+__all__ = ["OceanModel", "OceanEnsemble", "ensemble_output", "BasinConfig", "SWConfig", "ParallelConfig", "box_config", "read_mask",
            "make_unique_id", "run_ranks", "build", "lib", "OcnError", "OcnLibraryError"]

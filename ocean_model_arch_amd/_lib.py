@@ -103,11 +103,14 @@ CTX_SYMBOLS = ["ocn_decompose", "ocn_halo_schedule", "ocn_ctx_create", "ocn_ctx_
                "ocn_build_id", "ocn_launch_count"]
 ENS_SYMBOLS = ["ocn_ens_plan", "ocn_ens_create", "ocn_ens_destroy", "ocn_ens_size", "ocn_ens_member",
                "ocn_ens_init_state", "ocn_ens_step", "ocn_ens_complete", "ocn_ens_synchronize", "ocn_ens_info",
-               "ocn_ens_set_option"]
+               "ocn_ens_set_option", "ocn_ens_stats", "ocn_ens_stats_download", "ocn_ens_stats_output_r4",
+               "ocn_ens_extrema"]
 ALL_SYMBOLS = KERNEL_SYMBOLS + CTX_SYMBOLS + ENS_SYMBOLS
 ENS_MAX_MEMBERS = 256          # OCN_ENS_MAX_MEMBERS
 ENS_OPT_CAPACITY = 1
 ENS_OPT_MAX_GROUP = 2
+# OCN_ENS_STAT_* (ocn_ens_stats), in the order of their bits
+ENS_STATS = {"mean": 1, "var": 2, "spread": 4, "min": 8, "max": 16}
 
 
 class OcnLibraryError(RuntimeError):
@@ -178,6 +181,10 @@ class OcnEnsGroup(C.Structure):
 class OcnEnsInfo(C.Structure):
     _fields_ = [("members", C.c_int32), ("groups", C.c_int32), ("batched", C.c_int32), ("rows", C.c_int32),
                 ("tiles", C.c_int32), ("max_group", C.c_int32), ("capacity", C.c_int64)]
+
+
+class OcnEnsExtrema(C.Structure):
+    _fields_ = [("min", C.c_double), ("max", C.c_double), ("nonfinite", C.c_int64), ("count", C.c_int64)]
 
 
 HALO_LOCAL, HALO_SEND, HALO_RECV = 0, 1, 2
@@ -260,6 +267,10 @@ def lib() -> C.CDLL:
     L.ocn_ens_synchronize.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.ocn_ens_info.argtypes = [C.c_void_p, C.POINTER(OcnEnsInfo)]
     L.ocn_ens_set_option.argtypes = [C.c_void_p, C.c_int32, C.c_int64]
+    L.ocn_ens_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+    L.ocn_ens_stats_download.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    L.ocn_ens_stats_output_r4.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
+    L.ocn_ens_extrema.argtypes = [C.c_void_p, C.c_int32, C.POINTER(OcnEnsExtrema)]
     _lib = L
     return L
 

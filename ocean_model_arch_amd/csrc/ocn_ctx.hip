@@ -4324,6 +4324,15 @@ struct ocn_ens {
     int64_t cap_opt = 0;           // OCN_ENS_OPT_CAPACITY (0: none)
     int64_t max_group = 0;         // OCN_ENS_OPT_MAX_GROUP (0: none)
     ocn_ens_info_t last{};
+    // ocn_ens_stats: per local block, one buffer per statistic (mean, variance, spread, minimum, maximum)
+    // based like the members' arrays (raw: the allocations, made at first use), and the statistics the
+    // last call on that block formed (OCN_ENS_STAT_* bits)
+    struct Stats { void *raw[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+                   double *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; int formed = 0; };
+    std::vector<Stats> stats;
+    // ocn_ens_extrema: the blocks' interiors, the members' (field, lu) table, the per-tile partials and
+    // the results, in one device allocation made at first use; h_ext: the tables and the results in pinned host memory
+    void *d_ext = nullptr, *h_ext = nullptr;
 };
 
 // ocn_ens_plan's policy: ocn_ens_plan.h (pure host code, also built stand-alone)
@@ -4357,6 +4366,11 @@ int ocn_ens_destroy(ocn_ens *e)
     }
     if (e->d_tab) (void)hipFree(e->d_tab);
     if (e->d_bar) (void)hipFree(e->d_bar);
+    for (ocn_ens::Stats &q : e->stats)
+        for (void *r : q.raw)
+            if (r) (void)hipFree(r);
+    if (e->d_ext) (void)hipFree(e->d_ext);
+    if (e->h_ext) (void)hipHostFree(e->h_ext);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
     return OCN_OK;
@@ -4573,6 +4587,157 @@ int ocn_ens_set_option(ocn_ens *e, int32_t key, int64_t value)
         return OCN_OK;
     default: return set_error(OCN_ERR_ARG, "unknown ensemble option");
     }
+}
+
+// ------------------------------------------------------------------ ensemble statistics (ens_stats.hip)
+constexpr int kEnsStatAll = OCN_ENS_STAT_MEAN | OCN_ENS_STAT_VAR | OCN_ENS_STAT_SPREAD | OCN_ENS_STAT_MIN | OCN_ENS_STAT_MAX;
+static int ens_stat_index(int32_t stat)
+{
+    for (int i = 0; i < 5; ++i)
+        if (stat == (1 << i)) return i;
+    return -1;
+}
+
+int ocn_ens_stats(ocn_ens *e, int32_t k, int32_t field_id, const uint8_t *use, int32_t what)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    const ocn_ctx *c0 = e->m[0];
+    if (k < 0 || k >= (int32_t)c0->blocks.size()) return set_error(OCN_ERR_ARG, "ens_stats: bad block index");
+    if (!has_r8(c0, field_id)) return set_error(OCN_ERR_ARG, "ens_stats: not a real(8) field of the members");
+    if (what == 0 || (what & ~kEnsStatAll)) return set_error(OCN_ERR_ARG, "ens_stats: what = OCN_ENS_STAT_* bits");
+    std::vector<ocn_ctx *> in;
+    for (size_t i = 0; i < e->m.size(); ++i)
+        if (!use || use[i]) in.push_back(e->m[i]);
+    const bool need_var = (what & (OCN_ENS_STAT_VAR | OCN_ENS_STAT_SPREAD)) != 0;
+    if (in.empty()) return set_error(OCN_ERR_ARG, "ens_stats: no member in use");
+    if (need_var && in.size() < 2) return set_error(OCN_ERR_ARG, "ens_stats: variance / spread of fewer than two members");
+    HIPCHK(hipSetDevice(e->device));
+    const LBlock &b0 = c0->blocks[(size_t)k];
+    if (e->stats.empty()) e->stats.resize(c0->blocks.size());
+    ocn_ens::Stats &st = e->stats[(size_t)k];
+    // the buffers first (a failed allocation leaves the earlier results as they were)
+    const size_t lead = (size_t)((uintptr_t)b0.ptr[field_slot(field_id)] & 255u);
+    for (int i = 0; i < 5; ++i) {
+        if (!(what & (1 << i)) || st.raw[i]) continue;
+        HIPCHK(hipMalloc(&st.raw[i], field_bytes(b0) + 512));
+        st.p[i] = (double *)((char *)st.raw[i] + 256 + lead);
+    }
+    // the members in use: their pending call tails formed, their arrays as the field tables name them now
+    std::vector<const double *> src;
+    for (ocn_ctx *c : in) {
+        RC(guarded(c, "ocn_ens_stats", [&] { return complete_open(c); }));
+        src.push_back((const double *)c->blocks[(size_t)k].ptr[field_slot(field_id)]);
+    }
+    double *out[5];
+    for (int i = 0; i < 5; ++i) out[i] = (what & (1 << i)) ? st.p[i] : nullptr;
+    st.formed = 0;
+    RC(launch_ens_stats(&b0.g, src.data(), (int)src.size(), need_var, out, e->stream));
+    st.formed = what;
+    return OCN_OK;
+}
+
+// the statistic's buffer of block k, or an error
+static int ens_stat_buffer(ocn_ens *e, int32_t k, int32_t stat, const void *host, const double **p)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    const int i = ens_stat_index(stat);
+    if (!host || i < 0 || k < 0 || k >= (int32_t)e->m[0]->blocks.size())
+        return set_error(OCN_ERR_ARG, "ens_stats: bad block index, statistic or host array");
+    if (e->stats.empty() || !(e->stats[(size_t)k].formed & stat))
+        return set_error(OCN_ERR_STATE, "ens_stats: the last ocn_ens_stats on this block did not form that statistic");
+    *p = e->stats[(size_t)k].p[i];
+    return OCN_OK;
+}
+
+int ocn_ens_stats_download(ocn_ens *e, int32_t k, int32_t stat, double *host)
+{
+    const double *p = nullptr;
+    RC(ens_stat_buffer(e, k, stat, host, &p));
+    HIPCHK(hipSetDevice(e->device));
+    const ocn_block &g = e->m[0]->blocks[(size_t)k].g;
+    const size_t w = (size_t)(g.bnd_x2 - g.bnd_x1 + 1), rows = (size_t)(g.bnd_y2 - g.bnd_y1 + 1);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy2D(host, w * 8, p, (size_t)g.pitch * 8, w * 8, rows, hipMemcpyDeviceToHost));
+    return OCN_OK;
+}
+
+int ocn_ens_stats_output_r4(ocn_ens *e, int32_t k, int32_t stat, float undef, float *host)
+{
+    const double *p = nullptr;
+    RC(ens_stat_buffer(e, k, stat, host, &p));
+    HIPCHK(hipSetDevice(e->device));
+    ocn_ctx *c0 = e->m[0];
+    RC(guarded(c0, "ocn_ens_stats_output_r4", [&] { return complete_open(c0); }));   // (as ocn_ctx_output_r4 reads lu)
+    const LBlock &b = c0->blocks[(size_t)k];
+    const int w = b.g.nx_end - b.g.nx_start + 1, h = b.g.ny_end - b.g.ny_start + 1;
+    if (w <= 0 || h <= 0) return OCN_OK;
+    const long off = (long)(b.g.ny_start - b.g.bnd_y1) * b.g.pitch + (b.g.nx_start - b.g.bnd_x1);
+    float *d = nullptr;
+    HIPCHK(hipMallocAsync((void **)&d, (size_t)w * h * sizeof(float), e->stream));
+    const dim3 grid((unsigned)((w + 255) / 256), (unsigned)h);
+    hipLaunchKernelGGL(k_output_r4<double>, grid, dim3(256), 0, e->stream, p + off, b.f<float>(OCN_LU) + off,
+                       (long)b.g.pitch, w, h, undef, d);
+    int rc = check_launch();
+    if (rc == OCN_OK && hipMemcpyAsync(host, d, (size_t)w * h * sizeof(float), hipMemcpyDeviceToHost, e->stream) != hipSuccess)
+        rc = set_error(OCN_ERR_HIP, "ens_stats_output_r4: copy");
+    (void)hipFreeAsync(d, e->stream);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return rc;
+}
+
+int ocn_ens_extrema(ocn_ens *e, int32_t field_id, ocn_ens_extrema_t *out)
+{
+    static_assert(sizeof(EnsPartial) == sizeof(ocn_ens_extrema_t), "EnsPartial is ocn_ens_extrema_t");
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    const ocn_ctx *c0 = e->m[0];
+    if (!out || !has_r8(c0, field_id)) return set_error(OCN_ERR_ARG, "ens_extrema: null result or not a real(8) field of the members");
+    HIPCHK(hipSetDevice(e->device));
+    const size_t M = e->m.size(), nblk = c0->blocks.size();
+    std::vector<EnsExtBlock> blk(nblk);
+    int tiles = 0;
+    for (size_t k = 0; k < nblk; ++k) {
+        const ocn_block &g = c0->blocks[k].g;
+        EnsExtBlock &q = blk[k];
+        q.w = g.nx_end - g.nx_start + 1;
+        q.h = g.ny_end - g.ny_start + 1;
+        q.off = (long)(g.ny_start - g.bnd_y1) * g.pitch + (g.nx_start - g.bnd_x1);
+        q.pitch = (long)g.pitch;
+        q.first_tile = tiles;
+        tiles += ens_extrema_tiles(q.w, q.h, &q.tiles_x);
+    }
+    for (size_t i = 0; i < M; ++i) {
+        out[i].min = (double)INFINITY;
+        out[i].max = -(double)INFINITY;
+        out[i].nonfinite = out[i].count = 0;
+    }
+    if (tiles < 1) return OCN_OK;
+    const size_t blk_b = ((sizeof(EnsExtBlock) * nblk + 255) / 256) * 256,
+                 tab_b = ((sizeof(EnsExtSrc) * M * nblk + 255) / 256) * 256,
+                 part_b = ((sizeof(EnsPartial) * M * (size_t)tiles + 255) / 256) * 256;
+    const size_t res_b = sizeof(EnsPartial) * M;
+    if (!e->d_ext) HIPCHK(hipMalloc(&e->d_ext, blk_b + tab_b + part_b + res_b));
+    if (!e->h_ext) HIPCHK(hipHostMalloc(&e->h_ext, blk_b + tab_b + res_b, hipHostMallocDefault));
+    int first = OCN_OK;
+    char *d = (char *)e->d_ext, *h = (char *)e->h_ext;
+    EnsExtSrc *tab = (EnsExtSrc *)(h + blk_b);
+    for (size_t i = 0; i < M; ++i) {
+        ocn_ctx *c = e->m[i];
+        if (const int rc = guarded(c, "ocn_ens_extrema", [&] { return complete_open(c); }); rc && !first) first = rc;
+        for (size_t k = 0; k < nblk; ++k)
+            tab[i * nblk + k] = EnsExtSrc{c->blocks[k].f<double>(field_id), c->blocks[k].f<float>(OCN_LU)};
+    }
+    if (first) return first;
+    // the tables up, the launches, the results down, all on the ensemble's stream, and one wait (a
+    // synchronous entry: the previous call has ended, nothing reads the pinned tables now)
+    memcpy(h, blk.data(), sizeof(EnsExtBlock) * nblk);
+    HIPCHK(hipMemcpyAsync(d, h, blk_b + tab_b, hipMemcpyHostToDevice, e->stream));
+    EnsPartial *res = (EnsPartial *)(d + blk_b + tab_b + part_b);
+    RC(launch_ens_extrema((const EnsExtBlock *)d, (int)nblk, (const EnsExtSrc *)(d + blk_b), (int)M, tiles,
+                          (EnsPartial *)(d + blk_b + tab_b), res, e->stream));
+    HIPCHK(hipMemcpyAsync(h + blk_b + tab_b, res, res_b, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    memcpy(out, h + blk_b + tab_b, res_b);
+    return OCN_OK;
 }
 
 }  // extern "C"

@@ -215,6 +215,26 @@ size_t onepass_multi_b_entry_bytes();
 long onepass_multi_b_capacity();
 int launch_onepass_multi_b(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
                            int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, hipStream_t s);
+// Statistics over the members of an ensemble (ens_stats.hip; ocn_sw.h ocn_ens_stats): of the n arrays
+// src[0 .. n) (one field of one block geometry in member order, all with the lane of A(bnd_x1, :) in its
+// 256-B line that src[0] has) into out[0 .. 5) = mean, variance, spread, minimum, maximum (based like the
+// sources; nullptr: not stored), every point of A(bnd_x1:bnd_x2, bnd_y1:bnd_y2), ONE launch.  need_var:
+// the variance is formed (for out[1] or out[2]; n >= 2).  Up to kEnsStatsReg members the values stay in
+// registers between the two passes.
+constexpr int kEnsStatsReg = 32;
+int launch_ens_stats(const ocn_block *b, const double *const *src, int n, bool need_var, double *const out[5],
+                     hipStream_t s);
+// Per-member extrema (ocn_ens_extrema): EnsPartial is ocn_ens_extrema_t's layout.  d_blk[k]: block k's
+// interior (w x h points from element `off` of its arrays) and its first tile of the grid's x dimension
+// (ens_extrema_tiles(w, h) tiles each, tiles_x of them per tile row); d_tab[member * nblk + k]: that
+// member's field and lu of block k; d_part: members x ntiles partials; d_out: members results.  Two
+// launches: a wave per tile and member, then a wave per member.
+struct EnsPartial { double min, max; long long nonfinite, count; };
+struct EnsExtBlock { long off, pitch; int w, h, first_tile, tiles_x; };
+struct EnsExtSrc { const double *src; const float *lu; };
+int ens_extrema_tiles(int w, int h, int *tiles_x);
+int launch_ens_extrema(const EnsExtBlock *d_blk, int nblk, const EnsExtSrc *d_tab, int members, int ntiles,
+                       EnsPartial *d_part, EnsPartial *d_out, hipStream_t s);
 // the known-constant precondition of launch_onepass over r (sw_kernels.hip FallbackCheck: the
 // fallback points and the forcing hold +0.0, h_r and mu are uniform): ORs 1 into *flag where it
 // does not hold; writes h_r and mu at (r.m0, r.n0) to kc[0], kc[1]

@@ -15,6 +15,7 @@ from . import _lib
 from ._lib import check, lib
 from .config import BasinConfig, ParallelConfig, SWConfig
 from .model import BlockInfo, OceanModel
+from .output import UNDEF
 
 
 class _Member(OceanModel):
@@ -147,6 +148,63 @@ class OceanEnsemble:
         check(lib().ocn_ens_info(self.ens, C.byref(i)), "ocn_ens_info")
         return {"members": int(i.members), "groups": int(i.groups), "batched": int(i.batched), "rows": int(i.rows),
                 "tiles": int(i.tiles), "max_group": int(i.max_group), "capacity": int(i.capacity)}
+
+    # ------------------------------------------------------------ statistics over the members
+    def _use(self, members):
+        """ocn_ens_stats' `use` array: None (all), or one byte per member from an iterable of indices
+        (their order does not matter: the statistics run in member order)."""
+        if members is None:
+            return None
+        use = (C.c_uint8 * len(self.members))()
+        for i in members:
+            if not 0 <= int(i) < len(self.members):
+                raise IndexError(f"member {i} of {len(self.members)}")
+            use[int(i)] = 1
+        return use
+
+    @staticmethod
+    def _what(what) -> int:
+        names = (what,) if isinstance(what, str) else tuple(what)
+        bits = 0
+        for n in names:
+            bits |= _lib.ENS_STATS[n]
+        return bits
+
+    def stats(self, name: str, what=("mean", "spread"), members=None, k: int = 0) -> dict[str, np.ndarray]:
+        """Per-point statistics of real(8) field `name` of block k over `members` (indices; None: all),
+        formed on the device in one launch (ocn_ens_stats; the definitions are in include/ocn_sw.h):
+        {statistic: float64 array of the block's array shape, Fortran order} for the names in `what`
+        ("mean", "var", "spread", "min", "max").  Pending call tails of the members in use are formed first."""
+        names = (what,) if isinstance(what, str) else tuple(what)
+        L = lib()
+        check(L.ocn_ens_stats(self.ens, k, _lib.FIELD_ID[name], self._use(members), self._what(names)), "ocn_ens_stats")
+        out = {}
+        for n in names:
+            a = np.zeros(self.members[0].blocks[k].shape, dtype=np.float64, order="F")
+            check(L.ocn_ens_stats_download(self.ens, k, _lib.ENS_STATS[n], a.ctypes.data_as(C.c_void_p)),
+                  "ocn_ens_stats_download")
+            out[n] = a
+        return out
+
+    def stats_output_r4(self, name: str, stat: str, k: int = 0, undef: float = float(UNDEF), members=None) -> np.ndarray:
+        """The output record of one statistic of field `name` on block k's interior: real(4), `undef`
+        where member 0's lu says land (ocn_ens_stats_output_r4: OceanModel.output_r4's rule and layout)."""
+        L = lib()
+        check(L.ocn_ens_stats(self.ens, k, _lib.FIELD_ID[name], self._use(members), _lib.ENS_STATS[stat]), "ocn_ens_stats")
+        b = self.members[0].blocks[k]
+        a = np.zeros((b.nx_end - b.nx_start + 1, b.ny_end - b.ny_start + 1), dtype=np.float32, order="F")
+        check(L.ocn_ens_stats_output_r4(self.ens, k, _lib.ENS_STATS[stat], C.c_float(undef),
+                                        a.ctypes.data_as(C.c_void_p)), "ocn_ens_stats_output_r4")
+        return a
+
+    def extrema(self, name: str) -> list[dict]:
+        """Per member, over the interior sea points of real(8) field `name` on all blocks: min and max over
+        the finite values (+inf / -inf with none), nonfinite (NaN, +-Inf) and count (sea points) --
+        which member is about to blow up, without a download (ocn_ens_extrema).  Synchronous."""
+        out = (_lib.OcnEnsExtrema * len(self.members))()
+        check(lib().ocn_ens_extrema(self.ens, _lib.FIELD_ID[name], out), "ocn_ens_extrema")
+        return [{"min": float(x.min), "max": float(x.max), "nonfinite": int(x.nonfinite), "count": int(x.count)}
+                for x in out]
 
     @property
     def interior_cells(self) -> int:

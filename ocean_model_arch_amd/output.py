@@ -110,6 +110,12 @@ def _rank_barrier(model, barrier):
 def write_data(model, path: str, fname: str, nrec: int, name: str, barrier=None):
     """io.f90:276-386 write_data2D_real4 of field `name` (real(8) fields are converted like
     bufwp4%copy_from_real8) into record nrec (1-based) of path/fname."""
+    _write_record(model, path, fname, nrec, lambda b: model.output_r4(b.k, name, float(UNDEF)), barrier)
+
+
+def _write_record(model, path: str, fname: str, nrec: int, block_r4, barrier=None):
+    """write_data's record writer: block_r4(b) is the real(4) interior of block b of `model`'s blocks
+    (land already undef), written where io.f90 puts it in record nrec of path/fname."""
     barrier = _rank_barrier(model, barrier)
     nx, ny = model.basin.nx, model.basin.ny
     nxb, nxe, nyb, nye = 3, nx - 2, 3, ny - 2           # mmm, mm, nnn, nn (basinpar)
@@ -125,7 +131,7 @@ def write_data(model, path: str, fname: str, nrec: int, name: str, barrier=None)
         barrier()
     with open(fn, "r+b") as fh:                          # io.f90:318-356: every block's interior
         for b in model.blocks:
-            a = model.output_r4(b.k, name, float(UNDEF))
+            a = block_r4(b)
             for j in range(a.shape[1]):
                 fh.seek((nrec - 1) * recl + ((b.ny_start + j - nyb) * gw + (b.nx_start - nxb)) * 4)
                 fh.write(np.ascontiguousarray(a[:, j], dtype="<f4").tobytes())
@@ -174,6 +180,24 @@ def local_output(model, nrec: int, t: LocalOutputTime, path: str = "RESULTS/", b
     if model.sw.use_tracers > 0:
         write_data(model, path, "ff1.dat", nrec, f"ff1_{model.sw.tracer_num}", barrier)
         ctl("ff1.dat", nrec, 0, "ff1 (last)", "ff1")
+
+
+def ensemble_output(ens, nrec: int, t: LocalOutputTime, path: str = "RESULTS/", members=None):
+    """Record nrec of an ensemble's products, formed on the device (OceanEnsemble.stats_output_r4): the
+    mean and the spread of ssh over `members` (indices; None: all) as ssh_mean.dat / ssh_spread.dat, and
+    of ff1(tracer_num) as ff1_mean.dat / ff1_spread.dat with tracers -- write_data's record layout, land
+    undef by member 0's mask, each with its .ctl.  The reference has no counterpart (one model per run)."""
+    m0 = ens.members[0]
+    b = m0.basin
+    fields = [("ssh", "ssh", "SSH")] + ([(f"ff1_{m0.sw.tracer_num}", "ff1", "ff1 (last)")] if m0.sw.use_tracers > 0 else [])
+    for name, var, title in fields:
+        for stat in ("mean", "spread"):
+            fname = f"{var}_{stat}.dat"
+            _write_record(m0, path, fname, nrec,
+                          lambda blk: ens.stats_output_r4(name, stat, k=blk.k, undef=float(UNDEF), members=members))
+            ctl_file_write(os.path.join(path, fname), UNDEF, b.nx - 4, b.ny - 4, 1, nrec, 0, [b.rlon], b.dxst, 0,
+                           [b.rlat], b.dyst, 0, [0.0], 1.0, t.calendar, t.year, t.month, t.day, t.hour, t.minute,
+                           t.tstep, f"{title}, ensemble {stat}", f"{var}_{stat}")
 
 
 def run(model, nsteps: int, tau: float, t: LocalOutputTime, path: str = "RESULTS/", barrier=None):
