@@ -35,8 +35,9 @@ def _sections(elf: bytes):
     return out
 
 
-def gfx950_code_object(lib_path: str) -> bytes:
-    """The gfx950 code object (ELF) bundled in the library's .hip_fatbin section."""
+def gfx950_code_objects(lib_path: str):
+    """Every gfx950 code object (ELF) bundled in the library's .hip_fatbin section, in link order: one
+    per object file that holds device code."""
     data = open(lib_path, "rb").read()
     off, size, _addr, _i = _sections(data)[".hip_fatbin"]
     fat = data[off:off + size]
@@ -49,8 +50,14 @@ def gfx950_code_object(lib_path: str) -> bytes:
             triple = fat[p + 24:p + 24 + tlen].decode()
             p += 24 + tlen
             if triple.endswith("gfx950"):
-                return fat[pos + eoff:pos + eoff + esize]
+                yield fat[pos + eoff:pos + eoff + esize]
         pos = fat.find(_BUNDLE_MAGIC, pos + 1)
+
+
+def gfx950_code_object(lib_path: str) -> bytes:
+    """The first gfx950 code object of the library: sw_kernels.hip's, the first on the link line."""
+    for code in gfx950_code_objects(lib_path):
+        return code
     raise ValueError("no gfx950 code object in " + lib_path)
 
 

@@ -1,36 +1,12 @@
-// ocn_ctx.hip -- PSy layer of the MI355X shallow-water step: model context, decomposition,
-// device storage, initial state, halo exchange (intra-device copies + RCCL), step driver.
+// ocn_ctx.hip -- PSy layer of the MI355X shallow-water step: the stages, every step form, the call
+// planner (step_impl, complete_open, run_deferred, finish_call), check_coherence and the ocn_ctx_*
+// entries of the C ABI.  The context itself is ocn_ctx.h; its halo exchange is ctx_comm.hip, its
+// decomposition, storage and initial state ctx_setup.hip, the ensemble layer ocn_ens.hip.
 //
 // Reference counterparts (Andrcraft9/ocean_model_arch):
-//   storage        core/data_types.f90:44-144, core/ocean.f90:14-48, core/grid.f90:23-90
-//   decomposition  core/decomposition.f90:427-503 (uniform blocks), :614-669 (block -> rank),
-//                  :672-760 (local numbering, _MPP_SORTED_BLOCKS_), :950-1062 (neighbour maps)
 //   dispatcher     core/kernel_interface.f90:48-119 (envoke) + interface/shallow_water/sw_interface.f90
 //   algorithm      control/shallow_water/shallow_water.f90:22-94 (expl_shallow_water)
-//   halo           shared/mpp/sync.f90:294-556 + syncborder_block2D_gen_all.fi
-//   init           control/init_data.f90:29-125, kernel/service/grid_kernels.f90,
-//                  kernel/service/grid_parameters.f90:80-181, kernel/shallow_water/vel_ssh.f90:15-38
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
-#include <algorithm>
-#include <array>
-#include <atomic>
-#include <chrono>
-#include <cmath>
-#include <condition_variable>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <deque>
-#include <map>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
-
-#include "ocn_internal.h"
-#include "ocn_ens_plan.h"
+#include "ocn_ctx.h"
 
 namespace ocn {
 
@@ -51,106 +27,6 @@ int check_hip(hipError_t e, const char *what)
     return set_error(OCN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-#define HIPCHK(call)                                          \
-    do {                                                      \
-        int _rc = check_hip((call), #call);                   \
-        if (_rc) return _rc;                                  \
-    } while (0)
-#define RC(call)                                              \
-    do {                                                      \
-        int _rc = (call);                                     \
-        if (_rc) return _rc;                                  \
-    } while (0)
-
-
-// ------------------------------------------------------------------ halo segments
-// w strided 1-D runs of doubles side by side: dst[i*dst_stride + j*dst_jstride] =
-// src[i*src_stride + j*src_jstride], i < count, j < w.  A column strip several layers deep is one
-// such segment (merge_columns: w adjacent columns), so a wave's loads take the layers of 64 / w rows
-// from shared cache lines instead of one line per element and layer.
-struct Seg {
-    const double *src;
-    double *dst;
-    long src_stride, dst_stride;
-    int count;
-    int w = 1;
-    long src_jstride = 0, dst_jstride = 0;
-};
-
-// Grid: one workgroup per 64-element chunk of a segment (SegChunk: the chunk table of the list, so
-// no workgroup of a short segment idles as in a segments x longest-chunks grid); element e of a
-// segment: run j = e % w, row i = e / w -- one element per thread and one wave per workgroup, so
-// every load of a strip is in flight at once, spread over many CUs (a loop per workgroup would pay
-// one memory round trip per pass).
-constexpr int kSegChunk = 64;
-struct SegChunk { int seg, e0; };
-__device__ __forceinline__ bool seg_at(const Seg &g, int e, long &si, long &di)
-{
-    if (e >= g.count * g.w) return false;
-    const int i = e / g.w, j = e - i * g.w;
-    si = (long)i * g.src_stride + (long)j * g.src_jstride;
-    di = (long)i * g.dst_stride + (long)j * g.dst_jstride;
-    return true;
-}
-__global__ __launch_bounds__(kSegChunk) void k_segments(const Seg *__restrict__ segs, const SegChunk *__restrict__ ch,
-                                                        int nch)
-{
-    const int b = blockIdx.x;
-    if (b >= nch) return;
-    const SegChunk q = ch[b];
-    const Seg g = segs[q.seg];
-    long si, di;
-    if (!seg_at(g, q.e0 + (int)threadIdx.x, si, di)) return;
-    g.dst[di] = g.src[si];
-}
-
-// The same runs compared instead of copied: ORs 1 into *flags where dst differs from src (bits).
-__global__ __launch_bounds__(kSegChunk) void k_segments_cmp(const Seg *__restrict__ segs, const SegChunk *__restrict__ ch,
-                                                            int nch, int32_t *flags)
-{
-    const int k = blockIdx.x;
-    if (k >= nch) return;
-    const SegChunk q = ch[k];
-    const Seg g = segs[q.seg];
-    long si, di;
-    if (!seg_at(g, q.e0 + (int)threadIdx.x, si, di)) return;
-    const double a = g.dst[di], b = g.src[si];
-    unsigned long long x, y;
-    __builtin_memcpy(&x, &a, 8);
-    __builtin_memcpy(&y, &b, 8);
-    if (x != y) atomicOr(flags, 1);
-}
-
-// A segment list on the device with its chunk table (make_seglist)
-struct SegList {
-    Seg *d = nullptr;
-    SegChunk *ch = nullptr;
-    int n = 0, nch = 0;
-};
-
-// init_grid_data's bottom topography (control/init_data.f90:115-120): read_data2D_real4 fills the
-// block's interior from the file (tools/io.f90:130-147; the file holds the (nx-4) x (ny-4) interior,
-// Fortran order) and zeroes every point with |lu| < 0.5 (:158-171), the rest of the zero-initialised
-// array stays 0, then copy_from_real4 promotes it (core/data_types.f90:638-652); the sync follows.
-__global__ void k_topography(ocn_block g, double *h, const float *lu, const float *topo, int nxi)
-{
-    const int w = g.bnd_x2 - g.bnd_x1 + 1, rows = g.bnd_y2 - g.bnd_y1 + 1;
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)w * rows) return;
-    const int m = g.bnd_x1 + (int)(i % w), n = g.bnd_y1 + (int)(i / w);
-    const long at = (long)(m - g.bnd_x1) + (long)(n - g.bnd_y1) * g.pitch;
-    float v = 0.0f;
-    if (m >= g.nx_start && m <= g.nx_end && n >= g.ny_start && n <= g.ny_end) v = topo[(long)(m - 3) + (long)(n - 3) * nxi];
-    if (fabsf(lu[at]) < 0.5f) v = 0.0f;
-    h[at] = (double)v;
-}
-
-__global__ void k_fill_r8(double *p, long n, double v)
-{
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
 // One output record of a field (output.f90:101-106 copy_from_real8 + io.f90:343-349): real(4) of
 // the interior value, undef where |lu| < 0.5; dst is the packed interior, Fortran order.
 template <typename T>
@@ -161,855 +37,14 @@ __global__ void k_output_r4(const T *src, const float *lu, long pitch, int w, in
     const long s = (long)j * pitch + i;
     dst[(long)j * w + i] = fabsf(lu[s]) < 0.5f ? undef : (float)src[s];
 }
-
-// ------------------------------------------------------------------ geometry helpers
-// decomposition.f90:94-290, directions macros/kernel_macros.fi:4-12
-struct Rect { int x0, x1, y0, y1; };
-static const int kDirDm[9] = {0, 1, -1, 0, 0, 1, 1, -1, -1};
-static const int kDirDn[9] = {0, 0, 0, 1, -1, 1, -1, 1, -1};
-
-// Strip of a Rect inside a block array as (offset, count, stride): a 1-wide rect is a row
-// (stride 1) or a column (stride pitch).
-static void strip(const ocn_block &b, const Rect &r, long &off, int &count, long &stride)
+int launch_output_r4(const double *src, const float *lu, long pitch, int w, int h, float undef, float *dst,
+                     hipStream_t s)
 {
-    off = (long)(r.x0 - b.bnd_x1) + (long)(r.y0 - b.bnd_y1) * (long)b.pitch;
-    if (r.y0 == r.y1) { count = r.x1 - r.x0 + 1; stride = 1; }
-    else { count = r.y1 - r.y0 + 1; stride = (long)b.pitch; }
-}
-
-}  // namespace ocn
-
-using namespace ocn;
-
-// ------------------------------------------------------------------ context
-struct GBlock {            // one block of the global block grid
-    int bm, bn;
-    ocn_block g;           // pitch filled for local blocks only
-    int rank;              // -1 land block (bglob_proc = -1)
-    int k;                 // local index on its rank
-    double weight;         // sea points (bglob_weight)
-};
-
-struct LBlock {
-    ocn_block g;
-    int bm, bn, gid;
-    int nbr_rank[8], nbr_k[8], nbr_gid[8];
-    void *slab = nullptr;
-    std::vector<void *> ptr;           // field table, indexed by field_slot(id)
-    uint8_t *bits = nullptr;           // compact static fields (sw_stencils.h): mask bytes
-    float *rows = nullptr;             // and metric row tables
-    void *sshp_alt = nullptr;          // second sshp buffer of the recompute steps (one_step_fused)
-    void *up_alt = nullptr, *vp_alt = nullptr;   // second ubrtrp / vbrtrp buffers of the one-pass steps
-    std::vector<void *> ffp_alt;       // second ff1p buffer of every tracer (one-pass steps' tracer step)
-    double *kc = nullptr;              // device: h_r, mu of the one-pass step's known-constant variant
-    // one_step_x2 (one 2-deep state exchange per one-pass step, the march over the whole interior):
-    unsigned own = 0;                  // halo points neighbour blocks own (sw_stencils.h own_class bits)
-    float *ext = nullptr;              // metric values of rows bnd_y1 / bnd_y2 as the neighbours form them
-    float *rows_x = nullptr;           // the row table with those two rows (launch_rows_ext)
-    double *hr_x = nullptr;            // h_r with its second halo ring from the neighbours
-    double *ring2 = nullptr;           // the state's second halo ring as the reference leaves it (saved)
-    // one_step_x4 (two one-pass steps per launch, one 4-deep state exchange per pair): mask bytes and the
-    // row table over the block widened by kXRing rings (launch_x4_tables; bits_x4 based at
-    // A(bnd_x1 - kXRing, bnd_y1 - kXRing), pitch g.pitch)
-    uint8_t *bits_x4 = nullptr;
-    float *rows_x4 = nullptr;
-    SegList save, restore;   // its save / restore runs (k_segments)
-    // x4 pairs with tracers: the first step's new ssh, sshp, ubrtr, vbrtr (based like the fields: kXRing
-    // extra rows; MarchStep::trs), the state the second tracer step reads
-    double *trs[4] = {nullptr, nullptr, nullptr, nullptr};
-    template <typename T> T *f(int id) const { return (T *)ptr[field_slot(id)]; }
-};
-
-// Loopback transport (ocn_ctx_attach_loopback): the N ranks of a decomposition as N contexts of
-// ONE process on one device, each driven by its own host thread.  It replaces exactly two RCCL
-// calls and nothing else -- the ncclRecv / ncclSend pair of an exchange (run_sync) and the
-// ncclAllReduce of the role-flip vote (check_coherence) -- so the remote branch of the halo plans
-// (device pack / unpack, per-peer messages, per-role plans, sync_ca, overlap forks) runs as in
-// production.  An exchange is two host rendezvous with the peers:
-//   A: each rank has enqueued its pack and recorded lb_ev_a, and publishes its plan; then every
-//      rank copies each peer's send buffer (for it) into its own receive buffer, on its stream,
-//      after the peer's lb_ev_a, and records lb_ev_b;
-//   B: every rank's stream waits for its peers' lb_ev_b, so no send buffer is repacked before the
-//      peer's copy out of it has run (the completion guarantee of ncclGroupEnd).
-// The counters make the rendezvous of the k-th exchange of every rank meet (all ranks run the
-// same sequence of exchanges, as with RCCL); a peer cannot pass phase A of exchange k+1 before
-// this rank passed phase B of exchange k, so a published plan / recorded event is never replaced
-// before it was consumed.
-struct HaloPlan;
-struct Loopback {
-    int n = 0;
-    std::vector<ocn_ctx *> ctx;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<uint64_t> cnt[4];              // per rank: exchange A/B, reduce A/B phases passed
-    std::vector<const HaloPlan *> plan;        // plan of the rank's current exchange (phase A)
-    std::vector<int32_t *> vote;               // the rank's flag word (reduce phase A)
-    bool failed = false;
-    int refs = 0;
-};
-
-struct HaloPlan {
-    SegList local;                    // intra-process copies
-    // remote: per peer rank, pack segments (into send buffer) and unpack segments (from recv)
-    struct Peer { int rank; long count; double *send, *recv; };
-    std::vector<Peer> peers;
-    SegList pack, unpack;
-};
-
-namespace ocn {
-// What one step of an ocn_ctx_step call runs: check = check_ssh_err; first / last step of the
-// call; flip = role-flip step; a_done = its fused A already ran (fused into the previous step's
-// hh_init launch); next_a = fuse the next step's fused A into this step's hh_init (MarchCA),
-// next_reuse = the next step is a reuse step; rc = recompute steps (fused B forms hhq, hhu_p,
-// hhv_p itself and writes sshp's filter into the second sshp buffer), rc_next = the next step is
-// one (this step's hh_init + A launch then does not store hhq on the interior, hhu_p, hhv_p).
-// one = one-pass step (sw_kernels.hip MarchStep), next_one = the next step is one (this step
-// then runs no hh_init: the one-pass step forms hh_init's values itself).
-// x2 = the one-pass step as one_step_x2 (2-deep state exchange, whole-interior march); x2_save = the
-// first of a sequence (the reference's second halo ring of the state is saved first); x2_end = a
-// last step after such a sequence (that ring restored and the state's first ring exchanged first).
-// pair = this one-pass step and the next as one launch (one_step_pair), check2 = the next one's check.
-// multi = this many one-pass steps in one launch (one_step_multi), each checked if check.
-struct StepKind {
-    bool check, first, last, flip, a_done, next_a, next_reuse, rc, rc_next, one, next_one, one_last;
-    bool x2, x2_save, x2_end;
-    bool pair = false, check2 = false;
-    int multi = 0;
-    bool operator==(const StepKind &o) const
-    {
-        return check == o.check && first == o.first && last == o.last && flip == o.flip && a_done == o.a_done &&
-               next_a == o.next_a && next_reuse == o.next_reuse && rc == o.rc && rc_next == o.rc_next &&
-               one == o.one && next_one == o.next_one && one_last == o.one_last && x2 == o.x2 &&
-               x2_save == o.x2_save && x2_end == o.x2_end && pair == o.pair && check2 == o.check2 && multi == o.multi;
-    }
-};
-
-}  // namespace ocn
-
-// ocn_ctx::fb_state
-enum { kFbUnchecked = 0, kFbDevice = 1, kFbZero = 2, kFbGeneral = 3, kFbHr = 4 };
-
-#ifndef OCN_COMM_PRIO
-#define OCN_COMM_PRIO 1   // the comm stream at the device's highest stream priority
-#endif
-struct ocn_ctx {
-    ocn_basin basin;
-    ocn_sw_params sw;
-    ocn_decomp dec;
-    std::vector<int32_t> mask;         // global (nx, ny) column-major
-    std::vector<float> topo;           // bottom topography, (nx-4) x (ny-4) interior points (empty: none)
-    int bnx = 1, bny = 1;
-    std::vector<GBlock> gblocks;       // (bm-1) + (bn-1)*bnx
-    std::vector<LBlock> blocks;
-    hipStream_t stream = nullptr;
-    hipStream_t comm_stream = nullptr;  // halo exchanges overlapped with interior compute
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // the known-constant check's verdict copied to pinned host memory behind an event: a later call
-    // reads it once the event has completed (hipEventQuery: no wait), learn_fb_async
-    hipEvent_t ev_fb = nullptr;
-    int32_t *h_fbz = nullptr;
-    bool fb_copy = false;
-    int overlap = -1;            // OCN_OPT_OVERLAP: 0 none, 1 standard steps, 2 + role-flip steps, -1 auto
-    // OCN_OPT_OVERLAP auto with peers on other ranks: the x2 / x4 steps' form (inner part beside the
-    // exchange, or exchange then march) chosen from a measurement (ov_begin): ov_state 0 = nothing
-    // measured, 1 = a sequential step's events recorded, 2 = an overlapped one's too (the next vote
-    // reduces them), 3 = decided (ov_level); ov_kind = the step form measured (2: x2 steps, 4: x4 pairs);
-    // ov_ms = the two step times (this rank's, then the maxima over the ranks the decision used)
-    int ov_state = 0, ov_kind = 0, ov_level = 2;
-    hipEvent_t ov_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    double ov_ms[2] = {0.0, 0.0};
-    int xdelay_us = 0;           // OCN_OPT_XCHG_DELAY (tests): a device wait before each exchange with remote peers
-    int32_t *d_nbad = nullptr;
-    unsigned *d_bar = nullptr;   // the multi-step launch's grid-barrier words (kMultiBarBytes)
-    ncclComm_t comm = nullptr;
-    bool comm_aborted = false;         // fail_fatal aborted the communicator: calls with exchanges fail
-    Loopback *lb = nullptr;            // test transport between contexts of one process (ocn_ctx_attach_loopback)
-    hipEvent_t lb_ev_a = nullptr, lb_ev_b = nullptr;
-    std::map<std::vector<int>, HaloPlan> plans;
-    bool initialized = false;
-    bool use_graph = false;
-    // the launches a captured step replays depend on everything in its key (march and ring_sea
-    // select launch forms and the ring launch; options that change them also drop the cache)
-    struct Graph { hipGraphExec_t exec; double tau; ocn::StepKind kind; bool compact, march, ring_sea; int role, kc_mode; };
-    std::vector<Graph> graphs;         // one captured step per key
-    std::vector<void *> allocs;
-    // per-stage HIP-event timing (OCN_OPT_STAGE_TIMING): pending (stage, start, stop) records
-    bool stage_timing = false;
-    struct Rec { int stage; hipEvent_t a, b; };
-    std::vector<Rec> recs;
-    std::vector<hipEvent_t> event_pool;
-    double stage_ms[OCN_NUM_TIMERS] = {0};
-    int64_t stage_n[OCN_NUM_TIMERS] = {0};
-    bool fused = true;
-    std::vector<int> sync_a, sync_a_reuse, sync_b, sync_ca, sync_ca_reuse;
-    // compact static fields: requested (OCN_OPT_COMPACT), in use, stale (real(4) fields
-    // changed since they were built), or unusable because raw real(4) pointers were handed out
-    bool compact_req = true, compact = false, static_dirty = true;
-    bool march = true;   // OCN_OPT_MARCH
-    mutable bool r4_escaped = false;
-    // role-flip steps (one_step_fused): role = 1 while the ssh/sshn, ubrtr/ubrtrn, vbrtr/vbrtrn
-    // buffers of every block are swapped (only inside an ocn_ctx_step call); coherent = the pairs
-    // agree outside their write sets (sw_stencils.h Coherence), coherent_known = that was checked
-    // after the state last changed outside ocn_ctx_step; r8_escaped = raw pointers of a pair were
-    // handed out (check at every call); flip = OCN_OPT_FLIP
-    bool flip = true, coherent = false, flip_used = false, rc_used = false;
-    bool capturing = false;      // a step is being captured into a hipGraph
-    bool sync_pending = false;   // an exchange on comm_stream not yet joined (fork_sync)
-    bool ring_sea = true;   // some halo-ring point has a mask set (Prepare); else no ring launch
-    bool udiv_ok = true;    // every row divisor of the one-pass step in [2^-60, 2^60] (Prepare)
-    bool recompute = true;  // OCN_OPT_RECOMPUTE: recompute steps in role-flip calls
-    bool onepass = true;    // OCN_OPT_ONEPASS: one-pass steps in single-block role-flip calls
-    // OCN_OPT_PAIR: two one-pass steps per launch (one_step_pair) -- 0 never, 1 on blocks of at least
-    // kPairMinCells interior points, 2 on any block; pair_used: a call ran one
-    int pair = 1;
-    bool pair_used = false;
-    // OCN_OPT_MULTI: the one-pass steps of a small single block as one launch per call
-    // (one_step_multi); multi_used: the last call ran one
-    bool multi = true, multi_used = false;
-    // OCN_OPT_TRACER_STEP: tracer runs with one-pass steps -- expl_tracer of each step as one launch per
-    // tracer (run_tracer_step), run with the next step, after its exchange; tr_call: this call does;
-    // tr_pending: the current state's tracer step has not run yet; tr_alt_ok: the second ff1p
-    // buffers agree with the fields outside the tracer step's write set.  Role bits 8 (ff1 / ff1n
-    // traded) and 16 (ff1p / its second buffer traded), for every tracer at once.
-    bool tr_step = true, tr_call = false, tr_pending = false;
-    bool tr_forked = false;   // a tracer step runs on the comm stream beside the march (joined by run_step)
-    mutable bool tr_alt_ok = false;
-    bool known_const = true;   // OCN_OPT_KNOWN_CONSTANTS: the one-pass step's known-constant variant
-    bool last_hybrid = true;   // OCN_OPT_ONEPASS_LAST: one-pass last steps with exchanges / ring work too
-    bool one_used = false;
-    // the one-pass steps' second sshp / ubrtrp / vbrtrp buffers agree with the fields outside a8's
-    // write set (else they are copied at the start of the next such call)
-    mutable bool alt_ok = false;
-    // hh_init's stored depths were formed from the current state (the last step of the previous
-    // call or init_state ran it and nothing has changed the state since): the first step of a
-    // call may then be a one-pass step too, as a reuse step.  Never again once an r8 field's
-    // device pointer was handed out (it may be written behind our back).
-    mutable bool hh_consistent = false, r8_handed = false;
-    // hh_init's n level -- hqn = h_r and its interpolations hun / hvn / hhn (depth.f90:14-99 with
-    // ffs; no ssh in it) -- is what those arrays hold: a full hh_init wrote them from the current
-    // h_r, masks and metrics, and nothing has written them since (the one-pass, pair and
-    // multi-step launches never do).  last_finish's hh_init then leaves them as they are (32 B
-    // per cell of its 96 B of stores).  Cleared by every other step kind, by any upload, stage,
-    // sync or init, and never trusted once a raw pointer was handed out.
-    mutable bool hn_fresh = false;
-    // hhq_n may differ from h_r (an upload of either, or a raw pointer): every hh_init stores
-    // hhq_n = h_r, but the role-flip steps' fused hh_init + A (CA) does not, so the standard tracer
-    // stages after such a step copy it first (expl_tracer)
-    mutable bool hqn_stale = false;
-    // the one-pass step's known-constant precondition (sw_kernels.hip FallbackCheck: fallback points
-    // and forcing +0.0, h_r and mu uniform): kFbUnchecked until a check ran after the arrays last
-    // changed from outside the step; kFbDevice = its verdict is in device memory (d_fbz; both
-    // variants are launched and the device picks, ocn_ctx.hip never waits for it) until a host
-    // sync the caller makes anyway reads it (learn_fb): kFbZero / kFbHr (all but h_r: a
-    // non-uniform rest depth, read by the OCN_KC_KNOWN_HR variant) / kFbGeneral
-    mutable int fb_state = 0;
-    int kc_mode = 0;             // OCN_KC_* of the current call's one-pass launches
-    int32_t *d_fbz = nullptr;    // the check's verdict word
-    // lazy call tail (OCN_OPT_LAZY_TAIL): the last step run was a one-pass step; what the reference's
-    // last step leaves beyond the state (vort, stresses, RHS terms, hh_init's levels, a8's copies) is
-    // formed when the host next looks (complete_open: the step redone from the previous state, still
-    // intact in the other buffers, as the call's last step), so 1-step calls run one-pass steps
-    bool lazy = true, open = false, open_x2 = false;
-    double open_tau = 0.0;
-    // pairs in an open sequence (one_step_pair): open_pair = its last launch was a pair (the state
-    // before it is two steps back: complete_open redoes the pair's first step single, then the tail);
-    // deferred = the last 1 or 2 steps of the sequence, not yet run: a call runs pairs while 3 or
-    // more steps are pending and leaves the rest to the next call -- the 1-step cadence runs a pair
-    // every second call -- or to complete_open, which runs them as the last steps (a single + the
-    // last step, or the last step: no step run twice); synchronize runs them (as a pair or alone)
-    bool open_pair = false;
-    int deferred = 0;
-    bool deferred_check[2] = {false, false};
-    // one_step_x2 (OCN_OPT_X2): its static conditions (ext_ok: the real(4) fields are init_state's,
-    // so the ext rows are the neighbours' metric rows; rows_x_ok: their divisors in udiv's range;
-    // edge_ring_sea: a8 / a9 work on a halo ring no neighbour fills), the device checks of the last
-    // check_coherence (x2_dev_ok: the state's first halo ring holds the neighbours' values and its
-    // halo points no exchange fills hold +0.0), whether the h_r copy is current, and whether the
-    // state's second halo ring is saved (a sequence of x2 steps is under way)
-    bool x2 = true, rows_x_ok = false, edge_ring_sea = true, x2_dev_ok = false;
-    mutable bool ext_ok = false, hrx_ok = false;
-    bool ring2_saved = false, x2_used = false;
-    // one_step_x4 (OCN_OPT_X4): pairs of x2 steps with one 4-deep exchange each; x4_tab_ok: its tables
-    // were built from init_state's real(4) fields with every divisor in udiv's range; x4_dev_ok: the
-    // last vote found every rank able to run them (a communicator attached); x4_used: the last call did
-    // x4: 0 off, 1 auto (tracer runs: only with peers on other ranks), 3 always
-    int x4 = 1;
-    bool x4_tab_ok = false, x4_dev_ok = false, x4_used = false;
-    bool fb_x2 = false;          // the known-constant check's verdict is for the x2 range / tables
-    mutable bool coherent_known = false, r8_escaped = false;
-    int multi_spin = kMultiSpin;   // OCN_OPT_MULTI_SPIN (the multi-step launch's barrier bound)
-    // OCN_OPT_CO_LAUNCH: an x2 step's march and the previous state's tracer step as one launch;
-    // co_used: the last call did
-    bool co_launch = true, co_used = false;
-    double stage_max[OCN_NUM_TIMERS] = {0};   // longest record per timer (ocn_ctx_stage_stats)
-    // halo exchanges with remote peers (run_sync): how many were enqueued; while a watchdog is set an
-    // event after each (xq, under xmu) tells it the id of the last one the device completed (xdone)
-    int64_t xchg = 0, xdone = -1;
-    std::mutex xmu;
-    std::deque<std::pair<int64_t, hipEvent_t>> xq;
-    std::vector<hipEvent_t> xpool;
-    // host-side watchdog (ocn_ctx_set_watchdog): the thread, the call it watches (call_depth > 0: a
-    // guarded entry is running since call_t0), and whether it fired (wd_msg: what the calls return)
-    double wd_s = 0;
-    std::thread wd;
-    std::mutex wd_mu;
-    std::condition_variable wd_cv;
-    bool wd_stop = false;
-    int call_depth = 0;
-    std::chrono::steady_clock::time_point call_t0;
-    const char *call_name = "";
-    std::atomic<bool> wd_fired{false};
-    std::string wd_msg;
-    std::mutex comm_mu;          // the communicator is aborted once: by the watchdog or by fail_fatal
-    bool comm_abort_done = false;
-    int role = 0;
-    int steps_run = 0;           // launches statistics of the last call (ocn_ctx_get_option OCN_OPT_LAUNCHES)
-    int64_t launches = 0;
-    int32_t *d_flags = nullptr;
-    bool batch = true;           // OCN_OPT_BATCH
-    ocn::Batcher batcher;
-    // a member of an ensemble (ocn_ens_create): the ensemble owns the context and its compute stream,
-    // which the members share.  ens_collect (inside ocn_ens_step): step_impl plans a multi-step launch
-    // as ever but leaves it to the ensemble, which issues it with the other members' (ens_pending, ens_k)
-    ocn_ens *ens = nullptr;
-    bool ens_collect = false, ens_pending = false;
-    ocn::StepKind ens_k{};
-};
-
-// v on the device with its chunk table (one entry per kSegChunk elements of each segment), in one
-// allocation freed with the context
-static int make_seglist(ocn_ctx *c, const std::vector<Seg> &v, SegList &out)
-{
-    out = SegList{};
-    std::vector<SegChunk> ch;
-    for (size_t i = 0; i < v.size(); ++i)
-        for (long e = 0; e < (long)v[i].count * v[i].w; e += kSegChunk) ch.push_back(SegChunk{(int)i, (int)e});
-    if (v.empty() || ch.empty()) return OCN_OK;
-    const size_t sb = sizeof(Seg) * v.size(), cb = sizeof(SegChunk) * ch.size();
-    char *d = nullptr;
-    HIPCHK(hipMalloc(&d, sb + cb));
-    c->allocs.push_back(d);
-    HIPCHK(hipMemcpy(d, v.data(), sb, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d + sb, ch.data(), cb, hipMemcpyHostToDevice));
-    out.d = (Seg *)d;
-    out.ch = (SegChunk *)(d + sb);
-    out.n = (int)v.size();
-    out.nch = (int)ch.size();
-    return OCN_OK;
-}
-// the list's copies on s (cmp: compared instead, 1 ORed into *cmp where they differ)
-static int launch_segs(const SegList &l, hipStream_t s, int32_t *cmp = nullptr)
-{
-    if (!l.nch) return OCN_OK;
-    if (cmp) hipLaunchKernelGGL(k_segments_cmp, dim3((unsigned)l.nch), dim3(kSegChunk), 0, s, l.d, l.ch, l.nch, cmp);
-    else hipLaunchKernelGGL(k_segments, dim3((unsigned)l.nch), dim3(kSegChunk), 0, s, l.d, l.ch, l.nch);
+    hipLaunchKernelGGL(k_output_r4<double>, dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, s, src, lu,
+                       pitch, w, h, undef, dst);
     return check_launch();
 }
 
-namespace ocn {
-
-// real(8) fields of a context: the SW set, then flux_x, flux_y and ff1/ff1p/ff1n per tracer
-static int num_r8(const ocn_ctx *c)
-{
-    return OCN_NUM_R8 + (c->sw.use_tracers > 0 ? 2 + 3 * c->sw.tracer_num : 0);
-}
-static bool has_r8(const ocn_ctx *c, int id) { return id >= OCN_SSH && id < OCN_SSH + num_r8(c); }
-static bool has_field(const ocn_ctx *c, int id) { return is_r4(id) || has_r8(c, id); }
-
-// ------------------------------------------------------------------ decomposition
-// decomposition.f90:448-482: floor(real(remaining)/real(parts_left)) in default real(4)
-static std::vector<int> uniform_sizes(int total, int parts, std::string &err)
-{
-    std::vector<int> s;
-    int acc = 0;
-    for (int i = 1; i <= parts; ++i) {
-        int v = (i == parts) ? total - acc : (int)std::floor((float)(total - acc) / (float)(parts - i + 1));
-        if (v <= 0) { err = "Error in decomposition to uniform blocks: size <= 0"; return {}; }
-        s.push_back(v);
-        acc += v;
-    }
-    return s;
-}
-
-// MPI_Dims_create(n, 2): balanced, non-increasing factors (mpp.f90:89).
-static void dims_create(int n, int &d1, int &d2)
-{
-    d1 = n; d2 = 1;
-    for (int f = (int)std::floor(std::sqrt((double)n)); f >= 1; --f)
-        if (n % f == 0) { d1 = n / f; d2 = f; break; }
-}
-
-static int decompose(ocn_ctx *c)
-{
-    const int nx = c->basin.nx, ny = c->basin.ny;
-    std::string err;
-    auto xs = uniform_sizes(nx - 4, c->bnx, err);
-    auto ys = uniform_sizes(ny - 4, c->bny, err);
-    if (!err.empty()) return set_error(OCN_ERR_ARG, err);
-    int p1, p2;
-    dims_create(c->dec.nranks, p1, p2);
-    if (c->bnx % p1 || c->bny % p2)
-        return set_error(OCN_ERR_ARG, "mod(bnx, p_size(1)) or mod(bny, p_size(2)) not equal 0 (decomposition.f90:628)");
-    const int lbx = c->bnx / p1, lby = c->bny / p2;
-    c->gblocks.assign((size_t)c->bnx * c->bny, GBlock{});
-    int x0 = 0;
-    for (int bm = 1; bm <= c->bnx; ++bm) {
-        int y0 = 0;
-        for (int bn = 1; bn <= c->bny; ++bn) {
-            GBlock &g = c->gblocks[(size_t)(bm - 1) + (size_t)(bn - 1) * c->bnx];
-            g.bm = bm; g.bn = bn;
-            g.g.nx_start = 3 + x0; g.g.nx_end = g.g.nx_start + xs[bm - 1] - 1;
-            g.g.ny_start = 3 + y0; g.g.ny_end = g.g.ny_start + ys[bn - 1] - 1;
-            g.g.bnd_x1 = g.g.nx_start - 2; g.g.bnd_x2 = g.g.nx_end + 2;
-            g.g.bnd_y1 = g.g.ny_start - 2; g.g.bnd_y2 = g.g.ny_end + 2;
-            g.g.pitch = 0;
-            double w = 0.0;
-            for (int i = g.g.nx_start; i <= g.g.nx_end; ++i)
-                for (int j = g.g.ny_start; j <= g.g.ny_end; ++j)
-                    w += 1.0 - (double)c->mask[(size_t)(i - 1) + (size_t)(j - 1) * nx];
-            g.weight = w;
-            // create_uniform_decomposition: process coords (row-major cart), land blocks -> -1
-            const int c1 = (bm - 1) / lbx, c2 = (bn - 1) / lby;
-            g.rank = (w == 0.0) ? -1 : c1 * p2 + c2;
-            g.k = -1;
-            y0 += ys[bn - 1];
-        }
-        x0 += xs[bm - 1];
-    }
-    // local numbering per rank: _MPP_SORTED_BLOCKS_ = MINLOC over weight (column-major order)
-    std::vector<int> next(c->dec.nranks, 0);
-    std::vector<int> order(c->gblocks.size());
-    for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        return c->gblocks[a].weight < c->gblocks[b].weight;
-    });
-    for (int gid : order) {
-        GBlock &g = c->gblocks[gid];
-        if (g.rank >= 0) g.k = next[g.rank]++;
-    }
-    // local blocks of this rank, k order
-    std::vector<int> mine;
-    for (int gid : order)
-        if (c->gblocks[gid].rank == c->dec.rank) mine.push_back(gid);
-    c->blocks.clear();
-    for (int gid : mine) {
-        const GBlock &g = c->gblocks[gid];
-        LBlock lb;
-        lb.g = g.g;
-        lb.bm = g.bm; lb.bn = g.bn; lb.gid = gid;
-        const int w = g.g.bnd_x2 - g.g.bnd_x1 + 1;
-        // 512-B aligned rows for r8, with room for 2 * kXRing more columns (the extra halo rings of
-        // one_step_x4 live in the row padding: column bnd_x1 - j is the previous row's tail)
-        lb.g.pitch = (int64_t)((w + 2 * kXRing + 63) / 64 * 64);
-        for (int d = 1; d <= 8; ++d) {
-            const int m = g.bm + kDirDm[d], n = g.bn + kDirDn[d];
-            if (m < 1 || m > c->bnx || n < 1 || n > c->bny) {
-                lb.nbr_rank[d - 1] = -2; lb.nbr_k[d - 1] = -1; lb.nbr_gid[d - 1] = -1;
-            } else {
-                const int ng = (m - 1) + (n - 1) * c->bnx;
-                lb.nbr_rank[d - 1] = c->gblocks[ng].rank;
-                lb.nbr_k[d - 1] = c->gblocks[ng].k;
-                lb.nbr_gid[d - 1] = c->gblocks[ng].rank >= 0 ? ng : -1;
-            }
-            if (lb.nbr_rank[d - 1] >= 0)   // own_class(m) * 3 + own_class(n) of direction d's halo points
-                lb.own |= 1u << ((unsigned)(kDirDm[d] + 1) * 3u + (unsigned)(kDirDn[d] + 1));
-        }
-        c->blocks.push_back(lb);
-    }
-    return OCN_OK;
-}
-
-// ------------------------------------------------------------------ storage
-// The state arrays of the one-pass step as groups of physical buffers that agree on the second
-// halo ring (the reference never writes it; the pairs are coherent, the second buffers copies):
-// the field's own buffer first.
-static const int kStateIds[6] = {OCN_SSH, OCN_SSHP, OCN_UBRTR, OCN_UBRTRP, OCN_VBRTR, OCN_VBRTRP};
-static void state_group(const LBlock &b, int g, void *out[2])
-{
-    const int id = kStateIds[g];
-    out[0] = b.ptr[field_slot(id)];
-    switch (id) {
-    case OCN_SSH: out[1] = b.ptr[field_slot(OCN_SSHN)]; break;
-    case OCN_UBRTR: out[1] = b.ptr[field_slot(OCN_UBRTRN)]; break;
-    case OCN_VBRTR: out[1] = b.ptr[field_slot(OCN_VBRTRN)]; break;
-    case OCN_SSHP: out[1] = b.sshp_alt; break;
-    case OCN_UBRTRP: out[1] = b.up_alt; break;
-    default: out[1] = b.vp_alt; break;
-    }
-}
-
-// one_step_x2's per-block storage: the ext metric rows, the row table with them, the h_r copy, the
-// save area of the state's second halo ring and the runs that save / restore it (pointers of the
-// physical buffers: role independent)
-static int allocate_x2(ocn_ctx *c, LBlock &b)
-{
-    const int w = b.g.bnd_x2 - b.g.bnd_x1 + 1, h = b.g.bnd_y2 - b.g.bnd_y1 + 1;
-    const size_t nrow = row_table_size((unsigned)h);
-    HIPCHK(hipMalloc(&b.ext, kExtRowFloats * sizeof(float)));
-    c->allocs.push_back(b.ext);
-    HIPCHK(hipMalloc(&b.rows_x, nrow * sizeof(float)));
-    c->allocs.push_back(b.rows_x);
-    {   // based like the real(8) fields (kXRing more rows each side): x4 pairs of the h_r-read variant
-        // read it 4 rings deep
-        char *d = nullptr;
-        const size_t nb = sizeof(double) * (size_t)(b.g.pitch * (h + 2 * kXRing)) + 512;
-        HIPCHK(hipMalloc(&d, nb));
-        c->allocs.push_back(d);
-        HIPCHK(hipMemsetAsync(d, 0, nb, c->stream));   // (rings no exchange fills: +0.0)
-        b.hr_x = (double *)(d + 256) + (long)kXRing * b.g.pitch;
-    }
-    const long per = 2L * w + 2L * (h - 2);   // rows bnd_y1, bnd_y2; columns bnd_x1, bnd_x2 between them
-    // the state's six groups, then two per tracer (ff1 / ff1n, ff1p / its second buffer: x4 pairs
-    // exchange the tracers 2 deep)
-    const int ntr = c->sw.use_tracers > 0 ? c->sw.tracer_num : 0, ngroups = 6 + 2 * ntr;
-    HIPCHK(hipMalloc(&b.ring2, sizeof(double) * (size_t)(ngroups * per)));
-    c->allocs.push_back(b.ring2);
-    HIPCHK(hipMalloc(&b.bits_x4, (size_t)b.g.pitch * (h + 2 * kXRing)));
-    c->allocs.push_back(b.bits_x4);
-    HIPCHK(hipMalloc(&b.rows_x4, row_table_size((unsigned)(h + 2 * kXRing)) * sizeof(float)));
-    c->allocs.push_back(b.rows_x4);
-    if (ntr) {
-        const long xr = (long)kXRing * b.g.pitch;
-        for (double *&q : b.trs) {
-            char *d = nullptr;
-            HIPCHK(hipMalloc(&d, sizeof(double) * (size_t)(b.g.pitch * (h + 2 * kXRing)) + 512));
-            c->allocs.push_back(d);
-            q = (double *)(d + 256) + xr;
-        }
-    }
-    std::vector<Seg> save, restore;
-    const long p = (long)b.g.pitch;
-    for (int g = 0; g < ngroups; ++g) {
-        void *buf[2];
-        if (g < 6) {
-            state_group(b, g, buf);
-        } else {
-            const int t = 1 + (g - 6) / 2;
-            buf[0] = b.ptr[field_slot((g - 6) % 2 ? OCN_FF1P(t) : OCN_FF1(t))];
-            buf[1] = (g - 6) % 2 ? b.ffp_alt[(size_t)t - 1] : b.ptr[field_slot(OCN_FF1N(t))];
-        }
-        double *area = b.ring2 + g * per;
-        // (offset in the array, stride, count, offset in the area)
-        const long runs[4][4] = {{0, 1, w, 0}, {(long)(h - 1) * p, 1, w, w}, {p, p, h - 2, 2L * w},
-                                 {p + w - 1, p, h - 2, 2L * w + h - 2}};
-        for (const auto &r : runs) {
-            if (r[2] <= 0) continue;
-            save.push_back(Seg{(const double *)buf[0] + r[0], area + r[3], r[1], 1, (int)r[2]});
-            for (void *q : buf) restore.push_back(Seg{area + r[3], (double *)q + r[0], 1, r[1], (int)r[2]});
-        }
-    }
-    RC(make_seglist(c, save, b.save));
-    RC(make_seglist(c, restore, b.restore));
-    return OCN_OK;
-}
-
-static int allocate(ocn_ctx *c)
-{
-    for (LBlock &b : c->blocks) {
-        const long rows = b.g.bnd_y2 - b.g.bnd_y1 + 1;
-        const long n = (long)b.g.pitch * rows;
-        // every field padded to a 256-B multiple, based so that A(nx_start, :) rows are
-        // 256-B aligned: base offset shifted by (nx_start - bnd_x1) = 2 elements.
-        // OCN_FIELD_SKEW (bytes, multiple of 256): extra gap between consecutive fields.
-        // real(8) fields: kXRing more rows above and below the array (one_step_x4's extra rings)
-        const long xr = (long)kXRing * b.g.pitch * 8;
-        const long r8b = ((n * 8 + 16 + 255) / 256) * 256 + 256 + OCN_FIELD_SKEW + 2 * xr;
-        const long r4b = ((n * 4 + 8 + 255) / 256) * 256 + 256 + OCN_FIELD_SKEW;
-        const int nr8 = num_r8(c), ntr = c->sw.use_tracers > 0 ? c->sw.tracer_num : 0;
-        // + the three second buffers of the role-flip / one-pass steps, one per tracer (ff1p)
-        const size_t total = (size_t)(nr8 + 3 + ntr) * r8b + (size_t)OCN_NUM_R4 * r4b + 256;
-        HIPCHK(hipMalloc(&b.slab, total));
-        c->allocs.push_back(b.slab);
-        HIPCHK(hipMemsetAsync(b.slab, 0, total, c->stream));
-        char *base = (char *)b.slab;
-        size_t off = 0;
-        b.ptr.assign((size_t)(OCN_NUM_R4 + nr8), nullptr);
-        // r8 order in the slab: the one-pass step's state fields and their second buffers first,
-        // next to each other (the arrays one march streams through share DRAM pages and TLB
-        // entries), then the other SW fields, then the tracers'.  (Kernels address every field
-        // through its own pointer; only byte offsets within one field are 32-bit.)
-        std::vector<int> order = {OCN_SSH, OCN_SSHN, OCN_SSHP, OCN_UBRTR, OCN_UBRTRN, OCN_UBRTRP, OCN_VBRTR,
-                                  OCN_VBRTRN, OCN_VBRTRP, -1, -2, -3, OCN_HHU, OCN_HHU_P, OCN_HHV, OCN_HHV_P, OCN_HHH,
-                                  OCN_HHQ_REST, OCN_VORT, OCN_STR_T, OCN_STR_S, OCN_MU, OCN_RHSX, OCN_RHSY};
-        for (int id = OCN_SSH; id < OCN_SSH + nr8; ++id)
-            if (std::find(order.begin(), order.end(), id) == order.end()) order.push_back(id);
-        for (int k = 1; k <= ntr; ++k) order.push_back(-3 - k);
-        b.ffp_alt.assign((size_t)ntr, nullptr);
-        for (int id : order) {
-            char *p = base + off + 256 - 16 + xr;
-            off += r8b;
-            if (id == -1) b.sshp_alt = p;
-            else if (id == -2) b.up_alt = p;
-            else if (id == -3) b.vp_alt = p;
-            else if (id < -3) b.ffp_alt[(size_t)(-4 - id)] = p;
-            else b.ptr[field_slot(id)] = p;
-        }
-        for (int id = 0; id < OCN_NUM_R4; ++id) {
-            b.ptr[field_slot(id)] = base + off + 256 - 8;
-            off += r4b;
-        }
-    }
-    for (LBlock &b : c->blocks) {
-        const size_t n = (size_t)b.g.pitch * (b.g.bnd_y2 - b.g.bnd_y1 + 1);
-        // metric row tables + ratios + reciprocals (sw_stencils.h kRowTable, recip_offset)
-        const size_t nrow = row_table_size((unsigned)(b.g.bnd_y2 - b.g.bnd_y1 + 1));
-        HIPCHK(hipMalloc(&b.bits, n));
-        c->allocs.push_back(b.bits);
-        HIPCHK(hipMalloc(&b.rows, nrow * sizeof(float)));
-        c->allocs.push_back(b.rows);
-        RC(allocate_x2(c, b));
-    }
-    // d_nbad words: 0 check_ssh_err's count, 16 the fallback check's verdict (d_fbz), 32..47 flags and
-    // the vote (d_flags), 48..55 the loopback vote's reduction, 56 the count's maximum over the ranks
-    // (sync_impl), 61 the multi-step launch's barrier timeout flag; then per block h_r, mu (LBlock::kc)
-    const size_t kcb = 16 * c->blocks.size();
-    HIPCHK(hipMalloc(&c->d_nbad, 256 + kcb));
-    c->allocs.push_back(c->d_nbad);
-    HIPCHK(hipMalloc(&c->d_bar, kMultiBarBytes));
-    c->allocs.push_back(c->d_bar);
-    HIPCHK(hipMemsetAsync(c->d_nbad, 0, 256 + kcb, c->stream));
-    c->d_fbz = c->d_nbad + 16;
-    c->d_flags = c->d_nbad + 32;
-    for (size_t i = 0; i < c->blocks.size(); ++i) c->blocks[i].kc = (double *)((char *)c->d_nbad + 256) + 2 * i;
-    return OCN_OK;
-}
-
-// ------------------------------------------------------------------ halo plans
-// syncborder_block2D_gen_all.fi: halo of block k in dir d <- boundary of neighbour in inverse(d).
-// Messages between two processes carry, for every (sending block, dir) pair in global block
-// order and every field of the sync group, the boundary strip in column-major order.
-// Host-only schedule of one halo exchange (no device pointers): every entry copies the
-// 1-wide strip `src` of local block ks (local copy or send) into the strip `dst` of local block
-// k (local copy or receive).  Message layout between two processes: for every (receiving
-// block, dir) in global block order, every field of the group, the sender's boundary strip in
-// column-major order -- enumerated identically on both sides from global knowledge.
-struct PlanEntry {
-    int kind;          // OCN_HALO_LOCAL / OCN_HALO_SEND / OCN_HALO_RECV
-    int peer;          // rank (send/recv), own rank for local
-    int k, ks;         // destination / source local block (-1 where not applicable)
-    int field;
-    Rect dst, src;
-    long buf_off;      // element offset in the peer's message (send/recv)
-    int count;
-};
-
-// Layer j (1 .. depth) of the halo of block `rcv` in direction d and the boundary of its
-// neighbour `src` it receives: layer 1 is the reference's 1-wide exchange (syncborder_block2D_gen_all.fi);
-// layer 2 (depth 2, the one-pass steps' state exchange, one_step_x2) the next row / column out
-// (and depth x depth corner patches).  Corner layers are rows of `depth` points.
-static void halo_layer(const ocn_block &rcv, const ocn_block &src, int d, int j, int depth, Rect &hr, Rect &br)
-{
-    const int dm = kDirDm[d], dn = kDirDn[d];
-    // x: halo columns / source columns of this direction
-    int hx0, hx1, sx0, sx1;
-    if (dm > 0) { hx0 = rcv.nx_end + 1; hx1 = rcv.nx_end + (dn ? depth : 1); sx0 = src.nx_start; sx1 = sx0 + (hx1 - hx0); }
-    else if (dm < 0) { hx1 = rcv.nx_start - 1; hx0 = rcv.nx_start - (dn ? depth : 1); sx1 = src.nx_end; sx0 = sx1 - (hx1 - hx0); }
-    else { hx0 = rcv.nx_start; hx1 = rcv.nx_end; sx0 = src.nx_start; sx1 = src.nx_end; }
-    if (dm && !dn) {   // E / W edge: layer j is one column
-        hx0 = hx1 = dm > 0 ? rcv.nx_end + j : rcv.nx_start - j;
-        sx0 = sx1 = dm > 0 ? src.nx_start + j - 1 : src.nx_end - j + 1;
-    }
-    int hy, sy;
-    if (dn > 0) { hy = rcv.ny_end + j; sy = src.ny_start + j - 1; }
-    else if (dn < 0) { hy = rcv.ny_start - j; sy = src.ny_end - j + 1; }
-    else { hy = -1; sy = -1; }
-    if (dn) { hr = {hx0, hx1, hy, hy}; br = {sx0, sx1, sy, sy}; }
-    else { hr = {hx0, hx1, rcv.ny_start, rcv.ny_end}; br = {sx0, sx1, src.ny_start, src.ny_end}; }
-}
-
-// a tracer field (ff1 / ff1p / ff1n of some tracer)
-static bool is_tracer_field(int id) { return id >= OCN_TRACER_BASE; }
-// Depth of field id in an exchange of `depth`: the tracer fields are exchanged one point deep in
-// every exchange (one_step_x2 sends them with the state's two-deep strips: one message per peer)
-// tracers: 1 deep, 2 with the x4 pairs' 4-deep state (one_step_x4's first tracer step covers the halo
-// ring neighbours own)
-static int field_depth(int id, int depth) { return is_tracer_field(id) ? (depth >= 4 ? 2 : 1) : depth; }
-
-static int plan_entries(const ocn_ctx *c, const std::vector<int> &fields, std::vector<PlanEntry> &out,
-                        int depth = 1)
-{
-    out.clear();
-    std::map<int, int> k_of_gid;
-    for (size_t k = 0; k < c->blocks.size(); ++k) k_of_gid[c->blocks[k].gid] = (int)k;
-    std::map<int, long> send_count, recv_count;
-    // receiving side: my halos in gid order, dirs 1..8, layers 1..depth
-    for (auto &kv : k_of_gid) {
-        const int k = kv.second;
-        const LBlock &b = c->blocks[k];
-        for (int d = 1; d <= 8; ++d) {
-            const int r = b.nbr_rank[d - 1];
-            if (r < 0) continue;
-            const GBlock &src = c->gblocks[b.nbr_gid[d - 1]];
-            for (int j = 1; j <= depth; ++j) {
-                for (int id : fields) {
-                    const int fd = field_depth(id, depth);
-                    if (j > fd) continue;
-                    Rect hr, br;
-                    halo_layer(b.g, src.g, d, j, fd, hr, br);
-                    const int cnt = (hr.x1 - hr.x0 + 1) * (hr.y1 - hr.y0 + 1);
-                    if (r == c->dec.rank)
-                        out.push_back(PlanEntry{OCN_HALO_LOCAL, r, k, k_of_gid.at(b.nbr_gid[d - 1]), id, hr, br, 0, cnt});
-                    else {
-                        out.push_back(PlanEntry{OCN_HALO_RECV, r, k, -1, id, hr, br, recv_count[r], cnt});
-                        recv_count[r] += cnt;
-                    }
-                }
-            }
-        }
-    }
-    // sending side: remote receivers in gid order, dirs 1..8, layers 1..depth, whose source block is mine
-    for (size_t gid = 0; gid < c->gblocks.size(); ++gid) {
-        const GBlock &rb = c->gblocks[gid];
-        if (rb.rank < 0 || rb.rank == c->dec.rank) continue;
-        for (int d = 1; d <= 8; ++d) {
-            const int m = rb.bm + kDirDm[d], n = rb.bn + kDirDn[d];
-            if (m < 1 || m > c->bnx || n < 1 || n > c->bny) continue;
-            const int sg = (m - 1) + (n - 1) * c->bnx;
-            if (c->gblocks[sg].rank != c->dec.rank) continue;
-            const int ks = k_of_gid.at(sg);
-            for (int j = 1; j <= depth; ++j) {
-                for (int id : fields) {
-                    const int fd = field_depth(id, depth);
-                    if (j > fd) continue;
-                    Rect hr, br;
-                    halo_layer(rb.g, c->blocks[ks].g, d, j, fd, hr, br);
-                    const int cnt = (br.x1 - br.x0 + 1) * (br.y1 - br.y0 + 1);
-                    out.push_back(PlanEntry{OCN_HALO_SEND, rb.rank, -1, ks, id, hr, br, send_count[rb.rank], cnt});
-                    send_count[rb.rank] += cnt;
-                }
-            }
-        }
-    }
-    for (auto &kv : recv_count)
-        if (send_count[kv.first] != kv.second) return set_error(OCN_ERR_STATE, "halo plan: asymmetric message sizes");
-    for (auto &kv : send_count)
-        if (recv_count[kv.first] != kv.second) return set_error(OCN_ERR_STATE, "halo plan: asymmetric message sizes");
-    return OCN_OK;
-}
-
-// Column strips (a side with a stride) of the same length whose runs are adjacent columns on a strided
-// side (step +1 or -1), the other side's runs equally spaced -- as the layers of one field's E / W strip
-// are: one segment of w runs (up to kSegMaxW) instead of w, copying the same elements.
-constexpr int kSegMaxW = 8;
-static std::vector<Seg> merge_columns(const std::vector<Seg> &in)
-{
-    std::vector<Seg> out;
-    std::vector<char> used(in.size(), 0);
-    std::map<const double *, size_t> by_src, by_dst;   // the column strips by their strided side
-    for (size_t i = 0; i < in.size(); ++i) {
-        if (in[i].w != 1) continue;
-        if (in[i].src_stride > 1) by_src[in[i].src] = i;
-        else if (in[i].dst_stride > 1) by_dst[in[i].dst] = i;
-    }
-    for (size_t i = 0; i < in.size(); ++i) {
-        if (used[i]) continue;
-        used[i] = 1;
-        Seg g = in[i];
-        const bool sc = g.src_stride > 1, dc = !sc && g.dst_stride > 1;
-        if (g.w == 1 && (sc || dc)) {
-            for (const long step : {1L, -1L}) {
-                if (g.w > 1) break;
-                while (g.w < kSegMaxW) {
-                    auto &idx = sc ? by_src : by_dst;
-                    auto it = idx.find((sc ? (const double *)g.src : (const double *)g.dst) + (long)g.w * step);
-                    if (it == idx.end() || used[it->second]) break;
-                    const Seg &b = in[it->second];
-                    if (b.count != g.count || b.src_stride != g.src_stride || b.dst_stride != g.dst_stride) break;
-                    // the other side's spacing: set by the second run, kept by the rest
-                    const long other = sc ? (long)(b.dst - g.dst) : (long)(b.src - g.src);
-                    if (g.w == 1) {
-                        if (sc) { g.src_jstride = step; g.dst_jstride = other; }
-                        else { g.dst_jstride = step; g.src_jstride = other; }
-                    } else if (other != (long)g.w * (sc ? g.dst_jstride : g.src_jstride)) {
-                        break;
-                    }
-                    used[it->second] = 1;
-                    ++g.w;
-                }
-            }
-        }
-        out.push_back(g);
-    }
-    return out;
-}
-
-static int build_plan(ocn_ctx *c, const std::vector<int> &fields, HaloPlan &plan, int depth = 1)
-{
-    std::vector<PlanEntry> entries;
-    RC(plan_entries(c, fields, entries, depth));
-    std::map<int, long> msg;                       // peer -> message length
-    for (const PlanEntry &e : entries)
-        if (e.kind == OCN_HALO_RECV) msg[e.peer] = std::max(msg[e.peer], e.buf_off + e.count);
-    std::map<int, HaloPlan::Peer> peers;
-    for (auto &kv : msg) {
-        HaloPlan::Peer p{kv.first, kv.second, nullptr, nullptr};
-        HIPCHK(hipMalloc(&p.send, sizeof(double) * std::max(1L, p.count)));
-        HIPCHK(hipMalloc(&p.recv, sizeof(double) * std::max(1L, p.count)));
-        c->allocs.push_back(p.send); c->allocs.push_back(p.recv);
-        peers[kv.first] = p;
-        plan.peers.push_back(p);
-    }
-    std::vector<Seg> local, pack, unpack;
-    for (const PlanEntry &e : entries) {
-        long doff, soff, dstr, sstr; int dcnt, scnt;
-        if (e.kind == OCN_HALO_LOCAL) {
-            const LBlock &db = c->blocks[e.k], &sb = c->blocks[e.ks];
-            strip(db.g, e.dst, doff, dcnt, dstr);
-            strip(sb.g, e.src, soff, scnt, sstr);
-            local.push_back(Seg{sb.f<double>(e.field) + soff, db.f<double>(e.field) + doff, sstr, dstr, dcnt});
-        } else if (e.kind == OCN_HALO_RECV) {
-            const LBlock &db = c->blocks[e.k];
-            strip(db.g, e.dst, doff, dcnt, dstr);
-            unpack.push_back(Seg{peers.at(e.peer).recv + e.buf_off, db.f<double>(e.field) + doff, 1, dstr, dcnt});
-        } else {
-            const LBlock &sb = c->blocks[e.ks];
-            strip(sb.g, e.src, soff, scnt, sstr);
-            pack.push_back(Seg{sb.f<double>(e.field) + soff, peers.at(e.peer).send + e.buf_off, sstr, 1, scnt});
-        }
-    }
-    RC(make_seglist(c, merge_columns(local), plan.local));
-    RC(make_seglist(c, merge_columns(pack), plan.pack));
-    RC(make_seglist(c, merge_columns(unpack), plan.unpack));
-    return OCN_OK;
-}
-
-// Plans hold raw field pointers, so a plan is kept per role of the buffers its fields swap
-// between (the key is the field list followed by -1 - the relevant role bits).
-static bool is_alt_field(int id);
-// depth 2: the one-pass steps' 2-deep state exchange (halo_layer); priv: a plan over a private
-// buffer swapped into the field table while it is built and run (one_step_x2's h_r copy)
-static int get_plan(ocn_ctx *c, const std::vector<int> &fields, HaloPlan *&out, int depth = 1, int priv = 0)
-{
-    std::vector<int> key = fields;
-    // a plan holds the buffers its fields had when it was built: the pair roles (bit 1), and for
-    // sshp / ubrtrp / vbrtrp the second buffers' roles (bit 4: they persist between one-pass calls)
-    const bool alt = std::any_of(fields.begin(), fields.end(), [](int id) { return is_alt_field(id); });
-    // (tracer fields: the tracer steps' role bits 8 -- ff1 / ff1n -- and 16 -- ff1p's second buffer)
-    const bool tr = std::any_of(fields.begin(), fields.end(), [](int id) { return is_tracer_field(id); });
-    key.push_back(-1 - (c->role & 1) - (alt ? (c->role & 4) : 0) - (tr ? (c->role & 24) : 0));
-    if (depth != 1 || priv) key.push_back(-100 - depth - 10 * priv);
-    auto it = c->plans.find(key);
-    if (it == c->plans.end()) {
-        if (c->capturing) return set_error(OCN_ERR_STATE, "halo plan built while a step is captured");
-        HaloPlan p;
-        RC(build_plan(c, fields, p, depth));
-        it = c->plans.emplace(key, p).first;
-    }
-    out = &it->second;
-    return OCN_OK;
-}
-
-static int nccl_rc(ncclResult_t r, const char *what)
-{
-    if (r == ncclSuccess) return OCN_OK;
-    return set_error(OCN_ERR_COMM, std::string(what) + ": " + ncclGetErrorString(r));
-}
-
-static bool has_comm(const ocn_ctx *c) { return c->comm || c->lb || c->comm_aborted; }
-static int comm_gone(const ocn_ctx *c)
-{
-    return set_error(OCN_ERR_COMM, "the RCCL communicator was aborted after an earlier fatal error");
-}
 // OCN_OPT_OVERLAP in effect: by default (-1) the role-flip steps' exchanges overlap their inner
 // launches (2) when exchanges go to other ranks (RCCL: latency, not copy bandwidth), and run
 // between the launches (1) when every exchange is a local device copy -- there the frame bands
@@ -1054,353 +89,6 @@ static int ov_mark(ocn_ctx *c, int probe, bool end)
     return OCN_OK;
 }
 
-// a rank of a loopback group that fails releases its peers' waits at once
-static int lb_fail_on_error(ocn_ctx *c, int rc)
-{
-    if (rc && c->lb) {
-        std::lock_guard<std::mutex> g(c->lb->mu);
-        c->lb->failed = true;
-        c->lb->cv.notify_all();
-    }
-    return rc;
-}
-
-// An error inside a call that takes part in collectives (step, init_state, synchronize): the
-// loopback group's waits are released (lb_fail_on_error), and a fatal one (HIP, RCCL, state) aborts
-// the RCCL communicator -- its queued sends / receives are cancelled and nothing of this rank waits
-// on a peer that will not come; the host then ends the job, as abort_model's mpi_abort does
-// (shared/errors.f90:30-37).  OCN_ERR_BLOWUP is not fatal here: every rank returns it from the same
-// synchronize (sync_impl reduces the counts), and OCN_ERR_ARG is raised before any collective.
-static int fail_fatal(ocn_ctx *c, int rc)
-{
-    rc = lb_fail_on_error(c, rc);
-    if ((rc && rc != OCN_ERR_BLOWUP && rc != OCN_ERR_ARG) || c->wd_fired.load()) {
-        std::lock_guard<std::mutex> g(c->comm_mu);
-        if (c->comm) {
-            if (!c->comm_abort_done) (void)ncclCommAbort(c->comm);   // (the watchdog may have)
-            c->comm_abort_done = true;
-            c->comm = nullptr;
-            c->comm_aborted = true;
-        }
-    }
-    return rc;
-}
-
-// ------------------------------------------------------------------ host-side watchdog
-// ocn_ctx_set_watchdog: a thread per context watches the entries that may take part in a collective
-// (guarded below).  One that has not returned after wd_s is ended: the message names the call and the
-// last exchange with remote peers the device completed (polled from c->xq), the RCCL communicator is
-// aborted (RCCL's kernels waiting on a peer exit, so the call's stream wait returns) or the loopback
-// group failed (its rendezvous return), and the call returns OCN_ERR_COMM with the message.  A call
-// still stuck 10 s later ends the process (exit status 3).
-static int64_t poll_xdone(ocn_ctx *c)
-{
-    std::lock_guard<std::mutex> g(c->xmu);
-    while (!c->xq.empty() && hipEventQuery(c->xq.front().second) == hipSuccess) {
-        c->xdone = c->xq.front().first;
-        c->xpool.push_back(c->xq.front().second);
-        c->xq.pop_front();
-    }
-    return c->xdone;
-}
-
-static void wd_fire(ocn_ctx *c, const char *call, double waited)
-{
-    const int64_t done = poll_xdone(c);
-    char buf[512];
-    std::snprintf(buf, sizeof buf,
-                  "ocn watchdog: rank %d of %d: %s has not returned after %.1f s (limit %.1f s); last completed "
-                  "exchange id %lld of %lld enqueued; %s",
-                  c->dec.rank, c->dec.nranks, call, waited, c->wd_s, (long long)done, (long long)c->xchg,
-                  c->lb ? "failing the loopback group" : c->comm ? "aborting the RCCL communicator" : "no communicator");
-    c->wd_msg = buf;
-    c->wd_fired.store(true);
-    std::fprintf(stderr, "%s\n", buf);
-    std::fflush(stderr);
-    if (c->lb) {
-        std::lock_guard<std::mutex> g(c->lb->mu);
-        c->lb->failed = true;
-        c->lb->cv.notify_all();
-    }
-    std::lock_guard<std::mutex> g(c->comm_mu);
-    if (c->comm && !c->comm_abort_done) {
-        (void)ncclCommAbort(c->comm);
-        c->comm_abort_done = true;
-    }
-}
-
-static void wd_loop(ocn_ctx *c)
-{
-    (void)hipSetDevice(c->dec.device);
-    std::unique_lock<std::mutex> g(c->wd_mu);
-    while (!c->wd_stop) {
-        c->wd_cv.wait_for(g, std::chrono::milliseconds(100));
-        if (c->wd_stop || c->call_depth == 0 || c->wd_fired.load() || c->wd_s <= 0) continue;
-        const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - c->call_t0).count();
-        if (waited < c->wd_s) continue;
-        const char *call = c->call_name;
-        g.unlock();
-        wd_fire(c, call, waited);
-        g.lock();
-        if (!c->wd_cv.wait_for(g, std::chrono::seconds(10), [c] { return c->wd_stop || c->call_depth == 0; })) {
-            std::fprintf(stderr, "ocn watchdog: rank %d: %s still blocked 10 s after the abort; exiting (status 3)\n",
-                         c->dec.rank, call);
-            std::fflush(stderr);
-            std::_Exit(3);
-        }
-    }
-}
-
-// An entry that may take part in a collective, watched while a watchdog is set
-struct CallGuard {
-    ocn_ctx *c;
-    CallGuard(ocn_ctx *ctx, const char *name) : c(ctx)
-    {
-        std::lock_guard<std::mutex> g(c->wd_mu);
-        if (c->call_depth++ == 0) {
-            c->call_t0 = std::chrono::steady_clock::now();
-            c->call_name = name;
-        }
-    }
-    ~CallGuard()
-    {
-        std::lock_guard<std::mutex> g(c->wd_mu);
-        --c->call_depth;
-        c->wd_cv.notify_all();
-    }
-};
-template <class F> static int guarded(ocn_ctx *c, const char *name, F &&f)
-{
-    if (c->wd_fired.load()) return set_error(OCN_ERR_COMM, c->wd_msg);
-    int rc;
-    {
-        CallGuard g(c, name);
-        rc = f();
-    }
-    if (c->wd_fired.load()) {   // (the call returned because the watchdog ended it)
-        std::lock_guard<std::mutex> g(c->comm_mu);
-        if (c->comm) { c->comm = nullptr; c->comm_aborted = true; }
-        return set_error(OCN_ERR_COMM, c->wd_msg);
-    }
-    return rc;
-}
-
-// One loopback rendezvous: this rank passes phase `ph`, then waits until every rank in `peers`
-// has passed it as often (bounded wait: a rank that failed or never comes ends it with an error).
-static int lb_meet(ocn_ctx *c, int ph, const std::vector<int> &peers)
-{
-    Loopback &L = *c->lb;
-    const int r = c->dec.rank;
-    std::unique_lock<std::mutex> g(L.mu);
-    const uint64_t mine = ++L.cnt[ph][r];
-    L.cv.notify_all();
-    bool lost = false;   // a peer still needed failed or was destroyed
-    const bool ok = L.cv.wait_for(g, std::chrono::seconds(120), [&] {
-        bool all = true;
-        for (int p : peers)
-            if (L.cnt[ph][p] < mine) {
-                all = false;
-                lost = lost || L.failed || !L.ctx[p];
-            }
-        return all || lost;
-    });
-    if (!ok || lost) {
-        L.failed = true;
-        L.cv.notify_all();
-        return set_error(OCN_ERR_COMM, "loopback transport: a peer rank did not reach the exchange");
-    }
-    return OCN_OK;
-}
-
-// The ncclRecv / ncclSend pairs of one exchange over the loopback transport (see Loopback).
-static int lb_exchange(ocn_ctx *c, const HaloPlan *p, hipStream_t stream)
-{
-    Loopback &L = *c->lb;
-    const int r = c->dec.rank;
-    std::vector<int> peers;
-    for (const auto &q : p->peers) peers.push_back(q.rank);
-    HIPCHK(hipEventRecord(c->lb_ev_a, stream));
-    {
-        std::lock_guard<std::mutex> g(L.mu);
-        L.plan[r] = p;
-    }
-    RC(lb_meet(c, 0, peers));
-    for (const auto &q : p->peers) {
-        const HaloPlan *pp;
-        hipEvent_t ev;
-        {   // a peer destroyed after the rendezvous has left its slot empty: fail, do not dereference
-            std::lock_guard<std::mutex> g(L.mu);
-            if (!L.ctx[q.rank]) return set_error(OCN_ERR_COMM, "loopback transport: a peer rank was destroyed");
-            pp = L.plan[q.rank];
-            ev = L.ctx[q.rank]->lb_ev_a;
-        }
-        const HaloPlan::Peer *src = nullptr;
-        for (const auto &e : pp->peers)
-            if (e.rank == r) src = &e;
-        if (!src || src->count != q.count) return set_error(OCN_ERR_STATE, "loopback transport: message sizes disagree");
-        HIPCHK(hipStreamWaitEvent(stream, ev, 0));
-        HIPCHK(hipMemcpyAsync(q.recv, src->send, sizeof(double) * (size_t)q.count, hipMemcpyDeviceToDevice, stream));
-    }
-    HIPCHK(hipEventRecord(c->lb_ev_b, stream));
-    RC(lb_meet(c, 1, peers));
-    std::vector<hipEvent_t> evs;
-    {
-        std::lock_guard<std::mutex> g(L.mu);
-        for (const auto &q : p->peers) {
-            if (!L.ctx[q.rank]) return set_error(OCN_ERR_COMM, "loopback transport: a peer rank was destroyed");
-            evs.push_back(L.ctx[q.rank]->lb_ev_b);
-        }
-    }
-    for (hipEvent_t e : evs) HIPCHK(hipStreamWaitEvent(stream, e, 0));
-    return OCN_OK;
-}
-
-// max over the ranks of one device int32 (the role-flip vote): ncclAllReduce, or over the
-// loopback transport every rank reads every rank's word (after its lb_ev_a) into d_red and copies
-// it back after all ranks have read (lb_ev_b).
-struct VotePtrs { const int32_t *p[64]; int n, words; };
-__global__ void k_vote_max(VotePtrs v, int32_t *out)
-{
-    const int w = (int)threadIdx.x;
-    if (w >= v.words) return;
-    int32_t m = v.p[0][w];
-    for (int i = 1; i < v.n; ++i) m = max(m, v.p[i][w]);
-    out[w] = m;
-}
-constexpr int kVoteWords = 8;   // the role-flip vote (check_coherence): one 0/1 word per condition
-static int allreduce_max(ocn_ctx *c, int32_t *word, hipStream_t s, int words = 1)
-{
-    if (c->comm_aborted) return comm_gone(c);
-    if (c->wd_fired.load()) return set_error(OCN_ERR_COMM, c->wd_msg);
-    if (c->comm)
-        return nccl_rc(ncclAllReduce(word, word, (size_t)words, ncclInt32, ncclMax, c->comm, s), "ncclAllReduce");
-    if (!c->lb) return OCN_OK;
-    Loopback &L = *c->lb;
-    std::vector<int> all(L.n);
-    for (int i = 0; i < L.n; ++i) all[i] = i;
-    HIPCHK(hipEventRecord(c->lb_ev_a, s));
-    {
-        std::lock_guard<std::mutex> g(L.mu);
-        L.vote[c->dec.rank] = word;
-    }
-    RC(lb_meet(c, 2, all));
-    VotePtrs v{};
-    v.n = L.n;
-    v.words = words;
-    std::vector<hipEvent_t> evs;
-    {   // snapshot under the lock: a peer destroyed after the rendezvous fails the vote
-        std::lock_guard<std::mutex> g(L.mu);
-        for (int i = 0; i < L.n; ++i) {
-            if (!L.ctx[i]) return set_error(OCN_ERR_COMM, "loopback transport: a peer rank was destroyed");
-            v.p[i] = L.vote[i];
-            evs.push_back(L.ctx[i]->lb_ev_a);
-        }
-    }
-    for (hipEvent_t e : evs) HIPCHK(hipStreamWaitEvent(s, e, 0));
-    int32_t *red = c->d_nbad + 48;
-    hipLaunchKernelGGL(k_vote_max, dim3(1), dim3(64), 0, s, v, red);
-    RC(check_launch());
-    HIPCHK(hipEventRecord(c->lb_ev_b, s));
-    RC(lb_meet(c, 3, all));
-    evs.clear();
-    {
-        std::lock_guard<std::mutex> g(L.mu);
-        for (int i = 0; i < L.n; ++i) {
-            if (!L.ctx[i]) return set_error(OCN_ERR_COMM, "loopback transport: a peer rank was destroyed");
-            evs.push_back(L.ctx[i]->lb_ev_b);
-        }
-    }
-    for (hipEvent_t e : evs) HIPCHK(hipStreamWaitEvent(s, e, 0));
-    HIPCHK(hipMemcpyAsync(word, red, sizeof(int32_t) * (size_t)words, hipMemcpyDeviceToDevice, s));
-    return OCN_OK;
-}
-
-static int get_event(ocn_ctx *c, hipEvent_t &e);
-
-// The end of an exchange with remote peers on `stream`: its timer record, and while a watchdog is set
-// an event the watchdog polls for the last completed exchange (c->xq; completed events are recycled)
-static int exchange_done(ocn_ctx *c, ocn_ctx::Rec &xrec, hipStream_t stream)
-{
-    if (c->capturing) return OCN_OK;
-    if (xrec.b) {
-        HIPCHK(hipEventRecord(xrec.b, stream));
-        c->recs.push_back(xrec);
-    }
-    if (c->wd_s <= 0) return OCN_OK;
-    std::lock_guard<std::mutex> g(c->xmu);
-    while (!c->xq.empty() && (c->xq.size() > 256 || hipEventQuery(c->xq.front().second) == hipSuccess)) {
-        if (hipEventQuery(c->xq.front().second) == hipSuccess) c->xdone = c->xq.front().first;
-        else HIPCHK(hipEventSynchronize(c->xq.front().second));   // (256 in flight: the oldest has to finish)
-        c->xpool.push_back(c->xq.front().second);
-        c->xq.pop_front();
-    }
-    hipEvent_t e;
-    if (!c->xpool.empty()) { e = c->xpool.back(); c->xpool.pop_back(); }
-    else HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence));
-    HIPCHK(hipEventRecord(e, stream));
-    c->xq.emplace_back(c->xchg, e);
-    return OCN_OK;
-}
-
-// cmp != nullptr: compare the halos with what the exchange would deliver instead of writing them
-// (ORs 1 into *cmp where they differ); same messages, so every rank must take part.
-// OCN_OPT_XCHG_DELAY (tests): one wave waits c->xdelay_us on the device clock (a slow link's latency,
-// in front of an exchange with remote peers); the loop always ends
-__global__ void k_delay(unsigned long long ticks)
-{
-    const unsigned long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-}
-static int launch_delay(ocn_ctx *c, hipStream_t s)
-{
-    int khz = 0;
-    HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->dec.device));
-    const unsigned long long ticks = (unsigned long long)c->xdelay_us * (unsigned long long)(khz > 0 ? khz : 100000) / 1000ull;
-    hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, s, ticks);
-    return check_launch();
-}
-
-static int run_sync(ocn_ctx *c, const std::vector<int> &fields, hipStream_t stream = nullptr, int32_t *cmp = nullptr,
-                    int depth = 1, int priv = 0)
-{
-    HaloPlan *p;
-    RC(get_plan(c, fields, p, depth, priv));
-    if (!stream) stream = c->stream;
-    ocn_ctx::Rec xrec{OCN_TIMER_EXCHANGE, nullptr, nullptr};
-    const bool remote = !p->peers.empty();
-    if (remote) {
-        if (!has_comm(c)) return set_error(OCN_ERR_COMM, "remote neighbours but no RCCL communicator attached");
-        if (c->comm_aborted) return comm_gone(c);
-        if (c->wd_fired.load()) return set_error(OCN_ERR_COMM, c->wd_msg);
-        if (c->stage_timing && !c->capturing) {   // the exchange on its stream: pack, group, unpack
-            RC(get_event(c, xrec.a)); RC(get_event(c, xrec.b));
-            HIPCHK(hipEventRecord(xrec.a, stream));
-        }
-        ++c->xchg;
-        if (c->xdelay_us > 0) RC(launch_delay(c, stream));
-        RC(launch_segs(p->pack, stream));
-        if (c->lb) {
-            RC(lb_exchange(c, p, stream));
-        } else {
-            RC(nccl_rc(ncclGroupStart(), "ncclGroupStart"));
-            for (auto &peer : p->peers) {
-                RC(nccl_rc(ncclRecv(peer.recv, (size_t)peer.count, ncclDouble, peer.rank, c->comm, stream), "ncclRecv"));
-                RC(nccl_rc(ncclSend(peer.send, (size_t)peer.count, ncclDouble, peer.rank, c->comm, stream), "ncclSend"));
-            }
-            RC(nccl_rc(ncclGroupEnd(), "ncclGroupEnd"));
-        }
-    }
-    if (cmp) {
-        RC(launch_segs(p->local, stream, cmp));
-        RC(launch_segs(p->unpack, stream, cmp));
-        return remote ? exchange_done(c, xrec, stream) : OCN_OK;
-    }
-    RC(launch_segs(p->local, stream));
-    RC(launch_segs(p->unpack, stream));
-    if (remote) RC(exchange_done(c, xrec, stream));
-    return OCN_OK;
-}
-
 // ------------------------------------------------------------------ stages (envoke)
 // sync lists: interface/shallow_water/sw_interface.f90 envoke_*_sync
 static const std::vector<int> kSyncSsh = {OCN_SSHN};
@@ -1413,32 +101,6 @@ static const std::vector<int> kSyncHhInit = {OCN_HHU, OCN_HHV, OCN_HHH};
 // role-flip steps with halo exchanges: halo values that must equal the neighbours' (ocn_ctx.hip
 // check_coherence)
 static const std::vector<int> kHaloCheck = {OCN_SSH, OCN_UBRTR, OCN_VBRTR, OCN_HHU, OCN_HHV, OCN_HHQ_REST};
-
-// f(b) for every block of the context.  With OCN_OPT_BATCH and several blocks the launches f makes
-// on stream s are batched (ocn_internal.h Batcher): each kernel of the loop is launched once for all
-// the blocks (up to kPack of them per launch) instead of once per block.  Only for loops whose
-// launches read and write their own block's arrays, with nothing but batchable launches on s.
-// co: the loop's launches read nothing another writes -- a march batch and the tracer-step batch
-// after it may go as one launch (Batcher::co_launch; batched for one block too)
-template <class F> static int each_block(ocn_ctx *c, hipStream_t s, F &&f, bool co = false)
-{
-    const bool on = c->batch && (c->blocks.size() > 1 || co);
-    if (on) {
-        batch_begin(&c->batcher, s);
-        c->batcher.co_launch = co;
-    }
-    int rc = OCN_OK;
-    for (size_t i = 0; i < c->blocks.size() && rc == OCN_OK; ++i) {
-        if (on) batch_next(&c->batcher);
-        rc = f(c->blocks[i]);
-    }
-    if (on) {
-        const int r2 = batch_end(&c->batcher);
-        if (rc == OCN_OK) rc = r2;
-        if (co && c->batcher.co_launched) c->co_used = true;
-    }
-    return rc;
-}
 
 static int stage_kernel(ocn_ctx *c, const LBlock &b, int stage, double tau)
 {
@@ -1520,8 +182,6 @@ static const std::vector<int> *stage_sync(int stage)
     }
 }
 
-static void swap_roles(ocn_ctx *c);
-
 // every plan a step can use, built before any graph capture (no hipMalloc while capturing)
 static int prebuild_plans(ocn_ctx *c)
 {
@@ -1577,13 +237,13 @@ static int make_timer_event(hipEvent_t &e)
     HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
     return OCN_OK;
 }
-static int get_event(ocn_ctx *c, hipEvent_t &e)
+int get_event(ocn_ctx *c, hipEvent_t &e)
 {
     if (!c->event_pool.empty()) { e = c->event_pool.back(); c->event_pool.pop_back(); return OCN_OK; }
     return make_timer_event(e);
 }
 
-static int timer_begin(ocn_ctx *c, int id, ocn_ctx::Rec &rec)
+int timer_begin(ocn_ctx *c, int id, ocn_ctx::Rec &rec)
 {
     rec = ocn_ctx::Rec{id, nullptr, nullptr};
     if (!c->stage_timing) return OCN_OK;
@@ -1591,7 +251,7 @@ static int timer_begin(ocn_ctx *c, int id, ocn_ctx::Rec &rec)
     HIPCHK(hipEventRecord(rec.a, c->stream));
     return OCN_OK;
 }
-static int timer_end(ocn_ctx *c, ocn_ctx::Rec &rec)
+int timer_end(ocn_ctx *c, ocn_ctx::Rec &rec)
 {
     if (!c->stage_timing) return OCN_OK;
     HIPCHK(hipEventRecord(rec.b, c->stream));
@@ -1599,7 +259,7 @@ static int timer_end(ocn_ctx *c, ocn_ctx::Rec &rec)
     return OCN_OK;
 }
 
-static int envoke(ocn_ctx *c, int stage, double tau)
+int envoke(ocn_ctx *c, int stage, double tau)
 {
     ocn_ctx::Rec rec;
     RC(timer_begin(c, stage, rec));
@@ -1634,43 +294,6 @@ static int one_step(ocn_ctx *c, double tau, bool check)
     return OCN_OK;
 }
 
-static bool has_exchange(const ocn_ctx *c);
-
-// (Re)builds the compact static fields when the real(4) fields may have changed, and decides
-// whether the fused step reads them (sw_stencils.h "compact static fields").  Synchronises
-// only when a rebuild was needed (once after init / an upload of a real(4) field).
-static int prepare_static(ocn_ctx *c)
-{
-    if (!c->compact_req || c->r4_escaped) { c->compact = false; return OCN_OK; }
-    if (!c->static_dirty) return OCN_OK;
-    HIPCHK(hipMemsetAsync(c->d_flags, 0, 3 * sizeof(int32_t), c->stream));
-    RC(each_block(c, c->stream, [&](const LBlock &b) { return launch_prepare(&b.g, b.ptr.data(), b.bits, b.rows, c->d_flags, c->stream, b.own); }));
-    if (c->ext_ok)   // one_step_x2's row tables: the ext rows' divisor range into the second word
-        for (const LBlock &b : c->blocks) RC(launch_rows_ext(&b.g, b.rows, b.rows_x, b.ext, c->d_flags + 1, c->stream));
-    const bool x4_tabs = c->ext_ok && has_exchange(c);
-    int32_t *d_mask = nullptr;
-    if (x4_tabs) {   // one_step_x4's tables (the neighbours' mask bytes from the basin mask): the third word
-        const size_t nxy = (size_t)c->basin.nx * c->basin.ny;
-        HIPCHK(hipMallocAsync((void **)&d_mask, nxy * sizeof(int32_t), c->stream));
-        HIPCHK(hipMemcpyAsync(d_mask, c->mask.data(), nxy * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        for (const LBlock &b : c->blocks)
-            RC(launch_x4_tables(&b.g, b.bits, b.rows, b.ext, b.bits_x4, b.rows_x4, d_mask, c->basin.nx, c->basin.ny, b.own,
-                                c->d_flags + 2, c->stream));
-        HIPCHK(hipFreeAsync(d_mask, c->stream));
-    }
-    int32_t flags[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(flags, c->d_flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->ring_sea = (flags[0] & kCompactRingSea) != 0;
-    c->edge_ring_sea = (flags[0] & kCompactEdgeRingSea) != 0;
-    c->udiv_ok = (flags[0] & kCompactDivisorRange) == 0;
-    c->rows_x_ok = c->ext_ok && flags[1] == 0;
-    c->x4_tab_ok = x4_tabs && flags[2] == 0;
-    c->compact = (flags[0] & ~(kCompactRingSea | kCompactDivisorRange | kCompactEdgeRingSea)) == 0;
-    c->static_dirty = false;
-    return OCN_OK;
-}
-
 // Fused step (sw_kernels.hip "fused step groups"): 4 launches and 3 halo syncs per step,
 // bitwise the same state as one_step.  last = false skips stores no later kernel reads
 // (sw_stencils.h FusedB / HhInit `full`); the last step of every ocn_ctx_step call leaves the
@@ -1686,7 +309,7 @@ static int prepare_static(ocn_ctx *c)
 // Whether any exchange has strips: some local block has a neighbour block (local or on another
 // rank) in one of the 8 directions -- exactly when plan_entries enumerates an entry.  Decided from
 // the decomposition alone (no plan is built, so nothing can fail inside a graph capture).
-static bool has_exchange(const ocn_ctx *c)
+bool has_exchange(const ocn_ctx *c)
 {
     for (const LBlock &b : c->blocks)
         for (int d = 0; d < 8; ++d)
@@ -1713,11 +336,23 @@ static int join_sync(ocn_ctx *c)
     return OCN_OK;
 }
 
+// Block b's compact tables (prepare_static) as a launch's `cp` argument, nullptr while the context
+// does not use them (the 2-D real(4) arrays then; the one-pass forms run only with the tables).  The
+// value lives to the end of the call expression it is written in; the launches copy what they need.
+struct CompactArg {
+    Compact t;
+    bool on;
+    operator const Compact *() const { return on ? &t : nullptr; }
+};
+static CompactArg compact_of(const ocn_ctx *c, const LBlock &b)
+{
+    return CompactArg{Compact{b.bits, b.rows, c->march}, c->compact};
+}
 // block b's launch arguments: geometry, field table, compact tables (or nullptr)
-#define FT(b) &(b).g, (b).ptr.data(), (int)(b).ptr.size(), cp(b, t)
+#define FT(b) &(b).g, (b).ptr.data(), (int)(b).ptr.size(), compact_of(c, b)
 // The buffer pairs whose roles a role-flip step swaps (a8's copies ssh := sshn etc.)
 static const int kFlipPairs[3][2] = {{OCN_SSH, OCN_SSHN}, {OCN_UBRTR, OCN_UBRTRN}, {OCN_VBRTR, OCN_VBRTRN}};
-static void swap_roles(ocn_ctx *c)
+void swap_roles(ocn_ctx *c)
 {
     for (LBlock &b : c->blocks)
         for (const auto &pr : kFlipPairs) std::swap(b.ptr[field_slot(pr[0])], b.ptr[field_slot(pr[1])]);
@@ -1730,7 +365,7 @@ static void swap_sshp(ocn_ctx *c)
     c->role ^= 2;
 }
 // one-pass steps: sshp, ubrtrp, vbrtrp and their second buffers trade places (role bit 4)
-static void swap_alt3(ocn_ctx *c)
+void swap_alt3(ocn_ctx *c)
 {
     for (LBlock &b : c->blocks) {
         std::swap(b.ptr[field_slot(OCN_SSHP)], b.sshp_alt);
@@ -1754,8 +389,32 @@ static void swap_tracer_alt(ocn_ctx *c)
         for (int k = 1; k <= c->sw.tracer_num; ++k) std::swap(b.ptr[field_slot(OCN_FF1P(k))], b.ffp_alt[(size_t)k - 1]);
     c->role ^= 16;
 }
-static size_t field_bytes(const LBlock &b) { return (size_t)b.g.pitch * (b.g.bnd_y2 - b.g.bnd_y1 + 1) * 8; }
-static bool is_alt_field(int id) { return id == OCN_SSHP || id == OCN_UBRTRP || id == OCN_VBRTRP; }
+// "The second buffers start as copies": for every block, whole arrays, on the context stream -- the
+// second buffers of the first nsw of sshp, ubrtrp, vbrtrp (3: the one-pass steps', 1: the recompute
+// steps' sshp), and with `tracers` every tracer's second ff1p buffer := the field's current buffer
+static int copy_to_alt(ocn_ctx *c, int nsw, bool tracers)
+{
+    for (LBlock &b : c->blocks) {
+        const std::pair<void *, int> sw[3] = {{b.sshp_alt, OCN_SSHP}, {b.up_alt, OCN_UBRTRP}, {b.vp_alt, OCN_VBRTRP}};
+        for (int i = 0; i < nsw; ++i)
+            HIPCHK(hipMemcpyAsync(sw[i].first, b.ptr[field_slot(sw[i].second)], field_bytes(b), hipMemcpyDeviceToDevice,
+                                  c->stream));
+        for (int t = 1; tracers && t <= c->sw.tracer_num; ++t)
+            HIPCHK(hipMemcpyAsync(b.ffp_alt[(size_t)t - 1], b.ptr[field_slot(OCN_FF1P(t))], field_bytes(b),
+                                  hipMemcpyDeviceToDevice, c->stream));
+    }
+    return OCN_OK;
+}
+// a8's copies as the call's last step leaves them (sshn := ssh, ubrtrn := ubrtr, vbrtrn := vbrtr, whole
+// arrays: the new state is in the first buffers, both buffers of each pair end equal)
+static int copy_pairs(ocn_ctx *c)
+{
+    for (const LBlock &b : c->blocks)
+        for (const auto &pr : kFlipPairs)
+            HIPCHK(hipMemcpyAsync(b.ptr[field_slot(pr[1])], b.ptr[field_slot(pr[0])], field_bytes(b),
+                                  hipMemcpyDeviceToDevice, c->stream));
+    return OCN_OK;
+}
 static bool is_flip_field(int id)
 {
     for (const auto &pr : kFlipPairs)
@@ -1937,9 +596,6 @@ static int run_tracer_step(ocn_ctx *c, double tau, hipStream_t st);
 static int tracer_step_block(ocn_ctx *c, const LBlock &b, int k, double tau, hipStream_t st);
 static std::vector<int> with_tracers(const ocn_ctx *c, const std::vector<int> &fields);
 
-// block b's one-pass variant for the current call (ctx kc_mode, the device verdict, its constants)
-static OnepassKC kc_of(const ocn_ctx *c, const LBlock &b) { return OnepassKC{c->kc_mode, c->d_fbz, b.kc}; }
-
 // The part of block b's interior the one-pass step covers when halos are exchanged: the interior
 // less w points on each side that has a neighbour block -- E, W, N, S, or a diagonal one of that
 // side: a diagonal neighbour receives this block's interior corner point (CA's stored depths in
@@ -1953,14 +609,23 @@ static bool side_fed(const LBlock &b, int side)   // side: 1 E, 2 W, 3 N, 4 S (k
     static const int diag[5][2] = {{0, 0}, {5, 6}, {7, 8}, {5, 7}, {6, 8}};   // E: NE SE, W: NW SW, N: NE NW, S: SE SW
     return b.nbr_rank[side - 1] >= 0 || b.nbr_rank[diag[side][0] - 1] >= 0 || b.nbr_rank[diag[side][1] - 1] >= 0;
 }
-static Range onepass_inner(const LBlock &b, int w)
+// (every inner range of a step form: the hybrid steps' 1- and 2-point frames, the x2 steps' and the x4
+// pairs' bands -- ew columns off each fed E / W side, ns rows off each fed N / S side)
+static Range inner_range(const LBlock &b, int ew, int ns)
 {
     Range r{b.g.nx_start, b.g.nx_end, b.g.ny_start, b.g.ny_end};
-    if (side_fed(b, 2)) r.m0 += w;
-    if (side_fed(b, 1)) r.m1 -= w;
-    if (side_fed(b, 4)) r.n0 += w;
-    if (side_fed(b, 3)) r.n1 -= w;
+    if (side_fed(b, 2)) r.m0 += ew;
+    if (side_fed(b, 1)) r.m1 -= ew;
+    if (side_fed(b, 4)) r.n0 += ns;
+    if (side_fed(b, 3)) r.n1 -= ns;
     return r;
+}
+// The E / W bands of an x2 step or x4 pair: `tile` columns -- what one wave (kX2BandCols) or pair
+// workgroup (kX4BandCols) marches whatever the band's width, so the wider band takes them off the
+// inner launch for nothing -- where the block is at least three of them wide, else the exchange's depth
+static int band_cols(const LBlock &b, int tile, int depth)
+{
+    return b.g.nx_end - b.g.nx_start + 1 >= 3 * tile ? tile : depth;
 }
 
 // A one-pass step with halo exchanges (several blocks or ranks), or with a8 / a9 work on the
@@ -1991,23 +656,18 @@ static int one_step_hybrid(ocn_ctx *c, double tau, const StepKind &k, bool last 
 {
     const ocn_sw_params &sw = c->sw;
     ocn_ctx::Rec rec;
-    Compact t;
-    auto cp = [c](const LBlock &b, Compact &tt) -> const Compact * {
-        tt = Compact{b.bits, b.rows, c->march};
-        return &tt;
-    };
     int32_t *nbad = k.check ? c->d_nbad : nullptr;
     hipStream_t s = c->stream;
     const bool xch = has_exchange(c);
     // the previous step's hh_init and this step's A on the frames (bnd range outside inner_ca)
     auto ca_frames = [&](hipStream_t st) -> int {
         RC(each_block(c, st, [&](const LBlock &b) -> int {
-            Range in = onepass_inner(b, 2);
+            Range in = inner_range(b, 2, 2);
             if (!side_fed(b, 2)) in.m0 = b.g.bnd_x1;   // no frame on the sides without a neighbour
             if (!side_fed(b, 1)) in.m1 = b.g.bnd_x2;
             if (!side_fed(b, 4)) in.n0 = b.g.bnd_y1;
             if (!side_fed(b, 3)) in.n1 = b.g.bnd_y2;
-            RC(launch_fused_ca(&b.g, b.ptr.data(), (int)b.ptr.size(), cp(b, t), OCN_PART_FRAME, sw, tau, !last, false,
+            RC(launch_fused_ca(FT(b), OCN_PART_FRAME, sw, tau, !last, false,
                                st, &in));
             return OCN_OK;
         }));
@@ -2016,7 +676,7 @@ static int one_step_hybrid(ocn_ctx *c, double tau, const StepKind &k, bool last 
     // B on the one-point bands along the exchanged sides
     auto b_bands = [&](hipStream_t st) -> int {
         RC(each_block(c, st, [&](const LBlock &b) -> int {
-            const Range in = onepass_inner(b, 1);
+            const Range in = inner_range(b, 1, 1);
             const Range all{b.g.nx_start, b.g.nx_end, b.g.ny_start, b.g.ny_end};
             if (in.m0 == all.m0 && in.m1 == all.m1 && in.n0 == all.n0 && in.n1 == all.n1) return OCN_OK;
             RC(launch_fused_b(FT(b), OCN_PART_ALL, sw, tau, last, true, st, nbad, true, false, (double *)b.sshp_alt,
@@ -2037,8 +697,8 @@ static int one_step_hybrid(ocn_ctx *c, double tau, const StepKind &k, bool last 
         HIPCHK(hipEventRecord(c->ev_fork, s));
         RC(timer_begin(c, OCN_TIMER_ONEPASS, rec));
         RC(each_block(c, s, [&](const LBlock &b) -> int {
-            const Range in = onepass_inner(b, 1);
-            RC(launch_onepass(&b.g, b.ptr.data(), (int)b.ptr.size(), cp(b, t), sw, tau, nbad, (double *)b.sshp_alt,
+            const Range in = inner_range(b, 1, 1);
+            RC(launch_onepass(FT(b), sw, tau, nbad, (double *)b.sshp_alt,
                               (double *)b.up_alt, (double *)b.vp_alt, s, &in, last, kc_of(c, b)));
             return OCN_OK;
         }));
@@ -2060,8 +720,8 @@ static int one_step_hybrid(ocn_ctx *c, double tau, const StepKind &k, bool last 
     if (xch) RC(run_sync(c, last ? c->sync_ca : c->sync_ca_reuse));
     RC(timer_begin(c, OCN_TIMER_ONEPASS, rec));
     RC(each_block(c, s, [&](const LBlock &b) -> int {
-        const Range in = onepass_inner(b, 1);
-        RC(launch_onepass(&b.g, b.ptr.data(), (int)b.ptr.size(), cp(b, t), sw, tau, nbad, (double *)b.sshp_alt,
+        const Range in = inner_range(b, 1, 1);
+        RC(launch_onepass(FT(b), sw, tau, nbad, (double *)b.sshp_alt,
                           (double *)b.up_alt, (double *)b.vp_alt, s, &in, last, kc_of(c, b)));
         return OCN_OK;
     }));
@@ -2083,11 +743,6 @@ static int hybrid_tail(ocn_ctx *c, double tau, const StepKind &k, bool last)
 {
     const ocn_sw_params &sw = c->sw;
     ocn_ctx::Rec rec;
-    Compact t;
-    auto cp = [c](const LBlock &b, Compact &tt) -> const Compact * {
-        tt = Compact{b.bits, b.rows, c->march};
-        return &tt;
-    };
     hipStream_t s = c->stream;
     const bool xch = has_exchange(c);
     swap_alt3(c);
@@ -2098,16 +753,13 @@ static int hybrid_tail(ocn_ctx *c, double tau, const StepKind &k, bool last)
         RC(timer_begin(c, OCN_TIMER_FUSED_C1, rec));
         for (size_t i = 0; i < c->blocks.size(); ++i) {
             const LBlock &b = c->blocks[i];
-            RC(launch_fused_c1(&b.g, pre[i].data(), (int)pre[i].size(), cp(b, t), OCN_PART_FRAME, sw, nullptr, s,
+            RC(launch_fused_c1(&b.g, pre[i].data(), (int)pre[i].size(), compact_of(c, b), OCN_PART_FRAME, sw, nullptr, s,
                                (const double *)b.sshp_alt, (const double *)b.up_alt, (const double *)b.vp_alt));
         }
         RC(timer_end(c, rec));
     }
     if (last) {
-        for (const LBlock &b : c->blocks)
-            for (const auto &pr : kFlipPairs)
-                HIPCHK(hipMemcpyAsync(b.ptr[field_slot(pr[1])], b.ptr[field_slot(pr[0])], field_bytes(b),
-                                      hipMemcpyDeviceToDevice, s));
+        RC(copy_pairs(c));
         RC(timer_begin(c, OCN_STAGE_HH_INIT, rec));
         RC(each_block(c, s, [&](const LBlock &b) { return launch_fused_c2(FT(b), OCN_PART_ALL, sw, true, s); }));
         RC(timer_end(c, rec));
@@ -2116,7 +768,7 @@ static int hybrid_tail(ocn_ctx *c, double tau, const StepKind &k, bool last)
     }
     if (k.next_a) {   // the next step is the last, standard one: hh_init + its fused A, then their sync
         RC(timer_begin(c, OCN_TIMER_FUSED_CA, rec));
-        RC(each_block(c, s, [&](const LBlock &b) { return launch_fused_ca(&b.g, b.ptr.data(), (int)b.ptr.size(), cp(b, t), OCN_PART_ALL, sw, tau, k.next_reuse,
+        RC(each_block(c, s, [&](const LBlock &b) { return launch_fused_ca(FT(b), OCN_PART_ALL, sw, tau, k.next_reuse,
                                false, s); }));
         RC(timer_end(c, rec));
         if (xch) RC(run_sync(c, k.next_reuse ? c->sync_ca_reuse : c->sync_ca));
@@ -2137,23 +789,13 @@ static int last_finish(ocn_ctx *c)
 {
     hipStream_t s = c->stream;
     ocn_ctx::Rec rec;
-    Compact t;
-    auto cp = [c](const LBlock &b, Compact &tt) -> const Compact * {
-        tt = Compact{b.bits, b.rows, c->march};
-        return &tt;
-    };
     // a8's copies sshn := ssh, ubrtrn := ubrtr, vbrtrn := vbrtr (the new state is in the first
     // buffers): in the hh_init march, which reads ssh anyway (one pass instead of three copies)
     auto copy_of = [](const LBlock &b) {
         auto p = [&](int id) { return (double *)b.ptr[field_slot(id)]; };
         return TailCopy{{p(OCN_SSH), p(OCN_UBRTR), p(OCN_VBRTR)}, {p(OCN_SSHN), p(OCN_UBRTRN), p(OCN_VBRTRN)}};
     };
-    if (!c->march)
-        for (const LBlock &b : c->blocks)
-            for (const auto &pr : {std::make_pair(OCN_SSH, OCN_SSHN), std::make_pair(OCN_UBRTR, OCN_UBRTRN),
-                                   std::make_pair(OCN_VBRTR, OCN_VBRTRN)})
-                HIPCHK(hipMemcpyAsync(b.ptr[field_slot(pr.second)], b.ptr[field_slot(pr.first)], field_bytes(b),
-                                      hipMemcpyDeviceToDevice, s));
+    if (!c->march) RC(copy_pairs(c));
     // (not while capturing a graph: the replays would not see hn_fresh)
     const bool keep_n = c->hn_fresh && !c->capturing && !c->r8_handed && !c->r4_escaped;
     RC(timer_begin(c, OCN_STAGE_HH_INIT, rec));
@@ -2170,14 +812,9 @@ static int one_step_last(ocn_ctx *c, double tau, const StepKind &k)
 {
     const ocn_sw_params &sw = c->sw;
     ocn_ctx::Rec rec;
-    Compact t;
-    auto cp = [c](const LBlock &b, Compact &tt) -> const Compact * {
-        tt = Compact{b.bits, b.rows, c->march};
-        return &tt;
-    };
     hipStream_t s = c->stream;
     RC(timer_begin(c, OCN_TIMER_ONEPASS, rec));
-    RC(each_block(c, s, [&](const LBlock &b) { return launch_onepass(&b.g, b.ptr.data(), (int)b.ptr.size(), cp(b, t), sw, tau, k.check ? c->d_nbad : nullptr,
+    RC(each_block(c, s, [&](const LBlock &b) { return launch_onepass(FT(b), sw, tau, k.check ? c->d_nbad : nullptr,
                           (double *)b.sshp_alt, (double *)b.up_alt, (double *)b.vp_alt, s, nullptr, true,
                           kc_of(c, b)); }));
     RC(timer_end(c, rec));
@@ -2259,18 +896,39 @@ static int prebuild_x2(ocn_ctx *c)
 // on every side a neighbour (diagonals included) fills halos of -- a point's stencil reaches the
 // state 2 points away (D at +-1, formed from the state at +-1).
 constexpr int kX2BandCols = 60;   // a one-pass wave's output columns (sw_kernels.hip MarchStep, kHalo 2)
-static Range x2_inner(const LBlock &b)
+static Range x2_inner(const LBlock &b) { return inner_range(b, band_cols(b, kX2BandCols, 2), 2); }
+
+// An x2 step's or x4 pair's launches with the exchange overlapped (OCN_OPT_OVERLAP 2): inner(b) for
+// every block on the compute stream, timed as `timer`; beside it on the comm stream the second ring's
+// save (save: the first step of a sequence), the exchange of `fields` `depth` points deep, then bands(b)
+// for every block (co: its launches may go as one, each_block); the join orders what follows after both.
+// OCN_TIMER_EXPOSED: from the inner launches' end to the comm chain's end.
+template <class Inner, class Bands>
+static int overlapped_exchange(ocn_ctx *c, int timer, int depth, const std::vector<int> &fields, bool save,
+                               Inner &&inner, Bands &&bands, bool co)
 {
-    auto any = [&](int a, int d1, int d2) { return b.nbr_rank[a - 1] >= 0 || b.nbr_rank[d1 - 1] >= 0 || b.nbr_rank[d2 - 1] >= 0; };
-    Range r{b.g.nx_start, b.g.nx_end, b.g.ny_start, b.g.ny_end};
-    // (the E / W bands a whole wave wide where the block is wide enough: a band's waves march 60
-    // columns whatever its width, so the wider band takes them off the inner launch for nothing)
-    const int ew = b.g.nx_end - b.g.nx_start + 1 >= 3 * kX2BandCols ? kX2BandCols : 2;
-    if (any(1, 5, 6)) r.m1 -= ew;   // E, NE, SE
-    if (any(2, 7, 8)) r.m0 += ew;   // W, NW, SW
-    if (any(3, 5, 7)) r.n1 -= 2;   // N, NE, NW
-    if (any(4, 6, 8)) r.n0 += 2;   // S, SE, SW
-    return r;
+    hipStream_t s = c->stream;
+    ocn_ctx::Rec rec;
+    HIPCHK(hipEventRecord(c->ev_fork, s));
+    RC(timer_begin(c, timer, rec));
+    RC(each_block(c, s, inner));
+    RC(timer_end(c, rec));
+    ocn_ctx::Rec xrec{OCN_TIMER_EXPOSED, nullptr, nullptr};
+    if (c->stage_timing) {
+        RC(get_event(c, xrec.a)); RC(get_event(c, xrec.b));
+        HIPCHK(hipEventRecord(xrec.a, s));
+    }
+    HIPCHK(hipStreamWaitEvent(c->comm_stream, c->ev_fork, 0));
+    if (save) RC(ring2_run(c, true, c->comm_stream));
+    RC(run_sync(c, fields, c->comm_stream, nullptr, depth));
+    RC(each_block(c, c->comm_stream, bands, co));
+    if (xrec.b) {
+        HIPCHK(hipEventRecord(xrec.b, c->comm_stream));
+        c->recs.push_back(xrec);
+    }
+    HIPCHK(hipEventRecord(c->ev_join, c->comm_stream));
+    c->sync_pending = true;
+    return join_sync(c);
 }
 
 // One x2 step.  With OCN_OPT_OVERLAP 2 (the default when the context exchanges with other ranks;
@@ -2308,35 +966,17 @@ static int one_step_x2(ocn_ctx *c, double tau, const StepKind &k)
     const int lv = ov_begin(c, 2, !k.x2_save, probe);
     RC(ov_mark(c, probe, false));
     if (lv >= 2 && !c->capturing) {
-        HIPCHK(hipEventRecord(c->ev_fork, s));
-        RC(timer_begin(c, OCN_TIMER_ONEPASS, rec));
-        RC(each_block(c, s, [&](const LBlock &b) -> int {
-            const Range in = x2_inner(b);
-            RC(march(b, s, &in, nullptr));
-            return OCN_OK;
-        }));
-        RC(timer_end(c, rec));
-        ocn_ctx::Rec xrec{OCN_TIMER_EXPOSED, nullptr, nullptr};   // inner march end -> comm chain end
-        if (c->stage_timing) {
-            RC(get_event(c, xrec.a)); RC(get_event(c, xrec.b));
-            HIPCHK(hipEventRecord(xrec.a, s));
-        }
-        HIPCHK(hipStreamWaitEvent(c->comm_stream, c->ev_fork, 0));
-        if (k.x2_save) RC(ring2_run(c, true, c->comm_stream));
-        RC(run_sync(c, with_tracers(c, kStateX2), c->comm_stream, nullptr, 2));   // the state two points deep
-        RC(each_block(c, c->comm_stream, [&](const LBlock &b) -> int {   // the bands (+ the tracer step)
-            const Range in = x2_inner(b);
-            RC(march(b, c->comm_stream, nullptr, &in));
-            return co ? tracer_step_block(c, b, 1, tau, c->comm_stream) : OCN_OK;
-        }, co));
+        RC(overlapped_exchange(c, OCN_TIMER_ONEPASS, 2, with_tracers(c, kStateX2), k.x2_save,   // the state two points deep
+            [&](const LBlock &b) -> int {
+                const Range in = x2_inner(b);
+                return march(b, s, &in, nullptr);
+            },
+            [&](const LBlock &b) -> int {   // the bands (+ the tracer step)
+                const Range in = x2_inner(b);
+                RC(march(b, c->comm_stream, nullptr, &in));
+                return co ? tracer_step_block(c, b, 1, tau, c->comm_stream) : OCN_OK;
+            }, co));
         if (co) co_done();
-        if (xrec.b) {
-            HIPCHK(hipEventRecord(xrec.b, c->comm_stream));
-            c->recs.push_back(xrec);
-        }
-        HIPCHK(hipEventRecord(c->ev_join, c->comm_stream));
-        c->sync_pending = true;
-        RC(join_sync(c));
     } else {
         if (k.x2_save) RC(ring2_run(c, true, s));
         RC(run_sync(c, with_tracers(c, kStateX2), s, nullptr, 2));   // the state two points deep
@@ -2413,17 +1053,7 @@ static int one_step_pair(ocn_ctx *c, double tau, const StepKind &k)
 // wider band takes that many columns off the inner launch for nothing -- one GPU, 2x1 blocks of
 // 4096^2 overlapped: see DESIGN.md 4.4
 constexpr int kX4BandCols = 116;   // sw_kernels.hip MarchStep::kPairCols
-static Range x4_inner(const LBlock &b)
-{
-    auto any = [&](int a, int d1, int d2) { return b.nbr_rank[a - 1] >= 0 || b.nbr_rank[d1 - 1] >= 0 || b.nbr_rank[d2 - 1] >= 0; };
-    Range r{b.g.nx_start, b.g.nx_end, b.g.ny_start, b.g.ny_end};
-    const int ew = b.g.nx_end - b.g.nx_start + 1 >= 3 * kX4BandCols ? kX4BandCols : 4;
-    if (any(1, 5, 6)) r.m1 -= ew;   // E, NE, SE
-    if (any(2, 7, 8)) r.m0 += ew;   // W, NW, SW
-    if (any(3, 5, 7)) r.n1 -= 4;   // N, NE, NW
-    if (any(4, 6, 8)) r.n0 += 4;   // S, SE, SW
-    return r;
-}
+static Range x4_inner(const LBlock &b) { return inner_range(b, band_cols(b, kX4BandCols, 4), 4); }
 
 // With OCN_OPT_OVERLAP 2 (the default with remote peers; not while capturing): the inner part
 // (x4_inner) on the compute stream beside the exchange on the comm stream (the device's highest
@@ -2488,33 +1118,16 @@ static int one_step_x4(ocn_ctx *c, double tau, const StepKind &k)
     const int lv = ov_begin(c, 4, !k.x2_save && inner_ok, probe);
     RC(ov_mark(c, probe, false));
     if (lv >= 2 && !c->capturing && inner_ok) {
-        HIPCHK(hipEventRecord(c->ev_fork, s));
-        RC(timer_begin(c, OCN_TIMER_ONEPASS2, rec));
-        RC(each_block(c, s, [&](const LBlock &b) -> int {
-            const Range in = x4_inner(b);
-            return pair(b, s, &in, nullptr);
-        }));
-        RC(timer_end(c, rec));
-        ocn_ctx::Rec xrec{OCN_TIMER_EXPOSED, nullptr, nullptr};   // inner pair end -> comm chain end
-        if (c->stage_timing) {
-            RC(get_event(c, xrec.a)); RC(get_event(c, xrec.b));
-            HIPCHK(hipEventRecord(xrec.a, s));
-        }
-        HIPCHK(hipStreamWaitEvent(c->comm_stream, c->ev_fork, 0));
-        if (k.x2_save) RC(ring2_run(c, true, c->comm_stream));
-        RC(run_sync(c, tr ? with_tracers(c, kStateX2) : kStateX2, c->comm_stream, nullptr, 4));   // the state 4 deep
-        RC(each_block(c, c->comm_stream, [&](const LBlock &b) -> int {   // the bands (+ tracer step A)
-            const Range in = x4_inner(b);
-            RC(pair(b, c->comm_stream, nullptr, &in));
-            return co ? tr_a(b, 1, c->comm_stream) : OCN_OK;
-        }, co));
-        if (xrec.b) {
-            HIPCHK(hipEventRecord(xrec.b, c->comm_stream));
-            c->recs.push_back(xrec);
-        }
-        HIPCHK(hipEventRecord(c->ev_join, c->comm_stream));
-        c->sync_pending = true;
-        RC(join_sync(c));
+        RC(overlapped_exchange(c, OCN_TIMER_ONEPASS2, 4, tr ? with_tracers(c, kStateX2) : kStateX2, k.x2_save,   // the state 4 deep
+            [&](const LBlock &b) -> int {
+                const Range in = x4_inner(b);
+                return pair(b, s, &in, nullptr);
+            },
+            [&](const LBlock &b) -> int {   // the bands (+ tracer step A)
+                const Range in = x4_inner(b);
+                RC(pair(b, c->comm_stream, nullptr, &in));
+                return co ? tr_a(b, 1, c->comm_stream) : OCN_OK;
+            }, co));
     } else {
         if (k.x2_save) RC(ring2_run(c, true, s));
         RC(run_sync(c, tr ? with_tracers(c, kStateX2) : kStateX2, s, nullptr, 4));   // the state four points deep
@@ -2613,11 +1226,6 @@ static int one_step_fused(ocn_ctx *c, double tau, const StepKind &k)
     const bool check = k.check, first = k.first, last = k.last, flip = k.flip;
     const ocn_sw_params &sw = c->sw;
     ocn_ctx::Rec rec;
-    auto cp = [c](const LBlock &b, Compact &t) -> const Compact * {
-        t = Compact{b.bits, b.rows, c->march};
-        return c->compact ? &t : nullptr;
-    };
-    Compact t;
     int32_t *nbad = check ? c->d_nbad : nullptr;
     hipStream_t s = c->stream;
     const bool ffs = sw.full_free_surface > 0;
@@ -2631,7 +1239,7 @@ static int one_step_fused(ocn_ctx *c, double tau, const StepKind &k)
         if (k.one && (has_exchange(c) || c->ring_sea)) return one_step_hybrid(c, tau, k);
         if (k.one) {   // the whole step in one launch (single block: no exchange, no ring launch)
             RC(timer_begin(c, OCN_TIMER_ONEPASS, rec));
-            RC(each_block(c, s, [&](const LBlock &b) { return launch_onepass(&b.g, b.ptr.data(), (int)b.ptr.size(), cp(b, t), sw, tau, nbad,
+            RC(each_block(c, s, [&](const LBlock &b) { return launch_onepass(FT(b), sw, tau, nbad,
                                   (double *)b.sshp_alt, (double *)b.up_alt, (double *)b.vp_alt, s, nullptr, false,
                                   kc_of(c, b)); }));
             RC(timer_end(c, rec));
@@ -2639,7 +1247,7 @@ static int one_step_fused(ocn_ctx *c, double tau, const StepKind &k)
             swap_roles(c);
             if (k.next_a) {   // the next step is the last, standard one: hh_init + its fused A
                 RC(timer_begin(c, OCN_TIMER_FUSED_CA, rec));
-                RC(each_block(c, s, [&](const LBlock &b) { return launch_fused_ca(&b.g, b.ptr.data(), (int)b.ptr.size(), cp(b, t), OCN_PART_ALL, sw, tau,
+                RC(each_block(c, s, [&](const LBlock &b) { return launch_fused_ca(FT(b), OCN_PART_ALL, sw, tau,
                                        k.next_reuse, false, s); }));
                 RC(timer_end(c, rec));
             }
@@ -2684,7 +1292,7 @@ static int one_step_fused(ocn_ctx *c, double tau, const StepKind &k)
         auto hh_init = [&](int part) -> int {
             RC(each_block(c, s, [&](const LBlock &b) -> int {
                 if (k.next_a)
-                    RC(launch_fused_ca(&b.g, b.ptr.data(), (int)b.ptr.size(), cp(b, t), part, sw, tau, k.next_reuse,
+                    RC(launch_fused_ca(FT(b), part, sw, tau, k.next_reuse,
                                        k.next_reuse && k.rc_next, s));
                 else
                     RC(launch_fused_c2(FT(b), part, sw, full_c2, s));
@@ -2706,7 +1314,7 @@ static int one_step_fused(ocn_ctx *c, double tau, const StepKind &k)
                 const LBlock &b = c->blocks[i];
                 // recompute steps: B filtered sshp into the other buffer, now the current one; a8
                 // on the ring reads the previous one (sshp_alt after the swap) and completes it
-                RC(launch_fused_c1(&b.g, pre[i].data(), (int)pre[i].size(), cp(b, t), OCN_PART_FRAME, sw, nullptr, s,
+                RC(launch_fused_c1(&b.g, pre[i].data(), (int)pre[i].size(), compact_of(c, b), OCN_PART_FRAME, sw, nullptr, s,
                                    k.rc ? (const double *)b.sshp_alt : nullptr));
             }
             RC(timer_end(c, rec));
@@ -2830,8 +1438,7 @@ static int expl_tracer(ocn_ctx *c, double tau, bool compact)
 // tracer k's tracer step on block b
 static int tracer_step_block(ocn_ctx *c, const LBlock &b, int k, double tau, hipStream_t st)
 {
-    const Compact t{b.bits, b.rows, c->march};
-    return launch_tracer_step(&b.g, b.ptr.data(), (int)b.ptr.size(), c->compact ? &t : nullptr, k, tau, c->sw.time_smooth,
+    return launch_tracer_step(&b.g, b.ptr.data(), (int)b.ptr.size(), compact_of(c, b), k, tau, c->sw.time_smooth,
                               (double *)b.ptr[field_slot(OCN_FF1N(k))], (double *)b.ffp_alt[(size_t)k - 1], b.own, st);
 }
 static int run_tracer_step(ocn_ctx *c, double tau, hipStream_t st)
@@ -2863,204 +1470,40 @@ static std::vector<int> with_tracers(const ocn_ctx *c, const std::vector<int> &f
     return out;
 }
 
-// ------------------------------------------------------------------ initial state
-// init_grid_data + init_ocean_data (control/init_data.f90:29-125) with every 2-D field formed on
-// the device (init_kernels.hip); the host supplies the basin mask and the grid's O(nx + ny)
-// trigonometric row / column factors from its libm, as the reference computes them.
-static const float kPi = 3.1415926f;              // constants.f90:14
-static const double kDPi = 3.14159265358979;      // constants.f90:17
-static const double kLatExtr = 89.99999;          // constants.f90:20
-static const float kRadEarth = 6371000.0f;        // constants.f90:22
-static const float kEarthAngVel = 7.2921159e-5f;  // constants.f90:22
-static double dsind(double x) { return std::sin((x / 180.0) * kDPi); }   // core/math_tools.f90
-static double dcosd(double x) { return std::cos((x / 180.0) * kDPi); }
-
-// One block's grid tables in one device allocation (freed by the caller after the launch ran):
-// grid_base_init's coordinates xt / xu (columns) and yt / yv (rows) (grid_kernels.f90:94-202),
-// then grid_geo_init's factors of them (grid_parameters.f90:80-181).
-struct GridTables {
-    std::vector<float> cos_t, cos_v;                   // (float) dcosd(lat_mod(yt)), of yv, per row
-    std::vector<double> sin_v, cosy_v, cos_xu;         // dsind(yv), dcosd(yv) per row; dcosd(xu) per column
-    // the same factors of rows bnd_y1 and bnd_y2 (outside the metric range) from the global row
-    // formulas, as the neighbour blocks form them (GridInit ext)
-    float ext_ct[kExtRows], ext_cv[kExtRows];
-    double ext_sin_v[kExtRows], ext_cosy_v[kExtRows];
-};
-static void grid_tables(const ocn_ctx *c, const ocn_block &g, GridTables &t)
+// "The fields changed behind the step's back": what the step decisions rest on is dropped, by cause --
+// a raw device pointer handed out (ocn_ctx_field), an upload or a sync of field id, a stage launched by
+// the host, the initial state formed again.  (real(4) fields also void the compact tables: at the sites.)
+enum class Changed { Pointer, Upload, Sync, Stage, Init };
+static void fields_changed(ocn_ctx *c, Changed why, int id = -1)
 {
-    const ocn_basin &bs = c->basin;
-    const int w = g.bnd_x2 - g.bnd_x1 + 1, h = g.bnd_y2 - g.bnd_y1 + 1, mmm = 3, nnn = 3;
-    std::vector<double> xt(w), xu(w, 0.0), yt(h), yv(h, 0.0);
-    for (int m = g.bnd_x1; m <= g.bnd_x2; ++m) xt[m - g.bnd_x1] = bs.rlon + (double)(m - mmm) * bs.dxst;
-    for (int n = g.bnd_y1; n <= g.bnd_y2; ++n) yt[n - g.bnd_y1] = bs.rlat + (double)(n - nnn) * bs.dyst;
-    for (int i = 0; i + 1 < w; ++i) xu[i] = (xt[i] + xt[i + 1]) / 2.0;
-    for (int i = 0; i + 1 < h; ++i) yv[i] = (yt[i] + yt[i + 1]) / 2.0;
-    auto lat_mod = [](double y) { return std::max(std::min(y, kLatExtr), -kLatExtr); };
-    t.cos_t.assign(h, 0.0f); t.cos_v.assign(h, 0.0f); t.sin_v.assign(h, 0.0); t.cosy_v.assign(h, 0.0);
-    t.cos_xu.assign(w, 0.0);
-    for (int n = g.ny_start - 1; n <= g.ny_end + 1; ++n) {   // the metric range's rows and columns
-        const int r = n - g.bnd_y1;
-        t.cos_t[r] = (float)dcosd(lat_mod(yt[r]));
-        t.cos_v[r] = (float)dcosd(lat_mod(yv[r]));
-        t.sin_v[r] = dsind(yv[r]);
-        t.cosy_v[r] = dcosd(yv[r]);
-    }
-    for (int m = g.nx_start - 1; m <= g.nx_end + 1; ++m) t.cos_xu[m - g.bnd_x1] = dcosd(xu[m - g.bnd_x1]);
-    // grid_base_init on the neighbour: yt(n), yv(n) = (yt(n) + yt(n + 1)) / 2 (GridInit ext's rows)
-    const int ext_row[kExtRows] = {g.bnd_y1, g.bnd_y2, g.bnd_y1 - 1, g.bnd_y1 - 2, g.bnd_y2 + 1, g.bnd_y2 + 2};
-    for (int i = 0; i < kExtRows; ++i) {
-        const int n = ext_row[i];
-        const double yt_n = bs.rlat + (double)(n - nnn) * bs.dyst, yt_n1 = bs.rlat + (double)(n + 1 - nnn) * bs.dyst;
-        const double yv_n = (yt_n + yt_n1) / 2.0;
-        t.ext_ct[i] = (float)dcosd(lat_mod(yt_n));
-        t.ext_cv[i] = (float)dcosd(lat_mod(yv_n));
-        t.ext_sin_v[i] = dsind(yv_n);
-        t.ext_cosy_v[i] = dcosd(yv_n);
-    }
+    const bool ptr = why == Changed::Pointer, one = ptr || why == Changed::Upload || why == Changed::Sync;
+    // a field the role-flip vote's checks cover (check_coherence: the pairs, and for the x2 steps sshp /
+    // ubrtrp / vbrtrp, h_r and mu)
+    const bool voted = is_flip_field(id) || is_alt_field(id) || id == OCN_HHQ_REST || id == OCN_MU;
+    const bool r4_ptr = ptr && is_r4(id);   // (may be written behind our back: r4_escaped; of these flags only hn_fresh)
+    if (!one || why == Changed::Sync || voted) c->coherent_known = false;
+    // the current buffer changes; the one-pass steps' second buffer must be copied again
+    if (!one || is_alt_field(id)) c->alt_ok = false;
+    if (!one || is_tracer_field(id)) c->tr_alt_ok = false;
+    if (why != Changed::Init && !r4_ptr) c->hh_consistent = false;   // (init: set once init_state has run hh_init)
+    c->hn_fresh = false;
+    if (!r4_ptr) c->fb_state = kFbUnchecked;
+    // h_r's copy (refresh_hrx): any real(8) pointer, h_r itself otherwise (stage: left; init: init_state)
+    if (ptr ? !is_r4(id) : one && id == OCN_HHQ_REST) c->hrx_ok = false;
+    if (why == Changed::Upload && (id == OCN_HHQ_REST || id == OCN_HHQ_N)) c->hqn_stale = true;
+    // a raw r8 pointer names the field's own buffer from now on and may be written at any time
+    if (ptr && !is_r4(id)) c->r8_handed = true;
+    if (ptr && voted) c->r8_escaped = true;
 }
 
-static int upload_field(ocn_ctx *c, const LBlock &b, int id, const void *host, bool async)
+// An entry that may take part in a collective: the null check, then f watched under the entry's name
+template <class F> static int entry(ocn_ctx *c, const char *name, F &&f)
 {
-    const size_t es = is_r4(id) ? 4 : 8;
-    const size_t w = (size_t)(b.g.bnd_x2 - b.g.bnd_x1 + 1), rows = (size_t)(b.g.bnd_y2 - b.g.bnd_y1 + 1);
-    if (async)
-        HIPCHK(hipMemcpy2DAsync(b.ptr[field_slot(id)], (size_t)b.g.pitch * es, host, w * es, w * es, rows,
-                                hipMemcpyHostToDevice, c->stream));
-    else
-        HIPCHK(hipMemcpy2D(b.ptr[field_slot(id)], (size_t)b.g.pitch * es, host, w * es, w * es, rows,
-                           hipMemcpyHostToDevice));
-    return OCN_OK;
-}
-
-static int init_state(ocn_ctx *c)
-{
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const ocn_basin &bs = c->basin;
-    const size_t nxy = (size_t)bs.nx * bs.ny;
-    // device scratch of this call: the basin mask, then per block its grid tables
-    std::vector<GridTables> tabs(c->blocks.size());
-    const size_t topo_at = (nxy * sizeof(int32_t) + 255) / 256 * 256;
-    size_t bytes = topo_at + c->topo.size() * sizeof(float);
-    std::vector<size_t> at(c->blocks.size());
-    for (size_t i = 0; i < c->blocks.size(); ++i) {
-        grid_tables(c, c->blocks[i].g, tabs[i]);
-        at[i] = (bytes + 255) / 256 * 256;
-        bytes = at[i] + tabs[i].cos_t.size() * 2 * 4 + 256 + (tabs[i].sin_v.size() * 2 + tabs[i].cos_xu.size()) * 8;
-    }
-    char *scratch = nullptr;
-    HIPCHK(hipMalloc(&scratch, bytes));
-    struct Free { char *p; ~Free() { if (p) (void)hipFree(p); } } free_scratch{scratch};
-    HIPCHK(hipMemcpy(scratch, c->mask.data(), nxy * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (!c->topo.empty())
-        HIPCHK(hipMemcpy(scratch + topo_at, c->topo.data(), c->topo.size() * sizeof(float), hipMemcpyHostToDevice));
-    const float pip180 = kPi / 180.0f;
-    for (size_t i = 0; i < c->blocks.size(); ++i) {
-        const LBlock &b = c->blocks[i];
-        const GridTables &t = tabs[i];
-        const size_t h = t.cos_t.size(), w = t.cos_xu.size();
-        char *p = scratch + at[i];
-        GridInit q{};
-        q.g = b.g;
-        q.mask = (const int32_t *)scratch;
-        q.nx = bs.nx;
-        for (int id = 0; id < OCN_NUM_R4; ++id) q.r4[id] = b.f<float>(id);
-        q.cos_t = (const float *)p; q.cos_v = q.cos_t + h;
-        p += (h * 2 * 4 + 255) / 256 * 256;
-        q.sin_v = (const double *)p; q.cosy_v = q.sin_v + h; q.cos_xu = q.cosy_v + h;
-        HIPCHK(hipMemcpy((void *)q.cos_t, t.cos_t.data(), h * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy((void *)q.cos_v, t.cos_v.data(), h * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy((void *)q.sin_v, t.sin_v.data(), h * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy((void *)q.cosy_v, t.cosy_v.data(), h * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy((void *)q.cos_xu, t.cos_xu.data(), w * 8, hipMemcpyHostToDevice));
-        q.cos_rot = dcosd(bs.rotation_on_lat);
-        q.sin_rot = dsind(bs.rotation_on_lat);
-        q.sin_extr = dsind(kLatExtr);
-        q.sx = (float)bs.dxst * pip180 * kRadEarth;
-        q.sy = (float)bs.dyst * pip180 * kRadEarth;
-        q.cor = 2.0f * kEarthAngVel;
-        q.sqrt2 = std::sqrt(2.0f);
-        q.curve = bs.curve_grid != 0;
-        for (int j = 0; j < kExtRows; ++j) {
-            q.ext_ct[j] = t.ext_ct[j]; q.ext_cv[j] = t.ext_cv[j];
-            q.ext_sin_v[j] = t.ext_sin_v[j]; q.ext_cosy_v[j] = t.ext_cosy_v[j];
-        }
-        q.ext = b.ext;
-        RC(launch_init_grid(q, c->stream));
-        c->static_dirty = true;
-        if (c->topo.empty()) {
-            RC(launch_fill_field(b.g, b.f<double>(OCN_HHQ_REST), 100.0, c->stream));   // init_data.f90:112-114
-        } else {
-            const long pts = (long)(b.g.bnd_x2 - b.g.bnd_x1 + 1) * (b.g.bnd_y2 - b.g.bnd_y1 + 1);
-            hipLaunchKernelGGL(k_topography, dim3((unsigned)((pts + 255) / 256)), dim3(256), 0, c->stream, b.g,
-                               b.f<double>(OCN_HHQ_REST), b.f<float>(OCN_LU), (const float *)(scratch + topo_at), bs.nx - 4);
-            RC(check_launch());
-        }
-        RC(launch_gaussian(b.g, b.f<double>(OCN_SSH), b.f<float>(OCN_LU), bs.nx / 2, bs.ny / 2, 1.0, c->stream));
-    }
-    if (!c->topo.empty()) RC(run_sync(c, {OCN_HHQ_REST}));   // init_data.f90:119
-    RC(run_sync(c, {OCN_SSH}));                               // envoke_gaussian_elimination's sync
-    for (const LBlock &b : c->blocks) {                       // sshn = ssh, sshp = ssh (whole arrays)
-        const size_t bytes = (size_t)b.g.pitch * (b.g.bnd_y2 - b.g.bnd_y1 + 1) * 8;
-        HIPCHK(hipMemcpyAsync(b.ptr[field_slot(OCN_SSHN)], b.ptr[field_slot(OCN_SSH)], bytes,
-                              hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(b.ptr[field_slot(OCN_SSHP)], b.ptr[field_slot(OCN_SSH)], bytes,
-                              hipMemcpyDeviceToDevice, c->stream));
-    }
-    RC(envoke(c, OCN_STAGE_HH_INIT, 0.0));                    // init_data.f90:60-63
-    for (const LBlock &b : c->blocks) {                       // u = v = 0, mu = lvisc_2 then 0 (:67-77)
-        const long n = (long)b.g.pitch * (b.g.bnd_y2 - b.g.bnd_y1 + 1);
-        for (int id : {OCN_UBRTR, OCN_UBRTRN, OCN_UBRTRP, OCN_VBRTR, OCN_VBRTRN, OCN_VBRTRP, OCN_MU}) {
-            hipLaunchKernelGGL(k_fill_r8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                               b.f<double>(id), n, 0.0);
-            RC(check_launch());
-        }
-    }
-    if (c->sw.use_tracers > 0) {                              // init_data.f90:80-90
-        for (int k = 1; k <= c->sw.tracer_num; ++k) {
-            for (const LBlock &b : c->blocks)
-                RC(launch_gaussian(b.g, b.f<double>(OCN_FF1(k)), b.f<float>(OCN_LU), bs.nx / 2, bs.ny / 2, 0.5,
-                                   c->stream));
-            RC(run_sync(c, {OCN_FF1(k)}));
-            for (const LBlock &b : c->blocks) {
-                const size_t bytes = (size_t)b.g.pitch * (b.g.bnd_y2 - b.g.bnd_y1 + 1) * 8;
-                HIPCHK(hipMemcpyAsync(b.ptr[field_slot(OCN_FF1N(k))], b.ptr[field_slot(OCN_FF1(k))], bytes,
-                                      hipMemcpyDeviceToDevice, c->stream));
-                HIPCHK(hipMemcpyAsync(b.ptr[field_slot(OCN_FF1P(k))], b.ptr[field_slot(OCN_FF1(k))], bytes,
-                                      hipMemcpyDeviceToDevice, c->stream));
-            }
-        }
-        for (const LBlock &b : c->blocks) {
-            const long n = (long)b.g.pitch * (b.g.bnd_y2 - b.g.bnd_y1 + 1);
-            for (int id : {OCN_FLUX_X, OCN_FLUX_Y}) {
-                hipLaunchKernelGGL(k_fill_r8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                                   b.f<double>(id), n, 0.0);
-                RC(check_launch());
-            }
-        }
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->initialized = true;
-    c->ext_ok = true;   // the real(4) fields are init_state's: the ext rows are the neighbours' metric rows
-    c->hrx_ok = false;
-    return OCN_OK;
+    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
+    return guarded(c, name, f);
 }
 
 }  // namespace ocn
-
-static void set_mask(ocn_ctx *c, const int32_t *mask)
-{
-    const ocn_basin *basin = &c->basin;
-    const size_t nxy = (size_t)basin->nx * basin->ny;
-    c->mask.assign(nxy, 0);
-    if (mask) {
-        std::memcpy(c->mask.data(), mask, nxy * sizeof(int32_t));
-    } else {   // tools/io.f90:49-59: closed box with a 2-cell land frame
-        for (int n = 1; n <= basin->ny; ++n)
-            for (int m = 1; m <= basin->nx; ++m)
-                c->mask[(size_t)(m - 1) + (size_t)(n - 1) * basin->nx] =
-                    (m < 3 || m > basin->nx - 2 || n < 3 || n > basin->ny - 2) ? 1 : 0;
-    }
-}
 
 // ================================================================== C ABI (PSy layer)
 extern "C" {
@@ -3073,10 +1516,9 @@ int ocn_abi_version(void) { return OCN_ABI_VERSION; }
 const char *ocn_build_id(void) { return OCN_BUILD_ID; }
 int64_t ocn_launch_count(void) { return (int64_t)g_launches.load(std::memory_order_relaxed); }
 
-static int ctx_destroy(ocn_ctx *c);
 // shared: the compute stream of the ensemble `ens` the context becomes a member of (null: its own)
-static int ctx_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_decomp *dec, const int32_t *mask,
-                      hipStream_t shared, ocn_ens *ens, ocn_ctx **out)
+extern "C++" int ocn::ctx_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_decomp *dec, const int32_t *mask,
+                                 hipStream_t shared, ocn_ens *ens, ocn_ctx **out)
 {
     if (!basin || !sw || !dec || !out) return set_error(OCN_ERR_ARG, "null argument");
     if (basin->nx < 5 || basin->ny < 5) return set_error(OCN_ERR_ARG, "nx, ny must be >= 5");
@@ -3120,70 +1562,13 @@ int ocn_ctx_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_de
     return ctx_create(basin, sw, dec, mask, nullptr, nullptr, out);
 }
 
-// host-only context (decomposition only, no device) for the query entry points
-static int host_ctx(const ocn_basin *basin, const ocn_decomp *dec, const int32_t *mask, ocn_ctx *&c)
-{
-    if (!basin || !dec) return set_error(OCN_ERR_ARG, "null argument");
-    if (basin->nx < 5 || basin->ny < 5) return set_error(OCN_ERR_ARG, "nx, ny must be >= 5");
-    if (dec->bnx < 1 || dec->bny < 1 || dec->nranks < 1 || dec->rank < 0 || dec->rank >= dec->nranks)
-        return set_error(OCN_ERR_ARG, "bad decomposition request");
-    c = new ocn_ctx();
-    c->basin = *basin; c->dec = *dec; c->bnx = dec->bnx; c->bny = dec->bny;
-    set_mask(c, mask);
-    const int rc = decompose(c);
-    if (rc) { delete c; c = nullptr; }
-    return rc;
-}
-
-int ocn_decompose(const ocn_basin *basin, const ocn_decomp *dec, const int32_t *mask, ocn_block_info *out,
-                  int32_t cap, int32_t *count)
-{
-    ocn_ctx *c = nullptr;
-    RC(host_ctx(basin, dec, mask, c));
-    const int n = (int)c->blocks.size();
-    if (count) *count = n;
-    for (int k = 0; k < n && k < cap && out; ++k) {
-        const LBlock &b = c->blocks[k];
-        out[k].geom = b.g; out[k].bm = b.bm; out[k].bn = b.bn;
-        for (int d = 0; d < 8; ++d) { out[k].nbr_rank[d] = b.nbr_rank[d]; out[k].nbr_k[d] = b.nbr_k[d]; }
-    }
-    delete c;
-    return OCN_OK;
-}
-
-int ocn_halo_schedule(const ocn_basin *basin, const ocn_decomp *dec, const int32_t *mask, const int32_t *field_ids,
-                      int32_t nfields, ocn_halo_msg *out, int32_t cap, int32_t *count)
-{
-    if (!field_ids || nfields < 1) return set_error(OCN_ERR_ARG, "no fields");
-    std::vector<int> fields(field_ids, field_ids + nfields);
-    for (int id : fields)
-        if (id < OCN_SSH || id >= OCN_TRACER_BASE + 3 * kMaxTracers)
-            return set_error(OCN_ERR_ARG, "halo exchange is defined for real(8) fields");
-    ocn_ctx *c = nullptr;
-    RC(host_ctx(basin, dec, mask, c));
-    std::vector<PlanEntry> es;
-    const int rc = plan_entries(c, fields, es);
-    delete c;
-    RC(rc);
-    if (count) *count = (int32_t)es.size();
-    for (size_t i = 0; i < es.size() && (int32_t)i < cap && out; ++i) {
-        const PlanEntry &e = es[i];
-        ocn_halo_msg &o = out[i];
-        o.kind = e.kind; o.peer = e.peer; o.k = e.k; o.k_src = e.ks; o.field = e.field;
-        o.dst_x0 = e.dst.x0; o.dst_x1 = e.dst.x1; o.dst_y0 = e.dst.y0; o.dst_y1 = e.dst.y1;
-        o.src_x0 = e.src.x0; o.src_x1 = e.src.x1; o.src_y0 = e.src.y0; o.src_y1 = e.src.y1;
-        o.offset = e.buf_off; o.count = e.count;
-    }
-    return OCN_OK;
-}
-
 int ocn_ctx_destroy(ocn_ctx *c)
 {
     if (c && c->ens) return set_error(OCN_ERR_ARG, "a member of an ensemble is destroyed by ocn_ens_destroy");
     return ctx_destroy(c);
 }
 
-static int ctx_destroy(ocn_ctx *c)
+extern "C++" int ocn::ctx_destroy(ocn_ctx *c)
 {
     if (!c) return OCN_OK;
     if (c->wd.joinable()) {   // the watchdog first: nothing is watched from here on
@@ -3242,7 +1627,6 @@ int ocn_ctx_block_info(const ocn_ctx *c, int k, ocn_block_info *out)
 }
 
 static int alt_home(ocn_ctx *c);
-static int complete_open(ocn_ctx *c);
 void *ocn_ctx_field(const ocn_ctx *c, int k, int id)
 {
     if (!c || k < 0 || k >= (int)c->blocks.size() || !has_field(c, id)) {
@@ -3255,12 +1639,7 @@ void *ocn_ctx_field(const ocn_ctx *c, int k, int id)
     // a raw r8 pointer names the field's own buffer from now on (step_impl returns the current
     // values there at the end of every call)
     if (!is_r4(id) && alt_home(w) != OCN_OK) return nullptr;
-    if (is_flip_field(id)) { c->r8_escaped = true; c->coherent_known = false; }
-    if (is_alt_field(id)) c->alt_ok = false;
-    if (is_tracer_field(id)) c->tr_alt_ok = false;
-    if (!is_r4(id)) { c->r8_handed = true; c->hh_consistent = false; c->fb_state = kFbUnchecked; c->hrx_ok = false; }
-    c->hn_fresh = false;
-    if (is_alt_field(id) || id == OCN_HHQ_REST || id == OCN_MU) { c->r8_escaped = true; c->coherent_known = false; }
+    fields_changed(w, Changed::Pointer, id);
     return c->blocks[k].ptr[field_slot(id)];
 }
 
@@ -3395,80 +1774,52 @@ int ocn_ctx_set_topography(ocn_ctx *c, const float *h, int64_t count)
     return OCN_OK;
 }
 
-static int init_state_entry(ocn_ctx *c)
-{
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    HIPCHK(hipSetDevice(c->dec.device));
-    c->open = false;   // a pending call tail is void: every field is formed again
-    c->open_pair = false;
-    c->deferred = 0;
-    c->ring2_saved = false;   // (a saved second ring of an x2 sequence is void: init forms it again)
-    c->tr_pending = false;
-    c->coherent_known = false;
-    c->alt_ok = false; c->tr_alt_ok = false;
-    c->hn_fresh = false;
-    c->fb_state = kFbUnchecked;
-    // a multi-step launch's barrier timeout not yet reported is void too: the state is formed again
-    if (c->d_nbad) HIPCHK(hipMemsetAsync(c->d_nbad + 61, 0, sizeof(int32_t), c->stream));
-    const int rc = fail_fatal(c, init_state(c));
-    c->hh_consistent = rc == OCN_OK && !c->r8_handed;   // init_data.f90:60-63 ran hh_init last
-    c->hn_fresh = c->hh_consistent && !c->r4_escaped;    // (every level: the n one from h_r)
-    return rc;
-}
-
 int ocn_ctx_init_state(ocn_ctx *c)
 {
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    return guarded(c, "ocn_ctx_init_state", [&] { return init_state_entry(c); });
-}
-
-static int sync_entry(ocn_ctx *c, int field_id)
-{
-    if (!c || !has_r8(c, field_id)) return set_error(OCN_ERR_ARG, "sync: bad ctx or non-real(8) field");
-    HIPCHK(hipSetDevice(c->dec.device));
-    HaloPlan *p;
-    RC(get_plan(c, {field_id}, p));
-    // no neighbour block anywhere (one block, no other rank): the exchange writes nothing, so
-    // nothing the step decisions rest on changes and a pending call tail may stay pending -- a
-    // PSy-style caller syncing between 1-step calls pays no re-check, host wait or tail for it
-    if (!p->local.n && p->peers.empty()) return OCN_OK;
-    RC(complete_open(c));
-    c->coherent_known = false;
-    c->hh_consistent = false;
-    c->hn_fresh = false;
-    c->fb_state = kFbUnchecked;
-    if (field_id == OCN_HHQ_REST) c->hrx_ok = false;
-    // the current buffer's halos change; the one-pass steps' second buffer must be copied again
-    if (is_alt_field(field_id)) c->alt_ok = false;
-    if (is_tracer_field(field_id)) c->tr_alt_ok = false;
-    return run_sync(c, {field_id});
+    return entry(c, __func__, [&]() -> int {
+        HIPCHK(hipSetDevice(c->dec.device));
+        c->open = false;   // a pending call tail is void: every field is formed again
+        c->open_pair = false;
+        c->deferred = 0;
+        c->ring2_saved = false;   // (a saved second ring of an x2 sequence is void: init forms it again)
+        c->tr_pending = false;
+        fields_changed(c, Changed::Init);
+        // a multi-step launch's barrier timeout not yet reported is void too: the state is formed again
+        if (c->d_nbad) HIPCHK(hipMemsetAsync(c->d_nbad + 61, 0, sizeof(int32_t), c->stream));
+        const int rc = fail_fatal(c, init_state(c));
+        c->hh_consistent = rc == OCN_OK && !c->r8_handed;   // init_data.f90:60-63 ran hh_init last
+        c->hn_fresh = c->hh_consistent && !c->r4_escaped;    // (every level: the n one from h_r)
+        return rc;
+    });
 }
 
 int ocn_ctx_sync(ocn_ctx *c, int field_id)
 {
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    return guarded(c, "ocn_ctx_sync", [&] { return sync_entry(c, field_id); });
-}
-
-static int stage_entry(ocn_ctx *c, int stage_id, double tau)
-{
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    HIPCHK(hipSetDevice(c->dec.device));
-    if (stage_id < 0 || stage_id >= OCN_NUM_STAGES) return set_error(OCN_ERR_ARG, "bad stage id");
-    RC(complete_open(c));
-    c->coherent_known = false;
-    c->alt_ok = false; c->tr_alt_ok = false;
-    c->hh_consistent = false;
-    c->hn_fresh = false;
-    c->fb_state = kFbUnchecked;
-    RC(prepare_static(c));
-    return envoke(c, stage_id, tau);
+    return entry(c, __func__, [&]() -> int {
+        if (!has_r8(c, field_id)) return set_error(OCN_ERR_ARG, "sync: bad ctx or non-real(8) field");
+        HIPCHK(hipSetDevice(c->dec.device));
+        HaloPlan *p;
+        RC(get_plan(c, {field_id}, p));
+        // no neighbour block anywhere (one block, no other rank): the exchange writes nothing, so
+        // nothing the step decisions rest on changes and a pending call tail may stay pending -- a
+        // PSy-style caller syncing between 1-step calls pays no re-check, host wait or tail for it
+        if (!p->local.n && p->peers.empty()) return OCN_OK;
+        RC(complete_open(c));
+        fields_changed(c, Changed::Sync, field_id);
+        return run_sync(c, {field_id});
+    });
 }
 
 int ocn_ctx_stage(ocn_ctx *c, int stage_id, double tau)
 {
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    return guarded(c, "ocn_ctx_stage", [&] { return stage_entry(c, stage_id, tau); });
+    return entry(c, __func__, [&]() -> int {
+        HIPCHK(hipSetDevice(c->dec.device));
+        if (stage_id < 0 || stage_id >= OCN_NUM_STAGES) return set_error(OCN_ERR_ARG, "bad stage id");
+        RC(complete_open(c));
+        fields_changed(c, Changed::Stage);
+        RC(prepare_static(c));
+        return envoke(c, stage_id, tau);
+    });
 }
 
 static void drop_graphs(ocn_ctx *c)
@@ -3478,7 +1829,7 @@ static void drop_graphs(ocn_ctx *c)
 }
 
 // one model step (model.f90:146-160): expl_shallow_water, then expl_tracer
-static int run_step(ocn_ctx *c, double tau, const StepKind &k)
+extern "C++" int ocn::run_step(ocn_ctx *c, double tau, const StepKind &k)
 {
     if (c->tr_forked) {   // a tracer step forked beside the previous step's march (one_step_x2)
         RC(join_sync(c));
@@ -3532,21 +1883,16 @@ static int graph_step(ocn_ctx *c, double tau, const StepKind &k)
     return OCN_OK;
 }
 
-static int tracer_stage_entry(ocn_ctx *c, int stage_id, int tracer, double tau)
-{
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    HIPCHK(hipSetDevice(c->dec.device));
-    if (c->sw.use_tracers <= 0 || tracer < 1 || tracer > c->sw.tracer_num)
-        return set_error(OCN_ERR_ARG, "no such tracer (use_tracers / tracer_num)");
-    if (stage_id < 0 || stage_id >= OCN_NUM_TSTAGES) return set_error(OCN_ERR_ARG, "bad tracer stage id");
-    RC(complete_open(c));
-    return tracer_stage(c, stage_id, tracer, tau, false);
-}
-
 int ocn_ctx_tracer_stage(ocn_ctx *c, int stage_id, int tracer, double tau)
 {
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    return guarded(c, "ocn_ctx_tracer_stage", [&] { return tracer_stage_entry(c, stage_id, tracer, tau); });
+    return entry(c, __func__, [&]() -> int {
+        HIPCHK(hipSetDevice(c->dec.device));
+        if (c->sw.use_tracers <= 0 || tracer < 1 || tracer > c->sw.tracer_num)
+            return set_error(OCN_ERR_ARG, "no such tracer (use_tracers / tracer_num)");
+        if (stage_id < 0 || stage_id >= OCN_NUM_TSTAGES) return set_error(OCN_ERR_ARG, "bad tracer stage id");
+        RC(complete_open(c));
+        return tracer_stage(c, stage_id, tracer, tau, false);
+    });
 }
 
 // the current sshp / ubrtrp / vbrtrp (in the second buffers after one-pass steps: role bit 4)
@@ -3554,11 +1900,7 @@ int ocn_ctx_tracer_stage(ocn_ctx *c, int stage_id, int tracer, double tau)
 static int alt_home(ocn_ctx *c)
 {
     if (!(c->role & 4)) return OCN_OK;
-    for (LBlock &b : c->blocks)
-        for (const auto &pr : {std::make_pair(&b.sshp_alt, OCN_SSHP), std::make_pair(&b.up_alt, OCN_UBRTRP),
-                               std::make_pair(&b.vp_alt, OCN_VBRTRP)})
-            HIPCHK(hipMemcpyAsync(*pr.first, b.ptr[field_slot(pr.second)], field_bytes(b), hipMemcpyDeviceToDevice,
-                                  c->stream));
+    RC(copy_to_alt(c, 3, false));
     swap_alt3(c);
     return OCN_OK;
 }
@@ -3609,7 +1951,7 @@ static int prepare_kc(ocn_ctx *c, bool x2 = false)
         for (const LBlock &b : c->blocks) {
             std::vector<void *> tab = b.ptr;
             if (x2) tab[field_slot(OCN_HHQ_REST)] = b.hr_x;
-            const Range r = x2 ? Range{b.g.nx_start, b.g.nx_end, b.g.ny_start, b.g.ny_end} : onepass_inner(b, 1);
+            const Range r = x2 ? Range{b.g.nx_start, b.g.nx_end, b.g.ny_start, b.g.ny_end} : inner_range(b, 1, 1);
             RC(launch_fallback_check(&b.g, tab.data(), b.bits, r, c->d_fbz, b.kc, c->stream, x2 ? b.own : 0u));
         }
         if (!c->capturing) {   // the verdict to pinned host memory, learn_fb_async
@@ -3626,7 +1968,7 @@ static int prepare_kc(ocn_ctx *c, bool x2 = false)
 
 // The end of a call that leaves no step pending: nothing stays in flight, the pairs' roles return
 // (the last step left both buffers of each pair equal), the recompute steps' sshp comes home
-static int finish_call(ocn_ctx *c, int rc)
+extern "C++" int ocn::finish_call(ocn_ctx *c, int rc)
 {
     if (const int rj = join_sync(c); rc == OCN_OK) rc = rj;
     // a failed call drops its sequence: a saved second halo ring (x2 steps) must not be restored
@@ -3634,9 +1976,7 @@ static int finish_call(ocn_ctx *c, int rc)
     if (rc != OCN_OK) c->ring2_saved = false;
     if (c->role & 1) swap_roles(c);
     if (c->role & 2) {   // sshp's buffers are not equal: the current one is copied into the field's own buffer
-        for (LBlock &b : c->blocks)
-            HIPCHK(hipMemcpyAsync(b.sshp_alt, b.ptr[field_slot(OCN_SSHP)], field_bytes(b), hipMemcpyDeviceToDevice,
-                                  c->stream));
+        RC(copy_to_alt(c, 1, false));
         swap_sshp(c);
     }
     // one-pass steps: sshp / ubrtrp / vbrtrp stay in the second buffers (every access goes through
@@ -3647,10 +1987,7 @@ static int finish_call(ocn_ctx *c, int rc)
     // the roles return with no copy; the current ff1p is copied into the field's own buffer
     if (c->role & 8) swap_tracer_roles(c);
     if (c->role & 16) {
-        for (LBlock &b : c->blocks)
-            for (int t = 1; t <= c->sw.tracer_num; ++t)
-                HIPCHK(hipMemcpyAsync(b.ffp_alt[(size_t)t - 1], b.ptr[field_slot(OCN_FF1P(t))], field_bytes(b),
-                                      hipMemcpyDeviceToDevice, c->stream));
+        RC(copy_to_alt(c, 0, true));
         swap_tracer_alt(c);
     }
     c->tr_pending = false;
@@ -3729,12 +2066,59 @@ static int await_kc(ocn_ctx *c, bool x2, int nsteps)
     return OCN_OK;
 }
 
+// The step kinds of an open sequence and of the tail that ends one (a call's first steps are set up
+// one by one in step_impl's main loop).
+// A continuing one-pass step: nothing around its launch, the next step is one too
+static StepKind continuing_step(bool check, bool x2)
+{
+    StepKind k{};
+    k.check = check;
+    k.flip = k.one = k.next_one = k.a_done = true;
+    k.x2 = x2;   // (an x2 sequence: one_step_x2, as a pair one_step_x4)
+    return k;
+}
+// two of them as one launch (one_step_pair, one_step_x4)
+static StepKind continuing_pair(bool check, bool check2, bool x2)
+{
+    StepKind k = continuing_step(check, x2);
+    k.pair = true;
+    k.check2 = check2;
+    return k;
+}
+// nsteps of them as one launch (one_step_multi), each checked if check
+static StepKind multi_step(bool check, int nsteps)
+{
+    StepKind k = continuing_step(check, false);
+    k.multi = nsteps;
+    return k;
+}
+// The call's last step after one-pass steps.  It ends a sequence of x2 steps: the saved second ring is
+// restored and the first exchanged before it (x2_end), here and nowhere else
+static StepKind last_step(ocn_ctx *c, bool check)
+{
+    StepKind k{};
+    k.last = k.one_last = true;
+    k.check = check;
+    k.x2_end = c->ring2_saved;
+    c->ring2_saved = false;
+    return k;
+}
+// a one-pass step and the last step as one launch (one_step_pair with LAST: one block, no exchange)
+static StepKind last_pair(bool check, bool check2)
+{
+    StepKind k{};
+    k.last = k.one_last = k.pair = true;
+    k.check = check;
+    k.check2 = check2;
+    return k;
+}
+
 // The pending tail of an open sequence: the last step run (a one-pass step) is run again from the
 // previous state -- untouched in the other buffer of each pair and the other sshp / ubrtrp / vbrtrp
 // buffers -- as the call's last step (one_step_last: the same new state bit for bit, plus vort,
 // the stresses, the RHS terms, a8's copies and hh_init with every level).  Its check_ssh_err
 // count was taken the first time.
-static int complete_open(ocn_ctx *c)
+extern "C++" int ocn::complete_open(ocn_ctx *c)
 {
     if (!c->open) return OCN_OK;
     c->open = false;
@@ -3743,48 +2127,25 @@ static int complete_open(ocn_ctx *c)
         const int d = c->deferred;
         c->deferred = 0;
         c->open_pair = false;
-        if (d == 2 && pair_ok(c)) {   // both in one launch, the second as the last step (pair + LAST)
-            StepKind k{};
-            k.last = k.one_last = k.pair = true;
-            k.check = c->deferred_check[0];
-            k.check2 = c->deferred_check[1];
-            return finish_call(c, run_step(c, c->open_tau, k));
-        }
-        if (d == 2) {
-            StepKind k1{};
-            k1.check = c->deferred_check[0];
-            k1.flip = k1.one = k1.next_one = k1.a_done = true;
-            k1.x2 = c->open_x2;   // (x2 sequences with pairs of x2 steps: one_step_x4 deferred it)
+        if (d == 2 && pair_ok(c))   // both in one launch, the second as the last step (pair + LAST)
+            return finish_call(c, run_step(c, c->open_tau, last_pair(c->deferred_check[0], c->deferred_check[1])));
+        if (d == 2) {   // (x2 sequences with pairs of x2 steps: one_step_x4 deferred it)
+            const StepKind k1 = continuing_step(c->deferred_check[0], c->open_x2);
             if (const int rc = run_step(c, c->open_tau, k1)) return finish_call(c, rc);
         }
-        StepKind k{};
-        k.last = k.one_last = true;
-        k.check = c->deferred_check[d - 1];
-        k.x2_end = c->ring2_saved;
-        c->ring2_saved = false;
-        return finish_call(c, run_step(c, c->open_tau, k));
+        return finish_call(c, run_step(c, c->open_tau, last_step(c, c->deferred_check[d - 1])));
     }
     swap_roles(c);
     swap_alt3(c);
     c->tr_pending = false;   // (the tracer step of the state before the last step has run)
     if (c->open_pair) {   // the last launch was a pair (one flip, two steps): both again, from the state
         c->open_pair = false;   // before it, the second as the last step (counted the first time: no checks)
-        if (pair_ok(c)) {
-            StepKind k{};
-            k.last = k.one_last = k.pair = true;
-            return finish_call(c, run_step(c, c->open_tau, k));
-        }
-        StepKind k1{};
-        k1.flip = k1.one = k1.next_one = k1.a_done = true;
-        k1.x2 = c->open_x2;   // (a pair of x2 steps: its first step again, one_step_x2)
-        if (const int rc = run_step(c, c->open_tau, k1)) return finish_call(c, rc);
+        if (pair_ok(c)) return finish_call(c, run_step(c, c->open_tau, last_pair(false, false)));
+        // (a pair of x2 steps: its first step again, one_step_x2)
+        if (const int rc = run_step(c, c->open_tau, continuing_step(false, c->open_x2))) return finish_call(c, rc);
         c->tr_pending = false;   // (tracer runs: the pair ran the tracer step of that state too)
     }
-    StepKind k{};
-    k.last = k.one_last = true;
-    k.x2_end = c->ring2_saved;   // x2 steps: the second ring restored, the first exchanged (x2_end)
-    c->ring2_saved = false;
-    return finish_call(c, run_step(c, c->open_tau, k));
+    return finish_call(c, run_step(c, c->open_tau, last_step(c, false)));
 }
 
 static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every)
@@ -3814,11 +2175,7 @@ static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every
                 c->deferred = 0;
                 size_t i = 0;
                 for (; i + 2 < chk.size() && rc == OCN_OK; i += 2) {
-                    StepKind k{};
-                    k.check = chk[i];
-                    k.check2 = chk[i + 1];
-                    k.flip = k.one = k.next_one = k.a_done = k.pair = true;
-                    k.x2 = c->open_x2;
+                    const StepKind k = continuing_pair(chk[i], chk[i + 1], c->open_x2);
                     rc = graph_ok ? graph_step(c, tau, k) : run_step(c, tau, k);
                     c->open_pair = c->pair_used = true;
                 }
@@ -3827,19 +2184,11 @@ static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every
                     for (int j = 0; j < c->deferred; ++j) c->deferred_check[j] = chk[i + j];
                 }
             } else {
-                for (int j = 0; j < c->deferred && rc == OCN_OK; ++j) {   // (no pairs now: deferred steps first)
-                    StepKind k{};
-                    k.check = c->deferred_check[j];
-                    k.flip = k.one = k.next_one = k.a_done = true;
-                    k.x2 = c->open_x2;
-                    rc = run_step(c, tau, k);
-                }
+                for (int j = 0; j < c->deferred && rc == OCN_OK; ++j)   // (no pairs now: deferred steps first)
+                    rc = run_step(c, tau, continuing_step(c->deferred_check[j], c->open_x2));
                 c->deferred = 0;
                 if (!c->open_x2 && !graph_ok && nsteps >= 2 && rc == OCN_OK && multi_ok(c, check_every)) {
-                    StepKind k{};   // all the call's steps in one launch
-                    k.check = check_every == 1;
-                    k.flip = k.one = k.next_one = k.a_done = true;
-                    k.multi = nsteps;
+                    const StepKind k = multi_step(check_every == 1, nsteps);   // all the call's steps in one launch
                     // (inside ocn_ens_step: planned here, issued with the other members' launches)
                     if (c->ens_collect) { c->ens_k = k; c->ens_pending = true; }
                     else rc = run_step(c, tau, k);
@@ -3847,10 +2196,7 @@ static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every
                     c->multi_used = true;
                 } else {
                     for (int s = 1; s <= nsteps && rc == OCN_OK; ++s) {
-                        StepKind k{};
-                        k.check = check_every > 0 && (s % check_every == 0);
-                        k.flip = k.one = k.next_one = k.a_done = true;
-                        k.x2 = c->open_x2;
+                        const StepKind k = continuing_step(check_every > 0 && (s % check_every == 0), c->open_x2);
                         rc = graph_ok ? graph_step(c, tau, k) : run_step(c, tau, k);
                         c->open_pair = false;
                     }
@@ -3911,10 +2257,7 @@ static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every
     c->tr_call = c->sw.use_tracers > 0 && one_call;
     c->tr_pending = false;
     if (c->tr_call && !c->tr_alt_ok) {   // the second ff1p buffers start as copies
-        for (const LBlock &b : c->blocks)
-            for (int t = 1; t <= c->sw.tracer_num; ++t)
-                HIPCHK(hipMemcpyAsync(b.ffp_alt[(size_t)t - 1], b.ptr[field_slot(OCN_FF1P(t))], field_bytes(b),
-                                      hipMemcpyDeviceToDevice, c->stream));
+        RC(copy_to_alt(c, 0, true));
         c->tr_alt_ok = true;
     }
     c->hh_consistent = false;   // until this call's last step has run
@@ -3934,21 +2277,11 @@ static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every
     const bool rc_call = ca && c->recompute && !one_call;
     if (rc_call) c->alt_ok = false;
     if (one_call && !c->alt_ok) {   // the second buffers start as copies (they agree outside a8's write set)
-        for (const LBlock &b : c->blocks) {
-            HIPCHK(hipMemcpyAsync(b.sshp_alt, b.ptr[field_slot(OCN_SSHP)], field_bytes(b), hipMemcpyDeviceToDevice,
-                                  c->stream));
-            HIPCHK(hipMemcpyAsync(b.up_alt, b.ptr[field_slot(OCN_UBRTRP)], field_bytes(b), hipMemcpyDeviceToDevice,
-                                  c->stream));
-            HIPCHK(hipMemcpyAsync(b.vp_alt, b.ptr[field_slot(OCN_VBRTRP)], field_bytes(b), hipMemcpyDeviceToDevice,
-                                  c->stream));
-        }
+        RC(copy_to_alt(c, 3, false));
         c->alt_ok = true;
     }
     c->rc_used = rc_call && N >= 3;
-    if (rc_call)   // the second sshp buffer starts as a copy: the two agree outside a8's write set
-        for (const LBlock &b : c->blocks)
-            HIPCHK(hipMemcpyAsync(b.sshp_alt, b.ptr[field_slot(OCN_SSHP)], field_bytes(b), hipMemcpyDeviceToDevice,
-                                  c->stream));
+    if (rc_call) RC(copy_to_alt(c, 1, false));   // the second sshp buffer starts as a copy: the two agree outside a8's write set
     RC(join_sync(c));
     // two one-pass steps per launch where both are plain one-pass steps and the second is not the
     // last one run (a lazy tail redoes that one from the state before it, which a pair never writes)
@@ -4002,9 +2335,9 @@ static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every
     return finish_call(c, rc);
 }
 
-static int step_entry(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every)
+// ocn_ctx_step's call (ocn_ens_step makes it for every member, under its own name)
+extern "C++" int ocn::step_entry(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every)
 {
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
     // (a usage error before any collective: no peer waits on this rank yet, the communicator stays)
     if (!c->initialized) return set_error(OCN_ERR_STATE, "ocn_ctx_init_state not called");
     return fail_fatal(c, step_impl(c, tau, nsteps, check_every));
@@ -4012,20 +2345,12 @@ static int step_entry(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_ever
 
 int ocn_ctx_step(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every)
 {
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    return guarded(c, "ocn_ctx_step", [&] { return step_entry(c, tau, nsteps, check_every); });
-}
-
-static int complete_entry(ocn_ctx *c)
-{
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    return complete_open(c);
+    return entry(c, __func__, [&] { return step_entry(c, tau, nsteps, check_every); });
 }
 
 int ocn_ctx_complete(ocn_ctx *c)
 {
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    return guarded(c, "ocn_ctx_complete", [&] { return complete_entry(c); });
+    return entry(c, __func__, [&] { return complete_open(c); });
 }
 
 // The steps an open sequence deferred (ocn_ctx_step leaves up to two requested steps not yet
@@ -4034,12 +2359,9 @@ int ocn_ctx_complete(ocn_ctx *c)
 static int run_deferred(ocn_ctx *c)
 {
     if (!c->open || !c->deferred) return OCN_OK;
-    StepKind k{};
-    k.check = c->deferred_check[0];
-    k.flip = k.one = k.next_one = k.a_done = true;
-    k.pair = c->deferred == 2;   // (a pair only where pairs ran: pair_ok / x4_now held when they were deferred)
-    k.check2 = k.pair && c->deferred_check[1];
-    k.x2 = c->open_x2;
+    // (a pair only where pairs ran: pair_ok / x4_now held when they were deferred)
+    const StepKind k = c->deferred == 2 ? continuing_pair(c->deferred_check[0], c->deferred_check[1], c->open_x2)
+                                        : continuing_step(c->deferred_check[0], c->open_x2);
     c->open_pair = k.pair;
     c->deferred = 0;
     if (const int rc = run_step(c, c->open_tau, k)) { c->open = false; return finish_call(c, rc); }
@@ -4077,16 +2399,9 @@ static int sync_impl(ocn_ctx *c)
     return OCN_OK;
 }
 
-static int synchronize_entry(ocn_ctx *c)
-{
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    return fail_fatal(c, sync_impl(c));
-}
-
 int ocn_ctx_synchronize(ocn_ctx *c)
 {
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    return guarded(c, "ocn_ctx_synchronize", [&] { return synchronize_entry(c); });
+    return entry(c, __func__, [&] { return fail_fatal(c, sync_impl(c)); });
 }
 
 int ocn_ctx_stage_times(ocn_ctx *c, double *ms, int64_t *counts) { return ocn_ctx_stage_stats(c, ms, counts, nullptr); }
@@ -4120,87 +2435,67 @@ int ocn_ctx_stage_stats(ocn_ctx *c, double *ms, int64_t *counts, double *ms_max)
     return OCN_OK;
 }
 
-static int download_entry(ocn_ctx *c, int k, int id, void *host)
-{
-    if (!c || !host || k < 0 || k >= (int)c->blocks.size() || !has_field(c, id))
-        return set_error(OCN_ERR_ARG, "download: bad argument");
-    HIPCHK(hipSetDevice(c->dec.device));
-    RC(complete_open(c));
-    const LBlock &b = c->blocks[k];
-    const size_t es = is_r4(id) ? 4 : 8;
-    const size_t w = (size_t)(b.g.bnd_x2 - b.g.bnd_x1 + 1), rows = (size_t)(b.g.bnd_y2 - b.g.bnd_y1 + 1);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    learn_fb(c);
-    HIPCHK(hipMemcpy2D(host, w * es, b.ptr[field_slot(id)], (size_t)b.g.pitch * es, w * es, rows,
-                       hipMemcpyDeviceToHost));
-    return OCN_OK;
-}
-
 int ocn_ctx_download(ocn_ctx *c, int k, int id, void *host)
 {
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    return guarded(c, "ocn_ctx_download", [&] { return download_entry(c, k, id, host); });
-}
-
-static int output_r4_entry(ocn_ctx *c, int k, int id, float undef, float *host)
-{
-    if (!c || !host || k < 0 || k >= (int)c->blocks.size() || !has_field(c, id))
-        return set_error(OCN_ERR_ARG, "output_r4: bad argument");
-    HIPCHK(hipSetDevice(c->dec.device));
-    RC(complete_open(c));
-    const LBlock &b = c->blocks[k];
-    const int w = b.g.nx_end - b.g.nx_start + 1, h = b.g.ny_end - b.g.ny_start + 1;
-    if (w <= 0 || h <= 0) return OCN_OK;
-    const long off = (long)(b.g.ny_start - b.g.bnd_y1) * b.g.pitch + (b.g.nx_start - b.g.bnd_x1);
-    float *d = nullptr;
-    HIPCHK(hipMallocAsync((void **)&d, (size_t)w * h * sizeof(float), c->stream));
-    const float *lu = b.f<float>(OCN_LU) + off;
-    const dim3 grid((unsigned)((w + 255) / 256), (unsigned)h);
-    if (is_r4(id))
-        hipLaunchKernelGGL(k_output_r4<float>, grid, dim3(256), 0, c->stream, b.f<float>(id) + off, lu,
-                           (long)b.g.pitch, w, h, undef, d);
-    else
-        hipLaunchKernelGGL(k_output_r4<double>, grid, dim3(256), 0, c->stream, b.f<double>(id) + off, lu,
-                           (long)b.g.pitch, w, h, undef, d);
-    int rc = check_launch();
-    if (rc == OCN_OK && hipMemcpyAsync(host, d, (size_t)w * h * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-        rc = set_error(OCN_ERR_HIP, "output_r4: copy");
-    (void)hipFreeAsync(d, c->stream);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    learn_fb(c);
-    return rc;
+    return entry(c, __func__, [&]() -> int {
+        if (!host || k < 0 || k >= (int)c->blocks.size() || !has_field(c, id))
+            return set_error(OCN_ERR_ARG, "download: bad argument");
+        HIPCHK(hipSetDevice(c->dec.device));
+        RC(complete_open(c));
+        const LBlock &b = c->blocks[k];
+        const size_t es = is_r4(id) ? 4 : 8;
+        const size_t w = (size_t)(b.g.bnd_x2 - b.g.bnd_x1 + 1), rows = (size_t)(b.g.bnd_y2 - b.g.bnd_y1 + 1);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        learn_fb(c);
+        HIPCHK(hipMemcpy2D(host, w * es, b.ptr[field_slot(id)], (size_t)b.g.pitch * es, w * es, rows,
+                           hipMemcpyDeviceToHost));
+        return OCN_OK;
+    });
 }
 
 int ocn_ctx_output_r4(ocn_ctx *c, int k, int id, float undef, float *host)
 {
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    return guarded(c, "ocn_ctx_output_r4", [&] { return output_r4_entry(c, k, id, undef, host); });
-}
-
-static int upload_entry(ocn_ctx *c, int k, int id, const void *host)
-{
-    if (!c || !host || k < 0 || k >= (int)c->blocks.size() || !has_field(c, id))
-        return set_error(OCN_ERR_ARG, "upload: bad argument");
-    HIPCHK(hipSetDevice(c->dec.device));
-    RC(complete_open(c));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (is_r4(id)) { c->static_dirty = true; c->ext_ok = false; }
-    // (the x2 checks also cover sshp / ubrtrp / vbrtrp and h_r: check_coherence)
-    if (is_flip_field(id) || is_alt_field(id) || id == OCN_HHQ_REST || id == OCN_MU) c->coherent_known = false;
-    if (is_alt_field(id)) c->alt_ok = false;
-    if (is_tracer_field(id)) c->tr_alt_ok = false;
-    if (id == OCN_HHQ_REST) c->hrx_ok = false;
-    if (id == OCN_HHQ_REST || id == OCN_HHQ_N) c->hqn_stale = true;
-    c->hh_consistent = false;
-    c->hn_fresh = false;
-    c->fb_state = kFbUnchecked;
-    return upload_field(c, c->blocks[k], id, host, false);
+    return entry(c, __func__, [&]() -> int {
+        if (!host || k < 0 || k >= (int)c->blocks.size() || !has_field(c, id))
+            return set_error(OCN_ERR_ARG, "output_r4: bad argument");
+        HIPCHK(hipSetDevice(c->dec.device));
+        RC(complete_open(c));
+        const LBlock &b = c->blocks[k];
+        const int w = b.g.nx_end - b.g.nx_start + 1, h = b.g.ny_end - b.g.ny_start + 1;
+        if (w <= 0 || h <= 0) return OCN_OK;
+        const long off = (long)(b.g.ny_start - b.g.bnd_y1) * b.g.pitch + (b.g.nx_start - b.g.bnd_x1);
+        float *d = nullptr;
+        HIPCHK(hipMallocAsync((void **)&d, (size_t)w * h * sizeof(float), c->stream));
+        const float *lu = b.f<float>(OCN_LU) + off;
+        const dim3 grid((unsigned)((w + 255) / 256), (unsigned)h);
+        if (is_r4(id))
+            hipLaunchKernelGGL(k_output_r4<float>, grid, dim3(256), 0, c->stream, b.f<float>(id) + off, lu,
+                               (long)b.g.pitch, w, h, undef, d);
+        else
+            hipLaunchKernelGGL(k_output_r4<double>, grid, dim3(256), 0, c->stream, b.f<double>(id) + off, lu,
+                               (long)b.g.pitch, w, h, undef, d);
+        int rc = check_launch();
+        if (rc == OCN_OK && hipMemcpyAsync(host, d, (size_t)w * h * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            rc = set_error(OCN_ERR_HIP, "output_r4: copy");
+        (void)hipFreeAsync(d, c->stream);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        learn_fb(c);
+        return rc;
+    });
 }
 
 int ocn_ctx_upload(ocn_ctx *c, int k, int id, const void *host)
 {
-    if (!c) return set_error(OCN_ERR_ARG, "null ctx");
-    return guarded(c, "ocn_ctx_upload", [&] { return upload_entry(c, k, id, host); });
+    return entry(c, __func__, [&]() -> int {
+        if (!host || k < 0 || k >= (int)c->blocks.size() || !has_field(c, id))
+            return set_error(OCN_ERR_ARG, "upload: bad argument");
+        HIPCHK(hipSetDevice(c->dec.device));
+        RC(complete_open(c));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (is_r4(id)) { c->static_dirty = true; c->ext_ok = false; }
+        fields_changed(c, Changed::Upload, id);
+        return upload_field(c, c->blocks[k], id, host, false);
+    });
 }
 
 int ocn_ctx_set_option(ocn_ctx *c, int32_t key, int64_t value)
@@ -4305,439 +2600,6 @@ int ocn_ctx_get_option(const ocn_ctx *c, int32_t key, int64_t *value)
     case OCN_OPT_XCHG_DELAY: *value = c->xdelay_us; return OCN_OK;
     default: return set_error(OCN_ERR_ARG, "unknown option");
     }
-}
-
-// ------------------------------------------------------------------ ensembles (ocn_sw.h)
-struct ocn_ens {
-    std::vector<ocn_ctx *> m;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    unsigned *d_bar = nullptr;     // kMultiBarBytes of barrier words per member
-    void *d_tab = nullptr;         // the launches' member table (sw_kernels.hip EnsEntry), tab_bytes
-    size_t tab_bytes = 0;
-    // the table's pinned host copies: a call's launches fill disjoint parts of one, the next call takes
-    // the other; ev[i]: the stream has read copy i (awaited before it is written again)
-    void *h_tab[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool ev_set[2] = {false, false};
-    int slot = 0;
-    int64_t cap_opt = 0;           // OCN_ENS_OPT_CAPACITY (0: none)
-    int64_t max_group = 0;         // OCN_ENS_OPT_MAX_GROUP (0: none)
-    ocn_ens_info_t last{};
-    // ocn_ens_stats: per local block, one buffer per statistic (mean, variance, spread, minimum, maximum)
-    // based like the members' arrays (raw: the allocations, made at first use), and the statistics the
-    // last call on that block formed (OCN_ENS_STAT_* bits)
-    struct Stats { void *raw[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-                   double *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; int formed = 0; };
-    std::vector<Stats> stats;
-    // ocn_ens_extrema: the blocks' interiors, the members' (field, lu) table, the per-tile partials and
-    // the results, in one device allocation made at first use; h_ext: the tables and the results in pinned host memory
-    void *d_ext = nullptr, *h_ext = nullptr;
-};
-
-// ocn_ens_plan's policy: ocn_ens_plan.h (pure host code, also built stand-alone)
-static int ens_plan(const ocn_block *g, const int32_t *variant, int members, int64_t capacity,
-                    std::vector<ocn_ens_group> &out)
-{
-    const char *err = nullptr;
-    const int rc = ens_plan_groups(g, variant, members, capacity, out, &err);
-    return rc ? set_error(rc, std::string("ensemble plan: ") + err) : OCN_OK;
-}
-
-int ocn_ens_plan(const ocn_block *geom, const int32_t *variant, int32_t members, int64_t capacity, ocn_ens_group *out,
-                 int32_t cap, int32_t *count)
-{
-    std::vector<ocn_ens_group> gs;
-    RC(ens_plan(geom, variant, members, capacity, gs));
-    if (count) *count = (int32_t)gs.size();
-    for (size_t i = 0; i < gs.size() && (int32_t)i < cap && out; ++i) out[i] = gs[i];
-    return OCN_OK;
-}
-
-int ocn_ens_destroy(ocn_ens *e)
-{
-    if (!e) return OCN_OK;
-    (void)hipSetDevice(e->device);
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (ocn_ctx *c : e->m) (void)ctx_destroy(c);
-    for (int i = 0; i < 2; ++i) {
-        if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
-        if (e->h_tab[i]) (void)hipHostFree(e->h_tab[i]);
-    }
-    if (e->d_tab) (void)hipFree(e->d_tab);
-    if (e->d_bar) (void)hipFree(e->d_bar);
-    for (ocn_ens::Stats &q : e->stats)
-        for (void *r : q.raw)
-            if (r) (void)hipFree(r);
-    if (e->d_ext) (void)hipFree(e->d_ext);
-    if (e->h_ext) (void)hipHostFree(e->h_ext);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
-    return OCN_OK;
-}
-
-int ocn_ens_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_decomp *dec, const int32_t *mask,
-                   int32_t members, ocn_ens **out)
-{
-    if (!basin || !sw || !dec || !out) return set_error(OCN_ERR_ARG, "null argument");
-    if (members < 1 || members > OCN_ENS_MAX_MEMBERS)
-        return set_error(OCN_ERR_ARG, "ensemble: 1.." + std::to_string(OCN_ENS_MAX_MEMBERS) + " members");
-    if (dec->nranks != 1) return set_error(OCN_ERR_ARG, "ensemble: one rank (dec->nranks = 1)");
-    ocn_ens *e = new ocn_ens();
-    e->device = dec->device;
-    int rc = check_hip(hipSetDevice(dec->device), "hipSetDevice");
-    if (!rc) rc = check_hip(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate");
-    for (int i = 0; i < members && !rc; ++i) {
-        ocn_ctx *c = nullptr;
-        rc = ctx_create(basin, sw, dec, mask, e->stream, e, &c);
-        if (!rc) e->m.push_back(c);
-    }
-    e->tab_bytes = (size_t)members * onepass_multi_b_entry_bytes();
-    if (!rc) rc = check_hip(hipMalloc((void **)&e->d_bar, (size_t)members * kMultiBarBytes), "hipMalloc");
-    if (!rc) rc = check_hip(hipMalloc(&e->d_tab, e->tab_bytes), "hipMalloc");
-    for (int i = 0; i < 2 && !rc; ++i) {
-        rc = check_hip(hipHostMalloc(&e->h_tab[i], e->tab_bytes, hipHostMallocDefault), "hipHostMalloc");
-        if (!rc) rc = check_hip(hipEventCreateWithFlags(&e->ev[i], hipEventDisableTiming), "hipEventCreate");
-    }
-    if (rc) { ocn_ens_destroy(e); return rc; }
-    e->last.members = members;
-    *out = e;
-    return OCN_OK;
-}
-
-int ocn_ens_size(const ocn_ens *e) { return e ? (int)e->m.size() : -1; }
-
-int ocn_ens_member(ocn_ens *e, int32_t i, ocn_ctx **out)
-{
-    if (!e || !out || i < 0 || i >= (int32_t)e->m.size()) return set_error(OCN_ERR_ARG, "ensemble: bad member index");
-    *out = e->m[(size_t)i];
-    return OCN_OK;
-}
-
-int ocn_ens_init_state(ocn_ens *e)
-{
-    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
-    for (ocn_ctx *c : e->m) RC(ocn_ctx_init_state(c));
-    return OCN_OK;
-}
-
-int ocn_ens_complete(ocn_ens *e)
-{
-    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
-    int first = OCN_OK;
-    for (ocn_ctx *c : e->m)
-        if (const int rc = ocn_ctx_complete(c); rc && !first) first = rc;
-    return first;
-}
-
-static int64_t ens_capacity(const ocn_ens *e)
-{
-    const int64_t dev = onepass_multi_b_capacity();
-    return e->cap_opt > 0 ? std::min(dev, e->cap_opt) : dev;
-}
-
-// a member's planned multi-step launch did not go out: its call fails as step_impl's would
-static int ens_fail(ocn_ctx *c, int rc)
-{
-    c->open = false; c->deferred = 0; c->open_pair = false;
-    return fail_fatal(c, finish_call(c, rc));
-}
-
-int ocn_ens_step(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every)
-{
-    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
-    const int M = (int)e->m.size();
-    e->last = ocn_ens_info_t{};
-    e->last.members = M;
-    int first = OCN_OK;
-    auto note = [&](int rc) { if (rc && !first) first = rc; };
-    // every member plans its call as ocn_ctx_step does and runs whatever is not a multi-step launch
-    std::vector<int32_t> variant((size_t)M, -1);
-    for (int i = 0; i < M; ++i) {
-        ocn_ctx *c = e->m[(size_t)i];
-        c->ens_pending = false;
-        c->ens_collect = true;
-        note(guarded(c, "ocn_ens_step", [&] { return step_entry(c, tau, nsteps, check_every); }));
-        c->ens_collect = false;
-        // (batched: the library's fused path with the sw switches the launch needs; else its own launch)
-        if (c->ens_pending && c->fused && c->sw.full_free_surface == 1 && c->sw.trans_terms > 0 && c->sw.ksw_lat > 0)
-            variant[(size_t)i] = onepass_multi_variant(c->kc_mode, tau, c->ens_k.check);
-    }
-    HIPCHK(hipSetDevice(e->device));
-    e->last.capacity = ens_capacity(e);
-    std::vector<ocn_ens_group> groups;
-    if (e->last.capacity >= 1 && e->max_group < 1) {
-        note(ens_plan(&e->m[0]->blocks[0].g, variant.data(), M, e->last.capacity, groups));
-    } else if (e->last.capacity >= 1) {   // OCN_ENS_OPT_MAX_GROUP: the plan of every max_group planned members
-        std::vector<ocn_ens_group> part;
-        std::vector<int32_t> v((size_t)M, -1);
-        int n = 0;
-        for (int i = 0; i < M; ++i) {
-            if (variant[(size_t)i] >= 0) { v[(size_t)i] = variant[(size_t)i]; ++n; }
-            if (n && (n == e->max_group || i == M - 1)) {
-                note(ens_plan(&e->m[0]->blocks[0].g, v.data(), M, e->last.capacity, part));
-                groups.insert(groups.end(), part.begin(), part.end());
-                std::fill(v.begin(), v.end(), -1);
-                n = 0;
-            }
-        }
-    }
-    std::vector<char> done((size_t)M, 0);
-    if (!groups.empty()) {
-        const int sl = e->slot;
-        e->slot ^= 1;
-        if (e->ev_set[sl]) HIPCHK(hipEventSynchronize(e->ev[sl]));
-        HIPCHK(hipMemsetAsync(e->d_bar, 0, (size_t)M * kMultiBarBytes, e->stream));
-        const size_t eb = onepass_multi_b_entry_bytes();
-        size_t off = 0;
-        for (const ocn_ens_group &q : groups) {
-            std::vector<Compact> cps((size_t)q.members);
-            std::vector<EnsMember> ms((size_t)q.members);
-            std::vector<ocn_ctx::Rec> recs((size_t)q.members);
-            int rc = OCN_OK;
-            for (int j = 0; j < q.members; ++j) {
-                ocn_ctx *c = e->m[(size_t)q.member[j]];
-                const LBlock &b = c->blocks[0];
-                cps[(size_t)j] = Compact{b.bits, b.rows, c->march};
-                const OnepassKC kc = kc_of(c, b);
-                ms[(size_t)j] = EnsMember{&b.g, b.ptr.data(), (int)b.ptr.size(), &cps[(size_t)j],
-                                          c->ens_k.check ? c->d_nbad : nullptr,
-                                          {(double *)b.sshp_alt, (double *)b.up_alt, (double *)b.vp_alt},
-                                          e->d_bar + (size_t)q.member[j] * (kMultiBarBytes / sizeof(unsigned)),
-                                          c->d_nbad + 61, kc.kc, c->multi_spin};
-                if (!c->fused) c->hn_fresh = false;
-                if (!rc) rc = timer_begin(c, OCN_TIMER_ONEPASS_MULTI, recs[(size_t)j]);
-            }
-            if (!rc)
-                rc = launch_onepass_multi_b(ms.data(), q.members, q.variant, q.rows, e->m[(size_t)q.member[0]]->sw, tau,
-                                            nsteps, e->d_tab, (char *)e->h_tab[sl] + off, eb * (size_t)q.members,
-                                            (long)e->last.capacity, e->stream);
-            off += eb * (size_t)q.members;
-            for (int j = 0; j < q.members; ++j) {
-                ocn_ctx *c = e->m[(size_t)q.member[j]];
-                done[(size_t)q.member[j]] = 1;
-                c->ens_pending = false;
-                if (!rc) {   // the host side of one_step_multi
-                    const int rt = timer_end(c, recs[(size_t)j]);
-                    if (c->ens_k.multi & 1) {
-                        swap_alt3(c);
-                        swap_roles(c);
-                    }
-                    if (rt) note(ens_fail(c, rt));
-                } else {
-                    note(ens_fail(c, rc));
-                }
-            }
-            if (!rc) {
-                ++e->last.groups;
-                e->last.batched += q.members;
-                if (q.members > e->last.max_group) {
-                    e->last.max_group = q.members; e->last.rows = q.rows; e->last.tiles = q.tiles;
-                }
-            }
-        }
-        HIPCHK(hipEventRecord(e->ev[sl], e->stream));
-        e->ev_set[sl] = true;
-    }
-    // planned members in no group (no variant the launch takes, or too many tiles for the capacity in
-    // effect): their own multi-step launch, as ocn_ctx_step issues it
-    for (int i = 0; i < M; ++i) {
-        ocn_ctx *c = e->m[(size_t)i];
-        if (!c->ens_pending || done[(size_t)i]) continue;
-        c->ens_pending = false;
-        if (const int rc = run_step(c, tau, c->ens_k)) note(ens_fail(c, rc));
-    }
-    return first;
-}
-
-int ocn_ens_synchronize(ocn_ens *e, int32_t *status)
-{
-    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
-    int first = OCN_OK;
-    std::string msg;
-    for (size_t i = 0; i < e->m.size(); ++i) {   // (the first member's wait is the wait: one stream)
-        const int rc = ocn_ctx_synchronize(e->m[i]);
-        if (status) status[i] = rc;
-        if (rc && !first) { first = rc; msg = "member " + std::to_string(i) + ": " + ocn_last_error(); }
-    }
-    return first ? set_error(first, msg) : OCN_OK;
-}
-
-int ocn_ens_info(ocn_ens *e, ocn_ens_info_t *out)
-{
-    if (!e || !out) return set_error(OCN_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(e->device));
-    *out = e->last;
-    out->members = (int32_t)e->m.size();
-    out->capacity = ens_capacity(e);
-    return OCN_OK;
-}
-
-int ocn_ens_set_option(ocn_ens *e, int32_t key, int64_t value)
-{
-    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
-    switch (key) {
-    case OCN_ENS_OPT_CAPACITY:
-        if (value < 0) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_CAPACITY: >= 0");
-        e->cap_opt = value;
-        return OCN_OK;
-    case OCN_ENS_OPT_MAX_GROUP:
-        if (value < 0) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_MAX_GROUP: >= 0");
-        e->max_group = value;
-        return OCN_OK;
-    default: return set_error(OCN_ERR_ARG, "unknown ensemble option");
-    }
-}
-
-// ------------------------------------------------------------------ ensemble statistics (ens_stats.hip)
-constexpr int kEnsStatAll = OCN_ENS_STAT_MEAN | OCN_ENS_STAT_VAR | OCN_ENS_STAT_SPREAD | OCN_ENS_STAT_MIN | OCN_ENS_STAT_MAX;
-static int ens_stat_index(int32_t stat)
-{
-    for (int i = 0; i < 5; ++i)
-        if (stat == (1 << i)) return i;
-    return -1;
-}
-
-int ocn_ens_stats(ocn_ens *e, int32_t k, int32_t field_id, const uint8_t *use, int32_t what)
-{
-    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
-    const ocn_ctx *c0 = e->m[0];
-    if (k < 0 || k >= (int32_t)c0->blocks.size()) return set_error(OCN_ERR_ARG, "ens_stats: bad block index");
-    if (!has_r8(c0, field_id)) return set_error(OCN_ERR_ARG, "ens_stats: not a real(8) field of the members");
-    if (what == 0 || (what & ~kEnsStatAll)) return set_error(OCN_ERR_ARG, "ens_stats: what = OCN_ENS_STAT_* bits");
-    std::vector<ocn_ctx *> in;
-    for (size_t i = 0; i < e->m.size(); ++i)
-        if (!use || use[i]) in.push_back(e->m[i]);
-    const bool need_var = (what & (OCN_ENS_STAT_VAR | OCN_ENS_STAT_SPREAD)) != 0;
-    if (in.empty()) return set_error(OCN_ERR_ARG, "ens_stats: no member in use");
-    if (need_var && in.size() < 2) return set_error(OCN_ERR_ARG, "ens_stats: variance / spread of fewer than two members");
-    HIPCHK(hipSetDevice(e->device));
-    const LBlock &b0 = c0->blocks[(size_t)k];
-    if (e->stats.empty()) e->stats.resize(c0->blocks.size());
-    ocn_ens::Stats &st = e->stats[(size_t)k];
-    // the buffers first (a failed allocation leaves the earlier results as they were)
-    const size_t lead = (size_t)((uintptr_t)b0.ptr[field_slot(field_id)] & 255u);
-    for (int i = 0; i < 5; ++i) {
-        if (!(what & (1 << i)) || st.raw[i]) continue;
-        HIPCHK(hipMalloc(&st.raw[i], field_bytes(b0) + 512));
-        st.p[i] = (double *)((char *)st.raw[i] + 256 + lead);
-    }
-    // the members in use: their pending call tails formed, their arrays as the field tables name them now
-    std::vector<const double *> src;
-    for (ocn_ctx *c : in) {
-        RC(guarded(c, "ocn_ens_stats", [&] { return complete_open(c); }));
-        src.push_back((const double *)c->blocks[(size_t)k].ptr[field_slot(field_id)]);
-    }
-    double *out[5];
-    for (int i = 0; i < 5; ++i) out[i] = (what & (1 << i)) ? st.p[i] : nullptr;
-    st.formed = 0;
-    RC(launch_ens_stats(&b0.g, src.data(), (int)src.size(), need_var, out, e->stream));
-    st.formed = what;
-    return OCN_OK;
-}
-
-// the statistic's buffer of block k, or an error
-static int ens_stat_buffer(ocn_ens *e, int32_t k, int32_t stat, const void *host, const double **p)
-{
-    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
-    const int i = ens_stat_index(stat);
-    if (!host || i < 0 || k < 0 || k >= (int32_t)e->m[0]->blocks.size())
-        return set_error(OCN_ERR_ARG, "ens_stats: bad block index, statistic or host array");
-    if (e->stats.empty() || !(e->stats[(size_t)k].formed & stat))
-        return set_error(OCN_ERR_STATE, "ens_stats: the last ocn_ens_stats on this block did not form that statistic");
-    *p = e->stats[(size_t)k].p[i];
-    return OCN_OK;
-}
-
-int ocn_ens_stats_download(ocn_ens *e, int32_t k, int32_t stat, double *host)
-{
-    const double *p = nullptr;
-    RC(ens_stat_buffer(e, k, stat, host, &p));
-    HIPCHK(hipSetDevice(e->device));
-    const ocn_block &g = e->m[0]->blocks[(size_t)k].g;
-    const size_t w = (size_t)(g.bnd_x2 - g.bnd_x1 + 1), rows = (size_t)(g.bnd_y2 - g.bnd_y1 + 1);
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy2D(host, w * 8, p, (size_t)g.pitch * 8, w * 8, rows, hipMemcpyDeviceToHost));
-    return OCN_OK;
-}
-
-int ocn_ens_stats_output_r4(ocn_ens *e, int32_t k, int32_t stat, float undef, float *host)
-{
-    const double *p = nullptr;
-    RC(ens_stat_buffer(e, k, stat, host, &p));
-    HIPCHK(hipSetDevice(e->device));
-    ocn_ctx *c0 = e->m[0];
-    RC(guarded(c0, "ocn_ens_stats_output_r4", [&] { return complete_open(c0); }));   // (as ocn_ctx_output_r4 reads lu)
-    const LBlock &b = c0->blocks[(size_t)k];
-    const int w = b.g.nx_end - b.g.nx_start + 1, h = b.g.ny_end - b.g.ny_start + 1;
-    if (w <= 0 || h <= 0) return OCN_OK;
-    const long off = (long)(b.g.ny_start - b.g.bnd_y1) * b.g.pitch + (b.g.nx_start - b.g.bnd_x1);
-    float *d = nullptr;
-    HIPCHK(hipMallocAsync((void **)&d, (size_t)w * h * sizeof(float), e->stream));
-    const dim3 grid((unsigned)((w + 255) / 256), (unsigned)h);
-    hipLaunchKernelGGL(k_output_r4<double>, grid, dim3(256), 0, e->stream, p + off, b.f<float>(OCN_LU) + off,
-                       (long)b.g.pitch, w, h, undef, d);
-    int rc = check_launch();
-    if (rc == OCN_OK && hipMemcpyAsync(host, d, (size_t)w * h * sizeof(float), hipMemcpyDeviceToHost, e->stream) != hipSuccess)
-        rc = set_error(OCN_ERR_HIP, "ens_stats_output_r4: copy");
-    (void)hipFreeAsync(d, e->stream);
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return rc;
-}
-
-int ocn_ens_extrema(ocn_ens *e, int32_t field_id, ocn_ens_extrema_t *out)
-{
-    static_assert(sizeof(EnsPartial) == sizeof(ocn_ens_extrema_t), "EnsPartial is ocn_ens_extrema_t");
-    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
-    const ocn_ctx *c0 = e->m[0];
-    if (!out || !has_r8(c0, field_id)) return set_error(OCN_ERR_ARG, "ens_extrema: null result or not a real(8) field of the members");
-    HIPCHK(hipSetDevice(e->device));
-    const size_t M = e->m.size(), nblk = c0->blocks.size();
-    std::vector<EnsExtBlock> blk(nblk);
-    int tiles = 0;
-    for (size_t k = 0; k < nblk; ++k) {
-        const ocn_block &g = c0->blocks[k].g;
-        EnsExtBlock &q = blk[k];
-        q.w = g.nx_end - g.nx_start + 1;
-        q.h = g.ny_end - g.ny_start + 1;
-        q.off = (long)(g.ny_start - g.bnd_y1) * g.pitch + (g.nx_start - g.bnd_x1);
-        q.pitch = (long)g.pitch;
-        q.first_tile = tiles;
-        tiles += ens_extrema_tiles(q.w, q.h, &q.tiles_x);
-    }
-    for (size_t i = 0; i < M; ++i) {
-        out[i].min = (double)INFINITY;
-        out[i].max = -(double)INFINITY;
-        out[i].nonfinite = out[i].count = 0;
-    }
-    if (tiles < 1) return OCN_OK;
-    const size_t blk_b = ((sizeof(EnsExtBlock) * nblk + 255) / 256) * 256,
-                 tab_b = ((sizeof(EnsExtSrc) * M * nblk + 255) / 256) * 256,
-                 part_b = ((sizeof(EnsPartial) * M * (size_t)tiles + 255) / 256) * 256;
-    const size_t res_b = sizeof(EnsPartial) * M;
-    if (!e->d_ext) HIPCHK(hipMalloc(&e->d_ext, blk_b + tab_b + part_b + res_b));
-    if (!e->h_ext) HIPCHK(hipHostMalloc(&e->h_ext, blk_b + tab_b + res_b, hipHostMallocDefault));
-    int first = OCN_OK;
-    char *d = (char *)e->d_ext, *h = (char *)e->h_ext;
-    EnsExtSrc *tab = (EnsExtSrc *)(h + blk_b);
-    for (size_t i = 0; i < M; ++i) {
-        ocn_ctx *c = e->m[i];
-        if (const int rc = guarded(c, "ocn_ens_extrema", [&] { return complete_open(c); }); rc && !first) first = rc;
-        for (size_t k = 0; k < nblk; ++k)
-            tab[i * nblk + k] = EnsExtSrc{c->blocks[k].f<double>(field_id), c->blocks[k].f<float>(OCN_LU)};
-    }
-    if (first) return first;
-    // the tables up, the launches, the results down, all on the ensemble's stream, and one wait (a
-    // synchronous entry: the previous call has ended, nothing reads the pinned tables now)
-    memcpy(h, blk.data(), sizeof(EnsExtBlock) * nblk);
-    HIPCHK(hipMemcpyAsync(d, h, blk_b + tab_b, hipMemcpyHostToDevice, e->stream));
-    EnsPartial *res = (EnsPartial *)(d + blk_b + tab_b + part_b);
-    RC(launch_ens_extrema((const EnsExtBlock *)d, (int)nblk, (const EnsExtSrc *)(d + blk_b), (int)M, tiles,
-                          (EnsPartial *)(d + blk_b + tab_b), res, e->stream));
-    HIPCHK(hipMemcpyAsync(h + blk_b + tab_b, res, res_b, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    memcpy(out, h + blk_b + tab_b, res_b);
-    return OCN_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,440 @@
+// ocn_ens.hip -- ensembles (ocn_sw.h ocn_ens_*): many members of a small basin as contexts that share
+// one compute stream, their multi-step launches issued one per group (sw_kernels.hip k_march_multi_b),
+// and the statistics over the members (ens_stats.hip).  The members' calls are planned by ocn_ctx.hip
+// step_impl; ocn_ens_plan.h holds the grouping policy.
+#include "ocn_ctx.h"
+#include "ocn_ens_plan.h"
+
+extern "C" {
+
+// ------------------------------------------------------------------ ensembles (ocn_sw.h)
+struct ocn_ens {
+    std::vector<ocn_ctx *> m;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    unsigned *d_bar = nullptr;     // kMultiBarBytes of barrier words per member
+    void *d_tab = nullptr;         // the launches' member table (sw_kernels.hip EnsEntry), tab_bytes
+    size_t tab_bytes = 0;
+    // the table's pinned host copies: a call's launches fill disjoint parts of one, the next call takes
+    // the other; ev[i]: the stream has read copy i (awaited before it is written again)
+    void *h_tab[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool ev_set[2] = {false, false};
+    int slot = 0;
+    int64_t cap_opt = 0;           // OCN_ENS_OPT_CAPACITY (0: none)
+    int64_t max_group = 0;         // OCN_ENS_OPT_MAX_GROUP (0: none)
+    ocn_ens_info_t last{};
+    // ocn_ens_stats: per local block, one buffer per statistic (mean, variance, spread, minimum, maximum)
+    // based like the members' arrays (raw: the allocations, made at first use), and the statistics the
+    // last call on that block formed (OCN_ENS_STAT_* bits)
+    struct Stats { void *raw[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+                   double *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; int formed = 0; };
+    std::vector<Stats> stats;
+    // ocn_ens_extrema: the blocks' interiors, the members' (field, lu) table, the per-tile partials and
+    // the results, in one device allocation made at first use; h_ext: the tables and the results in pinned host memory
+    void *d_ext = nullptr, *h_ext = nullptr;
+};
+
+// ocn_ens_plan's policy: ocn_ens_plan.h (pure host code, also built stand-alone)
+static int ens_plan(const ocn_block *g, const int32_t *variant, int members, int64_t capacity,
+                    std::vector<ocn_ens_group> &out)
+{
+    const char *err = nullptr;
+    const int rc = ens_plan_groups(g, variant, members, capacity, out, &err);
+    return rc ? set_error(rc, std::string("ensemble plan: ") + err) : OCN_OK;
+}
+
+int ocn_ens_plan(const ocn_block *geom, const int32_t *variant, int32_t members, int64_t capacity, ocn_ens_group *out,
+                 int32_t cap, int32_t *count)
+{
+    std::vector<ocn_ens_group> gs;
+    RC(ens_plan(geom, variant, members, capacity, gs));
+    if (count) *count = (int32_t)gs.size();
+    for (size_t i = 0; i < gs.size() && (int32_t)i < cap && out; ++i) out[i] = gs[i];
+    return OCN_OK;
+}
+
+int ocn_ens_destroy(ocn_ens *e)
+{
+    if (!e) return OCN_OK;
+    (void)hipSetDevice(e->device);
+    if (e->stream) (void)hipStreamSynchronize(e->stream);
+    for (ocn_ctx *c : e->m) (void)ctx_destroy(c);
+    for (int i = 0; i < 2; ++i) {
+        if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
+        if (e->h_tab[i]) (void)hipHostFree(e->h_tab[i]);
+    }
+    if (e->d_tab) (void)hipFree(e->d_tab);
+    if (e->d_bar) (void)hipFree(e->d_bar);
+    for (ocn_ens::Stats &q : e->stats)
+        for (void *r : q.raw)
+            if (r) (void)hipFree(r);
+    if (e->d_ext) (void)hipFree(e->d_ext);
+    if (e->h_ext) (void)hipHostFree(e->h_ext);
+    if (e->stream) (void)hipStreamDestroy(e->stream);
+    delete e;
+    return OCN_OK;
+}
+
+int ocn_ens_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_decomp *dec, const int32_t *mask,
+                   int32_t members, ocn_ens **out)
+{
+    if (!basin || !sw || !dec || !out) return set_error(OCN_ERR_ARG, "null argument");
+    if (members < 1 || members > OCN_ENS_MAX_MEMBERS)
+        return set_error(OCN_ERR_ARG, "ensemble: 1.." + std::to_string(OCN_ENS_MAX_MEMBERS) + " members");
+    if (dec->nranks != 1) return set_error(OCN_ERR_ARG, "ensemble: one rank (dec->nranks = 1)");
+    ocn_ens *e = new ocn_ens();
+    e->device = dec->device;
+    int rc = check_hip(hipSetDevice(dec->device), "hipSetDevice");
+    if (!rc) rc = check_hip(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate");
+    for (int i = 0; i < members && !rc; ++i) {
+        ocn_ctx *c = nullptr;
+        rc = ctx_create(basin, sw, dec, mask, e->stream, e, &c);
+        if (!rc) e->m.push_back(c);
+    }
+    e->tab_bytes = (size_t)members * onepass_multi_b_entry_bytes();
+    if (!rc) rc = check_hip(hipMalloc((void **)&e->d_bar, (size_t)members * kMultiBarBytes), "hipMalloc");
+    if (!rc) rc = check_hip(hipMalloc(&e->d_tab, e->tab_bytes), "hipMalloc");
+    for (int i = 0; i < 2 && !rc; ++i) {
+        rc = check_hip(hipHostMalloc(&e->h_tab[i], e->tab_bytes, hipHostMallocDefault), "hipHostMalloc");
+        if (!rc) rc = check_hip(hipEventCreateWithFlags(&e->ev[i], hipEventDisableTiming), "hipEventCreate");
+    }
+    if (rc) { ocn_ens_destroy(e); return rc; }
+    e->last.members = members;
+    *out = e;
+    return OCN_OK;
+}
+
+int ocn_ens_size(const ocn_ens *e) { return e ? (int)e->m.size() : -1; }
+
+int ocn_ens_member(ocn_ens *e, int32_t i, ocn_ctx **out)
+{
+    if (!e || !out || i < 0 || i >= (int32_t)e->m.size()) return set_error(OCN_ERR_ARG, "ensemble: bad member index");
+    *out = e->m[(size_t)i];
+    return OCN_OK;
+}
+
+int ocn_ens_init_state(ocn_ens *e)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    for (ocn_ctx *c : e->m) RC(ocn_ctx_init_state(c));
+    return OCN_OK;
+}
+
+int ocn_ens_complete(ocn_ens *e)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    int first = OCN_OK;
+    for (ocn_ctx *c : e->m)
+        if (const int rc = ocn_ctx_complete(c); rc && !first) first = rc;
+    return first;
+}
+
+static int64_t ens_capacity(const ocn_ens *e)
+{
+    const int64_t dev = onepass_multi_b_capacity();
+    return e->cap_opt > 0 ? std::min(dev, e->cap_opt) : dev;
+}
+
+// a member's planned multi-step launch did not go out: its call fails as step_impl's would
+static int ens_fail(ocn_ctx *c, int rc)
+{
+    c->open = false; c->deferred = 0; c->open_pair = false;
+    return fail_fatal(c, finish_call(c, rc));
+}
+
+int ocn_ens_step(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    const int M = (int)e->m.size();
+    e->last = ocn_ens_info_t{};
+    e->last.members = M;
+    int first = OCN_OK;
+    auto note = [&](int rc) { if (rc && !first) first = rc; };
+    // every member plans its call as ocn_ctx_step does and runs whatever is not a multi-step launch
+    std::vector<int32_t> variant((size_t)M, -1);
+    for (int i = 0; i < M; ++i) {
+        ocn_ctx *c = e->m[(size_t)i];
+        c->ens_pending = false;
+        c->ens_collect = true;
+        note(guarded(c, "ocn_ens_step", [&] { return step_entry(c, tau, nsteps, check_every); }));
+        c->ens_collect = false;
+        // (batched: the library's fused path with the sw switches the launch needs; else its own launch)
+        if (c->ens_pending && c->fused && c->sw.full_free_surface == 1 && c->sw.trans_terms > 0 && c->sw.ksw_lat > 0)
+            variant[(size_t)i] = onepass_multi_variant(c->kc_mode, tau, c->ens_k.check);
+    }
+    HIPCHK(hipSetDevice(e->device));
+    e->last.capacity = ens_capacity(e);
+    std::vector<ocn_ens_group> groups;
+    if (e->last.capacity >= 1 && e->max_group < 1) {
+        note(ens_plan(&e->m[0]->blocks[0].g, variant.data(), M, e->last.capacity, groups));
+    } else if (e->last.capacity >= 1) {   // OCN_ENS_OPT_MAX_GROUP: the plan of every max_group planned members
+        std::vector<ocn_ens_group> part;
+        std::vector<int32_t> v((size_t)M, -1);
+        int n = 0;
+        for (int i = 0; i < M; ++i) {
+            if (variant[(size_t)i] >= 0) { v[(size_t)i] = variant[(size_t)i]; ++n; }
+            if (n && (n == e->max_group || i == M - 1)) {
+                note(ens_plan(&e->m[0]->blocks[0].g, v.data(), M, e->last.capacity, part));
+                groups.insert(groups.end(), part.begin(), part.end());
+                std::fill(v.begin(), v.end(), -1);
+                n = 0;
+            }
+        }
+    }
+    std::vector<char> done((size_t)M, 0);
+    if (!groups.empty()) {
+        const int sl = e->slot;
+        e->slot ^= 1;
+        if (e->ev_set[sl]) HIPCHK(hipEventSynchronize(e->ev[sl]));
+        HIPCHK(hipMemsetAsync(e->d_bar, 0, (size_t)M * kMultiBarBytes, e->stream));
+        const size_t eb = onepass_multi_b_entry_bytes();
+        size_t off = 0;
+        for (const ocn_ens_group &q : groups) {
+            std::vector<Compact> cps((size_t)q.members);
+            std::vector<EnsMember> ms((size_t)q.members);
+            std::vector<ocn_ctx::Rec> recs((size_t)q.members);
+            int rc = OCN_OK;
+            for (int j = 0; j < q.members; ++j) {
+                ocn_ctx *c = e->m[(size_t)q.member[j]];
+                const LBlock &b = c->blocks[0];
+                cps[(size_t)j] = Compact{b.bits, b.rows, c->march};
+                const OnepassKC kc = kc_of(c, b);
+                ms[(size_t)j] = EnsMember{&b.g, b.ptr.data(), (int)b.ptr.size(), &cps[(size_t)j],
+                                          c->ens_k.check ? c->d_nbad : nullptr,
+                                          {(double *)b.sshp_alt, (double *)b.up_alt, (double *)b.vp_alt},
+                                          e->d_bar + (size_t)q.member[j] * (kMultiBarBytes / sizeof(unsigned)),
+                                          c->d_nbad + 61, kc.kc, c->multi_spin};
+                if (!c->fused) c->hn_fresh = false;
+                if (!rc) rc = timer_begin(c, OCN_TIMER_ONEPASS_MULTI, recs[(size_t)j]);
+            }
+            if (!rc)
+                rc = launch_onepass_multi_b(ms.data(), q.members, q.variant, q.rows, e->m[(size_t)q.member[0]]->sw, tau,
+                                            nsteps, e->d_tab, (char *)e->h_tab[sl] + off, eb * (size_t)q.members,
+                                            (long)e->last.capacity, e->stream);
+            off += eb * (size_t)q.members;
+            for (int j = 0; j < q.members; ++j) {
+                ocn_ctx *c = e->m[(size_t)q.member[j]];
+                done[(size_t)q.member[j]] = 1;
+                c->ens_pending = false;
+                if (!rc) {   // the host side of one_step_multi
+                    const int rt = timer_end(c, recs[(size_t)j]);
+                    if (c->ens_k.multi & 1) {
+                        swap_alt3(c);
+                        swap_roles(c);
+                    }
+                    if (rt) note(ens_fail(c, rt));
+                } else {
+                    note(ens_fail(c, rc));
+                }
+            }
+            if (!rc) {
+                ++e->last.groups;
+                e->last.batched += q.members;
+                if (q.members > e->last.max_group) {
+                    e->last.max_group = q.members; e->last.rows = q.rows; e->last.tiles = q.tiles;
+                }
+            }
+        }
+        HIPCHK(hipEventRecord(e->ev[sl], e->stream));
+        e->ev_set[sl] = true;
+    }
+    // planned members in no group (no variant the launch takes, or too many tiles for the capacity in
+    // effect): their own multi-step launch, as ocn_ctx_step issues it
+    for (int i = 0; i < M; ++i) {
+        ocn_ctx *c = e->m[(size_t)i];
+        if (!c->ens_pending || done[(size_t)i]) continue;
+        c->ens_pending = false;
+        if (const int rc = run_step(c, tau, c->ens_k)) note(ens_fail(c, rc));
+    }
+    return first;
+}
+
+int ocn_ens_synchronize(ocn_ens *e, int32_t *status)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    int first = OCN_OK;
+    std::string msg;
+    for (size_t i = 0; i < e->m.size(); ++i) {   // (the first member's wait is the wait: one stream)
+        const int rc = ocn_ctx_synchronize(e->m[i]);
+        if (status) status[i] = rc;
+        if (rc && !first) { first = rc; msg = "member " + std::to_string(i) + ": " + ocn_last_error(); }
+    }
+    return first ? set_error(first, msg) : OCN_OK;
+}
+
+int ocn_ens_info(ocn_ens *e, ocn_ens_info_t *out)
+{
+    if (!e || !out) return set_error(OCN_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(e->device));
+    *out = e->last;
+    out->members = (int32_t)e->m.size();
+    out->capacity = ens_capacity(e);
+    return OCN_OK;
+}
+
+int ocn_ens_set_option(ocn_ens *e, int32_t key, int64_t value)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    switch (key) {
+    case OCN_ENS_OPT_CAPACITY:
+        if (value < 0) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_CAPACITY: >= 0");
+        e->cap_opt = value;
+        return OCN_OK;
+    case OCN_ENS_OPT_MAX_GROUP:
+        if (value < 0) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_MAX_GROUP: >= 0");
+        e->max_group = value;
+        return OCN_OK;
+    default: return set_error(OCN_ERR_ARG, "unknown ensemble option");
+    }
+}
+
+// ------------------------------------------------------------------ ensemble statistics (ens_stats.hip)
+constexpr int kEnsStatAll = OCN_ENS_STAT_MEAN | OCN_ENS_STAT_VAR | OCN_ENS_STAT_SPREAD | OCN_ENS_STAT_MIN | OCN_ENS_STAT_MAX;
+static int ens_stat_index(int32_t stat)
+{
+    for (int i = 0; i < 5; ++i)
+        if (stat == (1 << i)) return i;
+    return -1;
+}
+
+int ocn_ens_stats(ocn_ens *e, int32_t k, int32_t field_id, const uint8_t *use, int32_t what)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    const ocn_ctx *c0 = e->m[0];
+    if (k < 0 || k >= (int32_t)c0->blocks.size()) return set_error(OCN_ERR_ARG, "ens_stats: bad block index");
+    if (!has_r8(c0, field_id)) return set_error(OCN_ERR_ARG, "ens_stats: not a real(8) field of the members");
+    if (what == 0 || (what & ~kEnsStatAll)) return set_error(OCN_ERR_ARG, "ens_stats: what = OCN_ENS_STAT_* bits");
+    std::vector<ocn_ctx *> in;
+    for (size_t i = 0; i < e->m.size(); ++i)
+        if (!use || use[i]) in.push_back(e->m[i]);
+    const bool need_var = (what & (OCN_ENS_STAT_VAR | OCN_ENS_STAT_SPREAD)) != 0;
+    if (in.empty()) return set_error(OCN_ERR_ARG, "ens_stats: no member in use");
+    if (need_var && in.size() < 2) return set_error(OCN_ERR_ARG, "ens_stats: variance / spread of fewer than two members");
+    HIPCHK(hipSetDevice(e->device));
+    const LBlock &b0 = c0->blocks[(size_t)k];
+    if (e->stats.empty()) e->stats.resize(c0->blocks.size());
+    ocn_ens::Stats &st = e->stats[(size_t)k];
+    // the buffers first (a failed allocation leaves the earlier results as they were)
+    const size_t lead = (size_t)((uintptr_t)b0.ptr[field_slot(field_id)] & 255u);
+    for (int i = 0; i < 5; ++i) {
+        if (!(what & (1 << i)) || st.raw[i]) continue;
+        HIPCHK(hipMalloc(&st.raw[i], field_bytes(b0) + 512));
+        st.p[i] = (double *)((char *)st.raw[i] + 256 + lead);
+    }
+    // the members in use: their pending call tails formed, their arrays as the field tables name them now
+    std::vector<const double *> src;
+    for (ocn_ctx *c : in) {
+        RC(guarded(c, "ocn_ens_stats", [&] { return complete_open(c); }));
+        src.push_back((const double *)c->blocks[(size_t)k].ptr[field_slot(field_id)]);
+    }
+    double *out[5];
+    for (int i = 0; i < 5; ++i) out[i] = (what & (1 << i)) ? st.p[i] : nullptr;
+    st.formed = 0;
+    RC(launch_ens_stats(&b0.g, src.data(), (int)src.size(), need_var, out, e->stream));
+    st.formed = what;
+    return OCN_OK;
+}
+
+// the statistic's buffer of block k, or an error
+static int ens_stat_buffer(ocn_ens *e, int32_t k, int32_t stat, const void *host, const double **p)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    const int i = ens_stat_index(stat);
+    if (!host || i < 0 || k < 0 || k >= (int32_t)e->m[0]->blocks.size())
+        return set_error(OCN_ERR_ARG, "ens_stats: bad block index, statistic or host array");
+    if (e->stats.empty() || !(e->stats[(size_t)k].formed & stat))
+        return set_error(OCN_ERR_STATE, "ens_stats: the last ocn_ens_stats on this block did not form that statistic");
+    *p = e->stats[(size_t)k].p[i];
+    return OCN_OK;
+}
+
+int ocn_ens_stats_download(ocn_ens *e, int32_t k, int32_t stat, double *host)
+{
+    const double *p = nullptr;
+    RC(ens_stat_buffer(e, k, stat, host, &p));
+    HIPCHK(hipSetDevice(e->device));
+    const ocn_block &g = e->m[0]->blocks[(size_t)k].g;
+    const size_t w = (size_t)(g.bnd_x2 - g.bnd_x1 + 1), rows = (size_t)(g.bnd_y2 - g.bnd_y1 + 1);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy2D(host, w * 8, p, (size_t)g.pitch * 8, w * 8, rows, hipMemcpyDeviceToHost));
+    return OCN_OK;
+}
+
+int ocn_ens_stats_output_r4(ocn_ens *e, int32_t k, int32_t stat, float undef, float *host)
+{
+    const double *p = nullptr;
+    RC(ens_stat_buffer(e, k, stat, host, &p));
+    HIPCHK(hipSetDevice(e->device));
+    ocn_ctx *c0 = e->m[0];
+    RC(guarded(c0, "ocn_ens_stats_output_r4", [&] { return complete_open(c0); }));   // (as ocn_ctx_output_r4 reads lu)
+    const LBlock &b = c0->blocks[(size_t)k];
+    const int w = b.g.nx_end - b.g.nx_start + 1, h = b.g.ny_end - b.g.ny_start + 1;
+    if (w <= 0 || h <= 0) return OCN_OK;
+    const long off = (long)(b.g.ny_start - b.g.bnd_y1) * b.g.pitch + (b.g.nx_start - b.g.bnd_x1);
+    float *d = nullptr;
+    HIPCHK(hipMallocAsync((void **)&d, (size_t)w * h * sizeof(float), e->stream));
+    int rc = launch_output_r4(p + off, b.f<float>(OCN_LU) + off, (long)b.g.pitch, w, h, undef, d, e->stream);
+    if (rc == OCN_OK && hipMemcpyAsync(host, d, (size_t)w * h * sizeof(float), hipMemcpyDeviceToHost, e->stream) != hipSuccess)
+        rc = set_error(OCN_ERR_HIP, "ens_stats_output_r4: copy");
+    (void)hipFreeAsync(d, e->stream);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return rc;
+}
+
+int ocn_ens_extrema(ocn_ens *e, int32_t field_id, ocn_ens_extrema_t *out)
+{
+    static_assert(sizeof(EnsPartial) == sizeof(ocn_ens_extrema_t), "EnsPartial is ocn_ens_extrema_t");
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    const ocn_ctx *c0 = e->m[0];
+    if (!out || !has_r8(c0, field_id)) return set_error(OCN_ERR_ARG, "ens_extrema: null result or not a real(8) field of the members");
+    HIPCHK(hipSetDevice(e->device));
+    const size_t M = e->m.size(), nblk = c0->blocks.size();
+    std::vector<EnsExtBlock> blk(nblk);
+    int tiles = 0;
+    for (size_t k = 0; k < nblk; ++k) {
+        const ocn_block &g = c0->blocks[k].g;
+        EnsExtBlock &q = blk[k];
+        q.w = g.nx_end - g.nx_start + 1;
+        q.h = g.ny_end - g.ny_start + 1;
+        q.off = (long)(g.ny_start - g.bnd_y1) * g.pitch + (g.nx_start - g.bnd_x1);
+        q.pitch = (long)g.pitch;
+        q.first_tile = tiles;
+        tiles += ens_extrema_tiles(q.w, q.h, &q.tiles_x);
+    }
+    for (size_t i = 0; i < M; ++i) {
+        out[i].min = (double)INFINITY;
+        out[i].max = -(double)INFINITY;
+        out[i].nonfinite = out[i].count = 0;
+    }
+    if (tiles < 1) return OCN_OK;
+    const size_t blk_b = ((sizeof(EnsExtBlock) * nblk + 255) / 256) * 256,
+                 tab_b = ((sizeof(EnsExtSrc) * M * nblk + 255) / 256) * 256,
+                 part_b = ((sizeof(EnsPartial) * M * (size_t)tiles + 255) / 256) * 256;
+    const size_t res_b = sizeof(EnsPartial) * M;
+    if (!e->d_ext) HIPCHK(hipMalloc(&e->d_ext, blk_b + tab_b + part_b + res_b));
+    if (!e->h_ext) HIPCHK(hipHostMalloc(&e->h_ext, blk_b + tab_b + res_b, hipHostMallocDefault));
+    int first = OCN_OK;
+    char *d = (char *)e->d_ext, *h = (char *)e->h_ext;
+    EnsExtSrc *tab = (EnsExtSrc *)(h + blk_b);
+    for (size_t i = 0; i < M; ++i) {
+        ocn_ctx *c = e->m[i];
+        if (const int rc = guarded(c, "ocn_ens_extrema", [&] { return complete_open(c); }); rc && !first) first = rc;
+        for (size_t k = 0; k < nblk; ++k)
+            tab[i * nblk + k] = EnsExtSrc{c->blocks[k].f<double>(field_id), c->blocks[k].f<float>(OCN_LU)};
+    }
+    if (first) return first;
+    // the tables up, the launches, the results down, all on the ensemble's stream, and one wait (a
+    // synchronous entry: the previous call has ended, nothing reads the pinned tables now)
+    memcpy(h, blk.data(), sizeof(EnsExtBlock) * nblk);
+    HIPCHK(hipMemcpyAsync(d, h, blk_b + tab_b, hipMemcpyHostToDevice, e->stream));
+    EnsPartial *res = (EnsPartial *)(d + blk_b + tab_b + part_b);
+    RC(launch_ens_extrema((const EnsExtBlock *)d, (int)nblk, (const EnsExtSrc *)(d + blk_b), (int)M, tiles,
+                          (EnsPartial *)(d + blk_b + tab_b), res, e->stream));
+    HIPCHK(hipMemcpyAsync(h + blk_b + tab_b, res, res_b, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    memcpy(out, h + blk_b + tab_b, res_b);
+    return OCN_OK;
+}
+
+}  // extern "C"

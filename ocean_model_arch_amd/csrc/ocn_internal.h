@@ -95,7 +95,7 @@ int launch_fused_ca(const ocn_block *b, void *const *ptr, int nptr, const Compac
 // (sw_stencils.h kRowTable, recip_offset)
 size_t row_table_size(unsigned nrows);
 
-// Initial state on the device (init_kernels.hip; ocn_ctx.hip init_state).  GridInit: one block's
+// Initial state on the device (init_kernels.hip; ctx_setup.hip init_state).  GridInit: one block's
 // real(4) static fields from the basin mask (device copy, nx x ny int32, 1-based (m, n) at
 // (m-1) + (n-1) nx) and the grid's row / column factors from the host's libm.
 struct GridInit {

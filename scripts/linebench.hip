@@ -2,7 +2,7 @@
 // Pure streaming in the register-march shape (4 waves per workgroup, rows marched, the next
 // row's loads issued before the current row's stores, XCD-banded tile order) over the one-pass
 // step's mix: 6 r8 arrays + the u8 mask byte in, 6 r8 arrays out (97 B per cell), on a 4096^2
-// interior laid out as ocn_ctx.hip allocates (pitch 4160, rows 256-B aligned at nx_start).
+// interior laid out as ctx_setup.hip allocates (pitch 4160, rows 256-B aligned at nx_start).
 // Lane layouts (COLS output columns per wave, HALO load-only lanes each side):
 //   64 / 0: outputs start on 512-B boundaries (whole 128-B lines per store)
 //   60 / 2: the one-pass step's layout -- runs of 480 B starting on 32-B boundaries, so every

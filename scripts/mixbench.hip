@@ -116,7 +116,7 @@ static void report(const char *name, const Args &a)
 int main()
 {
     const size_t n = (size_t)PITCH * ROWS;
-    const size_t fb = ((n * 8 + 16 + 255) / 256) * 256 + 256;   // ocn_ctx.hip allocate()
+    const size_t fb = ((n * 8 + 16 + 255) / 256) * 256 + 256;   // ctx_setup.hip allocate()
     char *slab;
     CHK(hipMalloc(&slab, fb * 2 * MAXA + 4096));
     CHK(hipMemset(slab, 0, fb * 2 * MAXA + 4096));

@@ -101,6 +101,29 @@ def test_profile_applies_to_unchanged_kernel_code(tmp_path, monkeypatch):
     assert bench.load_traffic(_A("other"), "onepass2", 4096, True, [64, 64], [1, 1]) == (None, None)
 
 
+def test_every_source_contributes_a_code_object():
+    """Each object file with device code brings its own gfx950 bundle.  gfx950_code_object stays the
+    first one -- sw_kernels.hip's, first on the link line, where bench.py looks up the march kernels'
+    code_sha -- and the halo segment kernels (ctx_comm.hip) are found only over all of them, which is
+    what scripts/codeobj_diff.py compares between two builds."""
+    import subprocess
+    import sys
+    import ocean_model_arch_amd as amd
+    from ocean_model_arch_amd import _codeobj
+    lib = amd._lib.LIB_PATH
+    if not os.path.exists(lib):
+        pytest.skip("library not built")
+    objs = list(_codeobj.gfx950_code_objects(lib))
+    assert len(objs) >= 2 and objs[0] == _codeobj.gfx950_code_object(lib)
+    first = _codeobj.kernel_symbols(objs[0])
+    assert _codeobj.march_step_symbol("true, false, true, false, false, true, false") in first
+    rest = [n for o in objs[1:] for n in _codeobj.kernel_symbols(o)]
+    assert any("k_segments" in n for n in rest) and not any("k_segments" in n for n in first)
+    r = subprocess.run([sys.executable, os.path.join(bench.REPO, "scripts", "codeobj_diff.py"), lib, lib],
+                       capture_output=True, text=True)
+    assert r.returncode == 0 and "0 missing or different" in r.stdout, r.stdout + r.stderr
+
+
 def test_valu_needs_matching_stamp(tmp_path, monkeypatch):
     """roofline.valu: the one-pass kernel's VALU issue floor from the committed SQ pass, only on the
     build and workload it was taken on; 1024 SIMDs x 1 wave64 instruction per quad-cycle at 2.4 GHz."""

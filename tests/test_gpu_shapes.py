@@ -9,7 +9,7 @@ cost models with a last tile of one row, blocks lower than the shortest pair til
 4 x 4 block minimum, inner parts (overlap level 2) that are empty or one point wide, the E / W band
 widths' switch at blocks 180 / 348 wide, neighbour tables with holes (dropped all-land blocks: a
 diagonal neighbour with neither side neighbour at its corner, where the hybrid last step once left
-the corner halo of the depths' p and n levels stale -- ocn_ctx.hip onepass_inner), and h_r's copy
+the corner halo of the depths' p and n levels stale -- ocn_ctx.hip side_fed), and h_r's copy
 exchanged 4 rings deep between blocks 2-3 points wide (ocn_ctx.hip refresh_hrx).
 
 Every run: uploads, a first call of 2 steps, synchronize() (the known-constant verdict reaches the
