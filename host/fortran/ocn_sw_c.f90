@@ -38,7 +38,7 @@ module ocn_sw_c
                                      OCN_OPT_BATCH = 14, OCN_OPT_PAIR = 15, OCN_OPT_MULTI = 16,                    &
                                      OCN_OPT_TRACER_STEP = 17, OCN_OPT_MULTI_SPIN = 18, &
                                      OCN_OPT_X4 = 19, OCN_OPT_CO_LAUNCH = 20, &
-                                     OCN_OPT_XCHG_DELAY = 21
+                                     OCN_OPT_XCHG_DELAY = 21, OCN_OPT_INVISCID = 22
     integer(c_int32_t), parameter :: OCN_HALO_LOCAL = 0, OCN_HALO_SEND = 1, OCN_HALO_RECV = 2
     integer, parameter :: OCN_UNIQUE_ID_BYTES = 128   ! sizeof(ncclUniqueId)
 

@@ -444,6 +444,13 @@ int ocn_ctx_output_r4(ocn_ctx *ctx, int k, int field_id, float undef, float *hos
  *  step's march -- with OCN_OPT_OVERLAP 2 the part after the exchange -- and the previous state's
  *  tracer step go as ONE launch (their workgroups in one grid) instead of two.  Same results bit for
  *  bit.  ocn_ctx_get_option: 2 if the last ocn_ctx_step co-launched.
+ *  OCN_OPT_INVISCID (default 1): the two-step launches (OCN_OPT_PAIR, OCN_OPT_X4) of the known-constant
+ *  variants form none of the viscous (a5 stresses, a6 uv_diff2) and bottom-friction terms where the
+ *  checks find the viscosity mu +0.0 everywhere and r_diss +0.0f in every row, as ocn_ctx_init_state
+ *  leaves them: every such term is then +-0 and the momentum sums are the same bit for bit; rows whose
+ *  state is not finite and below 2^300 are computed in full.  Dropped, like the known-constant variant,
+ *  whenever a field is handed in or a raw real(8) pointer handed out, until the next check.  Same
+ *  results bit for bit.  ocn_ctx_get_option: 2 if the last ocn_ctx_step ran such launches.
  *  OCN_OPT_MULTI_SPIN (diagnostics; default 1 << 20, about 0.5 s): the multi-step launch's grid
  *  barrier gives up after this many polls -- the launch's workgroups end and ocn_ctx_synchronize
  *  returns OCN_ERR_HIP instead of the device hanging if the grid was not co-resident.  Tests set it
@@ -462,7 +469,8 @@ enum { OCN_OPT_GRAPH = 1, OCN_OPT_OVERLAP = 2, OCN_OPT_STAGE_TIMING = 3, OCN_OPT
        OCN_OPT_MARCH = 6, OCN_OPT_FLIP = 7, OCN_OPT_RECOMPUTE = 8, OCN_OPT_ONEPASS = 9,
        OCN_OPT_KNOWN_CONSTANTS = 10, OCN_OPT_ONEPASS_LAST = 11, OCN_OPT_LAZY_TAIL = 12, OCN_OPT_X2 = 13,
        OCN_OPT_BATCH = 14, OCN_OPT_PAIR = 15, OCN_OPT_MULTI = 16, OCN_OPT_TRACER_STEP = 17,
-       OCN_OPT_MULTI_SPIN = 18, OCN_OPT_X4 = 19, OCN_OPT_CO_LAUNCH = 20, OCN_OPT_XCHG_DELAY = 21 };
+       OCN_OPT_MULTI_SPIN = 18, OCN_OPT_X4 = 19, OCN_OPT_CO_LAUNCH = 20, OCN_OPT_XCHG_DELAY = 21,
+       OCN_OPT_INVISCID = 22 };
 
 /* Timer slots: the stage ids, then the fused groups (fused C2 is OCN_STAGE_HH_INIT), then the
  * three tracer stages (summed over tracers), then the role-flip steps' fused hh_init + next A,

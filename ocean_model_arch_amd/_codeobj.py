@@ -82,11 +82,13 @@ def kernel_symbols(code: bytes) -> dict:
 
 def march_step_symbol(args: str, batched: bool = False) -> str:
     """The mangled name of k_march<MarchStep<args>> (k_march_b with batched), args as in the profile
-    summaries: 'true, false, true, false, false, true, false'."""
+    summaries: 'true, false, true, false, false, true, false' (with an eighth, NV: k_march<MarchStepT<args>>)."""
     bits = "".join("Lb1E" if a.strip() == "true" else "Lb0E" for a in args.split(","))
+    # (eight arguments: MarchStepT, the body template itself -- the inviscid bodies, its last argument)
+    body = "10MarchStepT" if len(args.split(",")) == 8 else "9MarchStep"
     if batched:
-        return f"_ZN3ocn9k_march_bINS_9MarchStepII{bits}EEEEvNS_10MarchGridBENS_4PackIT_EE".replace("II", "I")
-    return f"_ZN3ocn7k_marchINS_9MarchStepII{bits}EEEEvNS_9MarchGridET_".replace("II", "I")
+        return f"_ZN3ocn9k_march_bINS_{body}I{bits}EEEEvNS_10MarchGridBENS_4PackIT_EE"
+    return f"_ZN3ocn7k_marchINS_{body}I{bits}EEEEvNS_9MarchGridET_"
 
 
 def kernel_code_sha(lib_path: str, symbol: str) -> str | None:

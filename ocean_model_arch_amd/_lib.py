@@ -89,6 +89,7 @@ OPT_MULTI_SPIN = 18
 OPT_X4 = 19
 OPT_CO_LAUNCH = 20
 OPT_XCHG_DELAY = 21
+OPT_INVISCID = 22
 
 # exported symbols (every one declared in include/ocn_sw.h)
 KERNEL_SYMBOLS = ["ocn_sw_update_ssh", "ocn_hh_update", "ocn_uv_trans_vort", "ocn_uv_trans",

@@ -277,7 +277,7 @@ int allocate(ocn_ctx *c)
         c->allocs.push_back(b.rows);
         RC(allocate_x2(c, b));
     }
-    // d_nbad words: 0 check_ssh_err's count, 16 the fallback check's verdict (d_fbz), 32..47 flags and
+    // d_nbad words: 0 check_ssh_err's count, 16 the fallback check's verdict (d_fbz) and 17 its mu word, 32..47 flags and
     // the vote (d_flags), 48..55 the loopback vote's reduction, 56 the count's maximum over the ranks
     // (sync_impl), 61 the multi-step launch's barrier timeout flag; then per block h_r, mu (LBlock::kc)
     const size_t kcb = 16 * c->blocks.size();
@@ -286,7 +286,7 @@ int allocate(ocn_ctx *c)
     HIPCHK(hipMalloc(&c->d_bar, kMultiBarBytes));
     c->allocs.push_back(c->d_bar);
     HIPCHK(hipMemsetAsync(c->d_nbad, 0, 256 + kcb, c->stream));
-    c->d_fbz = c->d_nbad + 16;
+    c->d_fbz = c->d_nbad + kFbzWord;   // (and kFbzWord + 1: its mu word)
     c->d_flags = c->d_nbad + 32;
     for (size_t i = 0; i < c->blocks.size(); ++i) c->blocks[i].kc = (double *)((char *)c->d_nbad + 256) + 2 * i;
     return OCN_OK;
@@ -321,8 +321,10 @@ int prepare_static(ocn_ctx *c)
     c->edge_ring_sea = (flags[0] & kCompactEdgeRingSea) != 0;
     c->udiv_ok = (flags[0] & kCompactDivisorRange) == 0;
     c->rows_x_ok = c->ext_ok && flags[1] == 0;
-    c->x4_tab_ok = x4_tabs && flags[2] == 0;
-    c->compact = (flags[0] & ~(kCompactRingSea | kCompactDivisorRange | kCompactEdgeRingSea)) == 0;
+    c->x4_tab_ok = x4_tabs && (flags[2] & ~kCompactViscousRow) == 0;
+    // (the inviscid bodies: the block's rows, and the neighbours' rows in one_step_x4's tables)
+    c->rdiss_zero = ((flags[0] | flags[2]) & kCompactViscousRow) == 0;
+    c->compact = (flags[0] & ~(kCompactRingSea | kCompactDivisorRange | kCompactEdgeRingSea | kCompactViscousRow)) == 0;
     c->static_dirty = false;
     return OCN_OK;
 }

@@ -219,7 +219,7 @@ struct ocn_ctx {
     bool use_graph = false;
     // the launches a captured step replays depend on everything in its key (march and ring_sea
     // select launch forms and the ring launch; options that change them also drop the cache)
-    struct Graph { hipGraphExec_t exec; double tau; ocn::StepKind kind; bool compact, march, ring_sea; int role, kc_mode; };
+    struct Graph { hipGraphExec_t exec; double tau; ocn::StepKind kind; bool compact, march, ring_sea; int role, kc_mode; bool kc_nv; };
     std::vector<Graph> graphs;         // one captured step per key
     std::vector<void *> allocs;
     // per-stage HIP-event timing (OCN_OPT_STAGE_TIMING): pending (stage, start, stop) records
@@ -293,6 +293,12 @@ struct ocn_ctx {
     // non-uniform rest depth, read by the OCN_KC_KNOWN_HR variant) / kFbGeneral
     mutable int fb_state = 0;
     int kc_mode = 0;             // OCN_KC_* of the current call's one-pass launches
+    // OCN_OPT_INVISCID: the two-step launches' inviscid bodies (sw_kernels.hip MarchStep NV) where mu is
+    // +0.0 (fb_inviscid: the word after the verdict, learnt with fb_state) and every r_diss row +0.0f with
+    // finite metrics (rdiss_zero: Prepare).  kc_nv: this call's pairs run them (prepare_kc; with a
+    // communicator every rank's verdict: nv_dev_ok, check_coherence); nv_used: a pair of the last call did
+    bool inviscid = true, rdiss_zero = false, nv_dev_ok = false, kc_nv = false, nv_used = false;
+    mutable bool fb_inviscid = false;
     int32_t *d_fbz = nullptr;    // the check's verdict word
     // lazy call tail (OCN_OPT_LAZY_TAIL): the last step run was a one-pass step; what the reference's
     // last step leaves beyond the state (vort, stresses, RHS terms, hh_init's levels, a8's copies) is
@@ -380,7 +386,7 @@ inline bool is_alt_field(int id) { return id == OCN_SSHP || id == OCN_UBRTRP || 
 inline size_t field_bytes(const LBlock &b) { return (size_t)b.g.pitch * (b.g.bnd_y2 - b.g.bnd_y1 + 1) * 8; }
 inline bool has_comm(const ocn_ctx *c) { return c->comm || c->lb || c->comm_aborted; }
 // block b's one-pass variant for the current call (ctx kc_mode, the device verdict, its constants)
-inline OnepassKC kc_of(const ocn_ctx *c, const LBlock &b) { return OnepassKC{c->kc_mode, c->d_fbz, b.kc}; }
+inline OnepassKC kc_of(const ocn_ctx *c, const LBlock &b) { return OnepassKC{c->kc_mode, c->d_fbz, b.kc, c->kc_nv}; }
 
 // ---- ctx_comm.hip: halo plans, the RCCL / loopback transport, the watchdog
 int make_seglist(ocn_ctx *c, const std::vector<Seg> &v, SegList &out);
@@ -388,6 +394,9 @@ int launch_segs(const SegList &l, hipStream_t s, int32_t *cmp = nullptr);
 int get_plan(ocn_ctx *c, const std::vector<int> &fields, HaloPlan *&out, int depth = 1, int priv = 0);
 int run_sync(ocn_ctx *c, const std::vector<int> &fields, hipStream_t stream = nullptr, int32_t *cmp = nullptr,
              int depth = 1, int priv = 0);
+// d_nbad's words of the known-constant check (ctx_setup.hip allocate): the verdict the launches' gates read,
+// and right after it the word FallbackCheck ORs into when mu's one value is not +0.0 (flag[1]; the host's alone)
+constexpr int kFbzWord = 16, kFbzWords = 2;
 constexpr int kVoteWords = 8;   // the role-flip vote (check_coherence): one 0/1 word per condition
 int allreduce_max(ocn_ctx *c, int32_t *word, hipStream_t s, int words = 1);
 int nccl_rc(ncclResult_t r, const char *what);

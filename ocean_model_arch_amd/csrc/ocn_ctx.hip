@@ -441,7 +441,7 @@ static bool is_flip_field(int id)
 enum { kVoteIncoherent = 0, kVoteIneligible, kVoteUdiv, kVoteHhStale, kVoteX2, kVoteX4, kVoteOvSeq, kVoteOvOv,
        kVoteUsed };
 static_assert(kVoteUsed <= kVoteWords, "vote words");
-struct VoteIn { bool eligible, udiv_ok, hh_consistent, x2_ok, x4_ok; };
+struct VoteIn { bool eligible, udiv_ok, hh_consistent, x2_ok, x4_ok, nv_ok; };
 struct VoteOut { bool udiv_ok, hh_consistent, x2_ok, x4_ok; };
 
 // one_step_x2's condition on the state's halo points that no exchange fills (the rings 1 and 2 of a
@@ -506,7 +506,8 @@ static int check_coherence(ocn_ctx *c, const VoteIn &in, VoteOut &out)
     host[kVoteUdiv] = !in.udiv_ok;
     host[kVoteHhStale] = !in.hh_consistent;
     host[kVoteX2] = !in.x2_ok;
-    host[kVoteX4] = !in.x4_ok;
+    // (one word, reduced by maximum: 2 = no pairs here, 1 = pairs but not their inviscid bodies, 0 = both)
+    host[kVoteX4] = !in.x4_ok ? 2 : !in.nv_ok ? 1 : 0;
     host[kVoteOvSeq] = host[kVoteOvOv] = INT32_MAX;
     if (c->ov_state == 2) {   // both probe steps recorded (ov_begin): their times, in us
         float ms[2] = {0.f, 0.f};
@@ -545,7 +546,7 @@ static int check_coherence(ocn_ctx *c, const VoteIn &in, VoteOut &out)
     out.hh_consistent = w[kVoteHhStale] == 0;
     out.x2_ok = w[kVoteX2] == 0 && exch && c->x2;
     c->x2_dev_ok = out.x2_ok;
-    out.x4_ok = out.x2_ok && w[kVoteX4] == 0;
+    out.x4_ok = out.x2_ok && w[kVoteX4] < 2;
     if (w[kVoteOvSeq] != INT32_MAX && w[kVoteOvOv] != INT32_MAX) {   // every rank measured: the faster form
         c->ov_ms[0] = 1.0e-3 * w[kVoteOvSeq];
         c->ov_ms[1] = 1.0e-3 * w[kVoteOvOv];
@@ -555,6 +556,7 @@ static int check_coherence(ocn_ctx *c, const VoteIn &in, VoteOut &out)
         c->ov_state = 0;
     }
     c->x4_dev_ok = out.x4_ok;
+    c->nv_dev_ok = w[kVoteX4] == 0;   // every rank's pairs run the inviscid bodies, or none's
     return OCN_OK;
 }
 
@@ -1546,7 +1548,7 @@ extern "C++" int ocn::ctx_create(const ocn_basin *basin, const ocn_sw_params *sw
     if (!rc) rc = check_hip(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming), "hipEventCreate");
     if (!rc) rc = check_hip(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming), "hipEventCreate");
     if (!rc) rc = check_hip(hipEventCreateWithFlags(&c->ev_fb, hipEventDisableTiming), "hipEventCreate");
-    if (!rc) rc = check_hip(hipHostMalloc((void **)&c->h_fbz, sizeof(int32_t), hipHostMallocDefault), "hipHostMalloc");
+    if (!rc) rc = check_hip(hipHostMalloc((void **)&c->h_fbz, kFbzWords * sizeof(int32_t), hipHostMallocDefault), "hipHostMalloc");
     if (!rc) rc = decompose(c);
     if (!rc) rc = allocate(c);
     if (!rc) rc = prebuild_plans(c);
@@ -1857,7 +1859,7 @@ static int graph_step(ocn_ctx *c, double tau, const StepKind &k)
     c->hn_fresh = false;   // (a replay runs whatever the captured step ran)
     for (const auto &g : c->graphs)
         if (g.tau == tau && g.kind == k && g.compact == c->compact && g.march == c->march && g.ring_sea == c->ring_sea &&
-            g.role == c->role && g.kc_mode == c->kc_mode) {
+            g.role == c->role && g.kc_mode == c->kc_mode && g.kc_nv == c->kc_nv) {
             HIPCHK(hipGraphLaunch(g.exec, c->stream));
             if (k.rc) swap_sshp(c);
             if (k.one || k.one_last) swap_alt3(c);
@@ -1878,7 +1880,7 @@ static int graph_step(ocn_ctx *c, double tau, const StepKind &k)
     e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     HIPCHK(e);
-    c->graphs.push_back(ocn_ctx::Graph{exec, tau, k, c->compact, c->march, c->ring_sea, role, c->kc_mode});
+    c->graphs.push_back(ocn_ctx::Graph{exec, tau, k, c->compact, c->march, c->ring_sea, role, c->kc_mode, c->kc_nv});
     HIPCHK(hipGraphLaunch(exec, c->stream));
     return OCN_OK;
 }
@@ -1910,9 +1912,11 @@ static int alt_home(ocn_ctx *c)
 static void learn_fb(ocn_ctx *c)
 {
     if (c->fb_state != kFbDevice) return;
-    int32_t f = 0;
-    if (hipMemcpy(&f, c->d_fbz, sizeof(f), hipMemcpyDeviceToHost) != hipSuccess) return;
+    int32_t fv[kFbzWords] = {0, 0};   // the verdict, and the word after it: mu is not +0.0
+    if (hipMemcpy(fv, c->d_fbz, sizeof(fv), hipMemcpyDeviceToHost) != hipSuccess) return;
+    const int32_t f = fv[0];
     c->fb_state = f == 0 ? kFbZero : f == 1 ? kFbHr : kFbGeneral;
+    c->fb_inviscid = fv[1] == 0;
     c->fb_copy = false;
 }
 
@@ -1924,6 +1928,7 @@ static void learn_fb_async(ocn_ctx *c)
     if (c->fb_state != kFbDevice || !c->fb_copy || hipEventQuery(c->ev_fb) != hipSuccess) return;
     const int32_t f = *(volatile int32_t *)c->h_fbz;
     c->fb_state = f == 0 ? kFbZero : f == 1 ? kFbHr : kFbGeneral;
+    c->fb_inviscid = ((volatile int32_t *)c->h_fbz)[1] == 0;
     c->fb_copy = false;
 }
 
@@ -1941,13 +1946,27 @@ static int kc_of_fb(const ocn_ctx *c)
     return c->fb_state == kFbZero ? OCN_KC_KNOWN : c->fb_state == kFbHr ? OCN_KC_KNOWN_HR
          : c->fb_state == kFbGeneral ? OCN_KC_GENERAL : OCN_KC_DEVICE;
 }
+// The two-step launches' inviscid bodies (MarchStep NV) for a call whose variant is kc_mode: a known-
+// constant variant chosen on the host from a verdict that found mu = +0.0, with every r_diss row +0.0f
+// (never unchecked, after an upload, or with a raw r8 pointer handed out: kc_mode is then another);
+// with a communicator only where every rank voted so (check_coherence)
+static bool nv_local(const ocn_ctx *c)
+{
+    return c->inviscid && c->known_const && !c->r8_handed && c->rdiss_zero && c->fb_inviscid &&
+           (c->fb_state == kFbZero || c->fb_state == kFbHr);
+}
+static void set_kc_mode(ocn_ctx *c, int mode)
+{
+    c->kc_mode = mode;
+    c->kc_nv = (mode == OCN_KC_KNOWN || mode == OCN_KC_KNOWN_HR) && nv_local(c) && (!has_comm(c) || c->nv_dev_ok);
+}
 static int prepare_kc(ocn_ctx *c, bool x2 = false)
 {
-    if (!c->known_const || c->r8_handed) { c->kc_mode = OCN_KC_GENERAL; return OCN_OK; }
+    if (!c->known_const || c->r8_handed) { set_kc_mode(c, OCN_KC_GENERAL); return OCN_OK; }
     learn_fb_async(c);
     if (c->fb_state != kFbUnchecked && x2 && !c->fb_x2) c->fb_state = kFbUnchecked;
     if (c->fb_state == kFbUnchecked) {
-        HIPCHK(hipMemsetAsync(c->d_fbz, 0, sizeof(int32_t), c->stream));
+        HIPCHK(hipMemsetAsync(c->d_fbz, 0, kFbzWords * sizeof(int32_t), c->stream));   // (the verdict and the mu word)
         for (const LBlock &b : c->blocks) {
             std::vector<void *> tab = b.ptr;
             if (x2) tab[field_slot(OCN_HHQ_REST)] = b.hr_x;
@@ -1955,14 +1974,14 @@ static int prepare_kc(ocn_ctx *c, bool x2 = false)
             RC(launch_fallback_check(&b.g, tab.data(), b.bits, r, c->d_fbz, b.kc, c->stream, x2 ? b.own : 0u));
         }
         if (!c->capturing) {   // the verdict to pinned host memory, learn_fb_async
-            HIPCHK(hipMemcpyAsync(c->h_fbz, c->d_fbz, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(c->h_fbz, c->d_fbz, kFbzWords * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipEventRecord(c->ev_fb, c->stream));
             c->fb_copy = true;
         }
         c->fb_state = kFbDevice;
         c->fb_x2 = x2;
     }
-    c->kc_mode = kc_of_fb(c);
+    set_kc_mode(c, kc_of_fb(c));
     return OCN_OK;
 }
 
@@ -2062,7 +2081,7 @@ static int await_kc(ocn_ctx *c, bool x2, int nsteps)
     if (!pairs) return OCN_OK;
     HIPCHK(hipEventSynchronize(c->ev_fb));
     learn_fb_async(c);
-    c->kc_mode = kc_of_fb(c);
+    set_kc_mode(c, kc_of_fb(c));
     return OCN_OK;
 }
 
@@ -2155,7 +2174,7 @@ static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every
     if (nsteps == 0) return OCN_OK;
     // (RCCL / events stay outside graphs; so do the tracer steps' calls: their launches follow pending state)
     const bool graph_ok = c->use_graph && !has_comm(c) && !c->stage_timing && !(c->sw.use_tracers > 0 && c->tr_step);
-    c->pair_used = false;
+    c->pair_used = c->nv_used = false;
     c->co_used = false;
     c->multi_used = false;
     if (c->open) {
@@ -2178,6 +2197,7 @@ static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every
                     const StepKind k = continuing_pair(chk[i], chk[i + 1], c->open_x2);
                     rc = graph_ok ? graph_step(c, tau, k) : run_step(c, tau, k);
                     c->open_pair = c->pair_used = true;
+                    if (!k.one_last) c->nv_used = c->kc_nv;   // (a pair whose second step is the call's last runs the full body)
                 }
                 if (rc == OCN_OK) {
                     c->deferred = (int)(chk.size() - i);   // 1 or 2
@@ -2220,7 +2240,7 @@ static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every
     int N = lazy_cand ? nsteps + 1 : nsteps;
     if (N >= 2 && (eligible || (has_comm(c) && c->flip)) && !c->coherent_known) {
         VoteOut v;
-        RC(check_coherence(c, VoteIn{eligible, c->udiv_ok, c->hh_consistent, x2_here, x4_here}, v));
+        RC(check_coherence(c, VoteIn{eligible, c->udiv_ok, c->hh_consistent, x2_here, x4_here, nv_local(c)}, v));
         udiv_ok = v.udiv_ok;
         first_one = v.hh_consistent;
         x2_ok = x2_here && v.x2_ok;
@@ -2321,6 +2341,7 @@ static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every
             k.next_a = k.next_reuse = false;
             ++s;
             c->pair_used = true;
+            if (!k.one_last) c->nv_used = c->kc_nv;   // (launch_onepass_pair: the full body with last)
         }
         rc = graph_ok ? graph_step(c, tau, k) : run_step(c, tau, k);
     }
@@ -2553,6 +2574,7 @@ int ocn_ctx_set_option(ocn_ctx *c, int32_t key, int64_t value)
         c->hrx_ok = false;   // (h_r's copy 2 or 4 rings deep: refresh_hrx)
         return OCN_OK;
     case OCN_OPT_CO_LAUNCH: c->co_launch = value != 0; return OCN_OK;
+    case OCN_OPT_INVISCID: c->inviscid = value != 0; return OCN_OK;   // (prepare_kc: from the next call on)
     case OCN_OPT_BATCH:
         if (c->batch != (value != 0)) drop_graphs(c);
         c->batch = value != 0;
@@ -2598,6 +2620,7 @@ int ocn_ctx_get_option(const ocn_ctx *c, int32_t key, int64_t *value)
     case OCN_OPT_X4: *value = c->x4_used ? 2 : c->x4 ? 1 : 0; return OCN_OK;
     case OCN_OPT_CO_LAUNCH: *value = c->co_used ? 2 : c->co_launch; return OCN_OK;
     case OCN_OPT_XCHG_DELAY: *value = c->xdelay_us; return OCN_OK;
+    case OCN_OPT_INVISCID: *value = c->nv_used ? 2 : c->inviscid; return OCN_OK;
     default: return set_error(OCN_ERR_ARG, "unknown option");
     }
 }

@@ -137,9 +137,12 @@ int launch_fill_field(const ocn_block &g, double *p, double v, hipStream_t s);
 // OCN_KC_KNOWN takes them as +0.0 / the uniform values kc[0], kc[1] (device memory, written by
 // launch_fallback_check); OCN_KC_KNOWN_HR the same but reads h_r (a non-uniform rest depth:
 // topography); OCN_KC_DEVICE launches all three, each running only if the device verdict *flag
-// (launch_fallback_check's: bit 0 h_r varies, bit 1 anything else) is its own -- no host wait.
+// (launch_fallback_check's: bit 0 h_r varies, bit 1 anything else) is its own -- no host wait.  The
+// word after it, flag[1]: nonzero if mu's one value is not +0.0 (read by the host only).
+// nv (OCN_KC_KNOWN / OCN_KC_KNOWN_HR chosen on the host): mu is +0.0 and every r_diss row +0.0f -- the
+// two-step launches run their inviscid bodies (MarchStep NV: no viscous or friction terms formed)
 enum { OCN_KC_GENERAL = 0, OCN_KC_KNOWN = 1, OCN_KC_DEVICE = 2, OCN_KC_KNOWN_HR = 3 };
-struct OnepassKC { int mode; const int32_t *flag; const double *kc; };
+struct OnepassKC { int mode; const int32_t *flag; const double *kc; bool nv = false; };
 // own (sw_stencils.h own_class bits, not with last): the halo points neighbour blocks own hold the
 // neighbours' state two points deep -- D there is formed as on their interior (MarchStep X2).
 // frame_of: only the part of the range outside *frame_of, as up to 4 bands in one launch
@@ -274,6 +277,7 @@ int launch_tracer_coherence(const ocn_block *b, void *const *ptr, const uint8_t 
 // Prepare's flag bit reporting mask bits on the halo ring (sw_stencils.h OCN_COMPACT_RING_SEA)
 constexpr int kCompactRingSea = 4;
 constexpr int kCompactDivisorRange = 8;   // sw_stencils.h OCN_COMPACT_DIVISOR_RANGE
+constexpr int kCompactViscousRow = 32;    // sw_stencils.h OCN_COMPACT_VISCOUS_ROW
 
 // Block batching (sw_kernels.hip): while a Batcher is active on this thread, the launches of the
 // march / range / frame kernels are collected per kernel type instead of issued, and batch_end

@@ -1781,6 +1781,12 @@ constexpr int kStepLdsRows = 4 * OCN_STEP_ROWS + 4 > OCN_PAIR_MAX_ROWS + 10 ? 4 
 
 __shared__ double g_step_rc[kStepLdsRows * kRowC];   // the workgroup's rows [nb - 2, ne + 2]
 __shared__ unsigned g_step_rlo;                       // table row of its first row
+// The inviscid bodies' table (MarchStep NV): the 17 row constants their hot path reads -- the viscous
+// and friction terms' ten (RC_RAT0..3, RC_DY2, RC_DX2, RC_DXB2, RC_DYB2, RC_RDSELF, RC_RDNEXT) are left
+// out; their exact re-run forms those from scalar loads of the row table (StepRegs::cst<0>)
+constexpr int kRowCNV = 17;
+constexpr int nv_col(int k) { return k <= RC_RDYB ? k : k == RC_RLH ? 14 : k == RC_AREA ? 15 : k == RC_RAREA ? 16 : -1; }
+__shared__ double g_step_rc_nv[kStepLdsRows * kRowCNV];
 // Two steps per launch (MarchStep PAIR): the producer waves' new state (ssh, sshp, ubrtr, ubrtrp,
 // vbrtr, vbrtrp after the first step, by row mod 4) for the consumer waves.
 // (Measured and dropped: a wave's 60-column output rows stored as whole 128-B lines through LDS,
@@ -1884,13 +1890,16 @@ struct StepRegs {
     int32_t *nbp;                      // where this wave's check_ssh_err count goes (null: unchecked)
     bool cnt;                          // the point is counted (PAIR producers: their workgroup's points only)
     int pj;                            // PAIR: the lane's column in the workgroup's LDS ring
+    bool big;                          // NV: a state value this lane took was not below 2^300 (MarchStep::guard)
     double fyx, fyy, vht, a2t;         // row n-1's n faces (MarchStep::face)
     double hr0, mu0;                   // known-constant variant: the uniform h_r and mu (MarchStep::kc)
     const __attribute__((address_space(3))) double *lds;   // (kLds) the workgroup's row constants
     unsigned rlo;                                            // table row of lds row 0
-    // row constant k (RowC) of row n + dy, from LDS or from scalar loads
-    template <bool LDS> __device__ __forceinline__ double cst(int k, int dy) const
+    // row constant k (RowC) of row n + dy: LDS = 1 from the LDS table, 2 from the inviscid bodies' table
+    // (nv_col: a constant it leaves out is never asked of it), 0 from scalar loads
+    template <int LDS> __device__ __forceinline__ double cst(int k, int dy) const
     {
+        if (LDS == 2) return lds[(rn + dy - rlo) * kRowCNV + nv_col(k)];
         if (LDS) return lds[(rn + dy - rlo) * kRowC + k];
         switch (k) {   // the same values from scalar loads of the row table
         case RC_RDXT: return rc(OCN_RC_DXT, dy);
@@ -1996,10 +2005,39 @@ struct StepRegs {
 // exchange before it delivered the state 4 points deep, the producers update the halo points
 // neighbours own 2 deep as those neighbours do (their D 3 deep, from the state 4 deep); the known-
 // constant variant only (h_r, mu, the forcing and the fallback values are not read).
-template <bool P2, bool LAST = false, bool ZF = false, bool X2 = false, bool HR = false, bool PAIR = false,
-          bool WT = false>
-struct MarchStep {
+// NV (ZF, not LAST; the two-step bodies get it): the inviscid body.  With mu = +0.0 at every point (kc[1]'s
+// bits are zero) and r_diss = +0.0f in every row (launch_prepare), every product of a6 uv_diff2 and of
+// a7's friction has a zero factor, so where every other operand is finite
+//   1. each of those products is +-0, each quotient of one is +-0, and rxd, ryd and both fric are +-0;
+//   2. ZF's rhsx / rhsy is the literal +0.0 and is added first, so rhsx + slx is never -0 (+0 + -0 = +0);
+//   3. a value that is not -0 is unchanged by adding +-0; the next partial sum (with rxa) is -0 only if
+//      both addends are, so it is not -0 either, and subtracting +-0 from it changes nothing:
+//      ((((+0 + slx) + rxd) + rxa) - fric) +- c  ==  ((+0 + slx) + rxa) +- c  bit for bit
+//   (enumerated on the host over signed zeros, denormals and huge values: tests/test_inviscid_cpu.py;
+//   without the leading +0.0 it is false -- -0 + -0 + -0 is not -0 + +0 -- so never the general variant).
+// The body therefore forms none of a5's stresses, a6's products and quotients, the friction, their
+// dividends' range checks and the lane shifts and LDS reads that feed them: grx = rhsx + slx + rxa +
+// (cx + cx') / 4, gry = rhsy + sly + rya - (c1 + c1') / 4.
+// The guard: 0 * inf and 0 * nan are NaN in the reference, so the identity needs finite operands.
+// Every operand of a dropped product is a product, sum or quotient of the six state values of the
+// rows n-1 .. n+2, h_r and the metrics (finite, their ratios finite: launch_prepare); with the state
+// and h_r below 2^300 in magnitude all of them are finite.  A wave sums the six |x| of every row it
+// takes (take: from memory or from the ring; NaN and inf propagate through the sum) and compares
+// once; a failing lane stays failed for the rest of the tile (StepRegs::big), and its wave then runs
+// each row again in full as the full body runs it (iteration: step<false, PH, true> -- udiv with all
+// its range checks, derive's dropped checks too -- then the IEEE re-run if they ask for it), the
+// stresses formed again from the state ring (viscous): nothing is carried from rows of the short
+// form.  The same full IEEE re-run (step<true>) serves a kept dividend out of udiv's range.  Why udiv
+// first: udiv of an infinite dividend is NaN where the IEEE quotient is infinite, so a marked wave
+// must divide as the full body does for the two to agree byte for byte on non-finite state.
+// Dropping the range checks of the dropped dividends changes no kept value on finite state: udiv
+// and the IEEE division agree wherever a kept dividend is in range, which its own check still tests.
+// (MarchStepT: the body with NV; MarchStep below names the bodies without it, so that their kernels keep
+// their symbols -- the committed counter summaries are keyed by them, ocean_model_arch_amd/_codeobj.py)
+template <bool P2, bool LAST, bool ZF, bool X2, bool HR, bool PAIR, bool WT, bool NV>
+struct MarchStepT {
     static_assert(!PAIR || !X2 || (ZF && !LAST), "two-step launches with exchanges: the known-constant variants");
+    static_assert(!NV || (ZF && !LAST), "the inviscid body: a known-constant variant, not a last step");
     static constexpr int kStAux = WT ? 16 : 0;
     static constexpr bool kPair = PAIR;
     static constexpr bool kX2 = X2;
@@ -2076,6 +2114,17 @@ struct MarchStep {
         x.bits.s<PH>(3) = q.bits;
         x.v.s<PH>(2) = q.v; x.vp.s<PH>(2) = q.vp; x.mu.s<PH>(2) = q.mu;
         x.rhsx = q.rhsx; x.rhsy = q.rhsy;
+        if constexpr (NV) guard(x, q.u, q.up, q.ssh, q.shp, q.v, q.vp, q.hr);
+    }
+    // NV: the row's state (and h_r where it is read) finite and below 2^300, or the lane is marked for
+    // good (see MarchStep) -- the sum of the magnitudes: inf and NaN propagate, one compare
+    __device__ __forceinline__ static void guard(StepRegs &x, double a, double b, double c, double d, double e, double f,
+                                                 double hr)
+    {
+        double s = __builtin_fabs(a) + __builtin_fabs(b) + __builtin_fabs(c) + __builtin_fabs(d) + __builtin_fabs(e) +
+                   __builtin_fabs(f);
+        if (HR) s += __builtin_fabs(hr);
+        x.big = x.big || !(s < 0x1p300);
     }
 
     // hh_init's interpolation weights of row n + dy (slot dy + 1): interp_wt(h) = h * dx * dy * lu
@@ -2182,14 +2231,25 @@ struct MarchStep {
         if (!E) exp_check(acc, sh);
         if (!E) {   // (a / g1) / g2: a's range bounds a / g1's (|g1| <= 2^60)
             exp_check(acc, a_u0); exp_check(acc, a_v0); exp_check(acc, a_h0); exp_check(acc, a_u1);
-            exp_check(acc, a_v1); exp_check(acc, x.up.s<PH>(2)); exp_check(acc, x.vp.s<PH>(2)); exp_check(acc, x.up.s<PH>(3));
+            exp_check(acc, a_v1);
+            if (!NV) { exp_check(acc, x.up.s<PH>(2)); exp_check(acc, x.vp.s<PH>(2)); exp_check(acc, x.up.s<PH>(3)); }
         }
         // the nine first quotients (hh_init's five, a5's four) at once, then the five second ones
         // (each stage of udiv issued for all of them: independent chains in flight together)
+        // NV: hh_init's five only (a5's stresses are formed by no row of the short form)
         double q1[9], q2[5];
-        dvn<E, 9>({a_u0, a_v0, a_h0, a_u1, a_v1, x.up.s<PH>(2), x.vp.s<PH>(2), x.up.s<PH>(3), x.vp.s<PH>(2)},
-                  {dxt, dxh, dxb, dxt, dxh, dyh, dxh, x.cst<kLds>(RC_DXT, 2), dyt},
-                  {rxt, rxh, x.cst<kLds>(RC_RDXB, 1), rxt, rxh, ryh, rxh, x.cst<kLds>(RC_RDXT, 2), ryt}, q1);
+        if constexpr (NV) {
+            double q5[5];
+            dvn<E, 5>({a_u0, a_v0, a_h0, a_u1, a_v1}, {dxt, dxh, dxb, dxt, dxh},
+                      {rxt, rxh, x.cst<kLds>(RC_RDXB, 1), rxt, rxh}, q5);
+#pragma unroll
+            for (int i = 0; i < 5; ++i) q1[i] = q5[i];
+            q1[5] = q1[6] = q1[7] = q1[8] = 0.0;
+        } else {
+            dvn<E, 9>({a_u0, a_v0, a_h0, a_u1, a_v1, x.up.s<PH>(2), x.vp.s<PH>(2), x.up.s<PH>(3), x.vp.s<PH>(2)},
+                      {dxt, dxh, dxb, dxt, dxh, dyh, dxh, x.cst<kLds>(RC_DXT, 2), dyt},
+                      {rxt, rxh, x.cst<kLds>(RC_RDXB, 1), rxt, rxh, ryh, rxh, x.cst<kLds>(RC_RDXT, 2), ryt}, q1);
+        }
         dvn<E, 5>({q1[0], q1[1], q1[2], q1[3], q1[4]}, {dyh, dyt, dyb, dyh, dyt},
                   {ryh, ryt, x.cst<kLds>(RC_RDYB, 1), ryh, ryt}, q2);
         const double u0 = q2[0], v0 = q2[1], h0 = q2[2], u1 = q2[3], v1 = q2[4];
@@ -2203,8 +2263,11 @@ struct MarchStep {
         // is the previous row's, up/dxt at n+1 the next row's (formed here, kept for the next
         // row), vp/dyt at m+1 the right lane's -- the same operands, so the same values
         const double qa = q1[5], qb = q1[6], qc1 = q1[7], qe = q1[8];
-        const double st = x.cst<kLds>(RC_RAT0, 1) * (qa - shz(qa, -1)) - x.cst<kLds>(RC_RAT1, 1) * (qb - x.qb);
-        const double ss = x.cst<kLds>(RC_RAT2, 1) * (qc1 - x.qc) + x.cst<kLds>(RC_RAT3, 1) * (shz(qe, 1) - qe);
+        double st = 0.0, ss = 0.0;
+        if constexpr (!NV) {
+            st = x.cst<kLds>(RC_RAT0, 1) * (qa - shz(qa, -1)) - x.cst<kLds>(RC_RAT1, 1) * (qb - x.qb);
+            ss = x.cst<kLds>(RC_RAT2, 1) * (qc1 - x.qc) + x.cst<kLds>(RC_RAT3, 1) * (shz(qe, 1) - qe);
+        }
         qb_next = qb;
         qc_next = qc1;
         const double hu = fb.llu ? u0 : fb.hu;
@@ -2212,10 +2275,13 @@ struct MarchStep {
         const double hh = fb.luh ? h0 : fb.hh;
         const double vt = fb.vt ? vort : fb.vort;
         const double stt = fb.st ? st : fb.stt;
-        x.hu.s<PH>(2) = hu; x.hv.s<PH>(2) = hv; x.hh.s<PH>(2) = hh; x.vort.s<PH>(2) = vt; x.stt.s<PH>(2) = stt;
+        x.hu.s<PH>(2) = hu; x.hv.s<PH>(2) = hv; x.hh.s<PH>(2) = hh; x.vort.s<PH>(2) = vt;
         x.hu1.s<PH>(2) = fb.llu ? u1 : fb.hu1;
         x.hv1.s<PH>(2) = fb.llv ? v1 : fb.hv1;
-        x.sts.s<PH>(2) = fb.ss ? ss : fb.sts;
+        if constexpr (!NV) {
+            x.stt.s<PH>(2) = stt;
+            x.sts.s<PH>(2) = fb.ss ? ss : fb.sts;
+        }
         // shared products of row r (S reads them at m +- 1 and at rows n-1 .. n+1); each is the
         // reference's sub-expression with the same operands in the same order
         x.pu.s<PH>(2) = u_0 * dyh * hu;                                  // uv_trans: u * dyh * hu
@@ -2226,7 +2292,9 @@ struct MarchStep {
         x.rr.s<PH>(2) = rr;
         x.cx.s<PH>(2) = rr * (v_r + v_0);                                //   ... * (vbrtr(1,0) + vbrtr)
         const double hq = x.hr.s<PH>(2) + x.ssh.s<PH>(2);                    // depth.f90:48 hq = h_r + sh*ffs (ffs = 1)
-        if constexpr (kLds) {   // (the LDS rows hold dy**2 * mu, dx**2 * mu: prologue)
+        if constexpr (NV) {   // (uv_diff2's products: the exact re-run forms them itself, step<true>)
+            (void)hq; (void)stt;
+        } else if constexpr (kLds) {   // (the LDS rows hold dy**2 * mu, dx**2 * mu: prologue)
             x.dt.s<PH>(2) = x.cst<kLds>(RC_DY2, 1) * hq * stt;
             x.dxq.s<PH>(2) = x.cst<kLds>(RC_DX2, 1) * hq * stt;
         } else {
@@ -2245,11 +2313,63 @@ struct MarchStep {
         x.fyx = (pv + shz(pv, 1)) / 2.0 * (u_n + u) / 2.0 * luu;
         x.vht = x.vh.s<PH>(1) * (v_r + v);
         x.fyy = (pv + pvn) / 2.0 * (v + v_n) / 2.0;
-        if constexpr (ZF) {   // (uv_diff2_math's muh_p with mu one value: its lane shifts are the value)
+        if constexpr (ZF && !NV) {   // (uv_diff2_math's muh_p with mu one value: its lane shifts are the value)
             const double mu = x.mu.s<PH>(1), mu_n = x.mu.s<PH>(2), muh_p = (mu + mu + mu_n + mu_n) / 4.0;
             (void)muh_p;   // (kLds = ZF: the LDS row holds dxb**2 * muh)
             x.a2t = x.cst<kLds>(RC_DXB2, 0) * x.hh.s<PH>(1) * x.sts.s<PH>(1);
         }
+    }
+
+    // NV, the exact re-run of S(n): a5's stresses of rows n-1 .. n+1 from the state ring (the quotients
+    // and differences derive forms row by row in the other bodies, on the same operands; the ZF
+    // fallback values +0.0 where D takes the array's) and a6 uv_diff2 over them as face / step form it,
+    // with a1's quotient -- IEEE divisions; the row constants the NV table leaves out from scalar loads,
+    // multiplied by mu / muh as the other bodies' prologue multiplies them.  E as in step: udiv with the range
+    // checks of a1 .. a4, or IEEE divisions -- whichever the full body runs on this row, so that where the state
+    // is not finite (udiv of an infinite dividend is NaN, the IEEE quotient infinite) the two bodies agree.
+    // Only a1's quotient is exactly the full body's by that choice.  The stresses of rows n-1 .. n+1 the full
+    // body formed one per derive iteration, each under that iteration's own E; here all three take this row's.
+    // That is the same result ONLY because mu0 = +0.0 multiplies every one of them: on finite state udiv and
+    // IEEE give the same quotient in range and, out of it, a finite stress either way, whose product with 0
+    // is +-0 and cannot change the sums (MarchStepT); on non-finite state inf and NaN both become NaN under
+    // 0 * x.  With a non-zero mu this function would NOT reproduce the full body -- the NV bodies never run then.
+    template <bool E, int PH>
+    __device__ __forceinline__ void viscous(const StepRegs &x, int m, int n, double a_ssh, int &acc, double &q_ssh,
+                                            double &rxd, double &ryd) const
+    {
+        auto C = [&](int k, int dy) { return x.cst<0>(k, dy); };
+        auto Q = [&](double a, int k, int rk, int dy) { return dv<E>(a, C(k, dy), C(rk, dy)); };   // a / row constant k
+        const double mu0 = x.mu0, muh = (mu0 + mu0 + mu0 + mu0) / 4.0;
+        auto str_t = [&](int dy) {   // row n + dy (slot dy + 1), dy = 0, 1
+            const int k = dy + 1;
+            const double qa = Q(x.up.s<PH>(k), RC_DYH, RC_RDYH, dy), qb = Q(x.vp.s<PH>(k), RC_DXH, RC_RDXH, dy),
+                         qbm = Q(x.vp.s<PH>(k - 1), RC_DXH, RC_RDXH, dy - 1);
+            const double st = C(RC_RAT0, dy) * (qa - shz(qa, -1)) - C(RC_RAT1, dy) * (qb - qbm);
+            Fallback f;
+            fallback<PH, 0>(x, f, m, n + dy, k);
+            return f.st ? st : 0.0;
+        };
+        auto str_s = [&](int dy) {   // dy = -1, 0
+            const int k = dy + 1;
+            const double qc1 = Q(x.up.s<PH>(k + 1), RC_DXT, RC_RDXT, dy + 1), qc = Q(x.up.s<PH>(k), RC_DXT, RC_RDXT, dy),
+                         qe = Q(x.vp.s<PH>(k), RC_DYT, RC_RDYT, dy);
+            const double ss = C(RC_RAT2, dy) * (qc1 - qc) + C(RC_RAT3, dy) * (shz(qe, 1) - qe);
+            Fallback f;
+            fallback<PH, 0>(x, f, m, n + dy, k);
+            return f.ss ? ss : 0.0;
+        };
+        const double stt0 = str_t(0), stt1 = str_t(1), sts0 = str_s(0), stsm = str_s(-1);
+        const double hq0 = x.hr.s<PH>(1) + x.ssh.s<PH>(1), hq1 = x.hr.s<PH>(2) + x.ssh.s<PH>(2);
+        const double dtc = C(RC_DY2, 0) * mu0 * hq0 * stt0;
+        const double dxq0 = C(RC_DX2, 0) * mu0 * hq0 * stt0, dxq1 = C(RC_DX2, 1) * mu0 * hq1 * stt1;
+        const double hh = x.hh.s<PH>(1);
+        const double a2p = C(RC_DXB2, 0) * muh * hh * sts0, a2t = C(RC_DXB2, -1) * muh * x.hh.s<PH>(0) * stsm;
+        const double a4p = C(RC_DYB2, 0) * muh * hh * sts0;
+        const double a1 = shz(dtc, 1) - dtc, a2 = a2p - a2t, a3 = dxq1 - dxq0, a4 = a4p - shz(a4p, -1);
+        if (!E) { exp_check(acc, a1); exp_check(acc, a2); exp_check(acc, a3); exp_check(acc, a4); }
+        q_ssh = Q(a_ssh, RC_AREA, RC_RAREA, 0);
+        rxd = Q(a1, RC_DYH, RC_RDYH, 0) + Q(a2, RC_DXT, RC_RDXT, 0);
+        ryd = -Q(a3, RC_DXH, RC_RDXH, 0) + Q(a4, RC_DYT, RC_RDYT, 0);
     }
 
     // a row's outputs and where they are stored (store_out, after S's branch)
@@ -2261,10 +2381,13 @@ struct MarchStep {
     };
     // S at row n: a1, fused B, a8's filters, check_ssh_err (sw_stencils.h sw_update_ssh_math,
     // uv_trans_math, uv_diff2_math, sw_update_uv_math written out over the shared products)
-    template <bool E, int PH>
+    // FULL (NV bodies; the others always): with the viscous and friction terms -- the short form where it is false
+    // RE: a re-run of the row (it corrects the first pass's check_ssh_err count)
+    template <bool E, int PH, bool FULL = true, bool RE = E>
     __device__ __forceinline__ void step(const StepRegs &x, const Lane &L, int n, int &acc, bool &bad, Out &o) const
     {
         (void)n;
+        constexpr bool kShort = NV && !FULL;
         const double u = x.u.s<PH>(1), v = x.v.s<PH>(1), hu = x.hu.s<PH>(1), hv = x.hv.s<PH>(1), hh = x.hh.s<PH>(1);
         const double dxt = x.cst<kLds>(RC_DXT, 0), dyt = x.cst<kLds>(RC_DYT, 0), dxh = x.cst<kLds>(RC_DXH, 0),
                      dyh = x.cst<kLds>(RC_DYH, 0);
@@ -2300,9 +2423,15 @@ struct MarchStep {
             o.fyy = fy_p;
         }
         // a6 uv_diff2 (vel_ssh.f90:375-452)
-        double rxd, ryd;
+        double rxd = 0.0, ryd = 0.0;
         double q_ssh = 0.0;   // a1's a_ssh / area
-        {
+        if constexpr (kShort) {   // a1's quotient alone
+            double qd[1];
+            dvn<E, 1>({a_ssh}, {x.cst<kLds>(RC_AREA, 0)}, {x.cst<kLds>(RC_RAREA, 0)}, qd);
+            q_ssh = qd[0];
+        } else if constexpr (NV) {
+            viscous<E, PH>(x, L.m, n, a_ssh, acc, q_ssh, rxd, ryd);
+        } else {
             // ZF: mu is one value over the step's reach, so its neighbours are that value (the lane
             // shifts differ only on the edge lanes, which produce no output and whose mu terms no
             // other lane reads) and the three averages are one loop-invariant value
@@ -2353,9 +2482,14 @@ struct MarchStep {
                 const double bp0 = qtau(x, x.hu1.s<PH>(1) * dxt * dyh / 2.0);
                 const double slx = -(g * (shz(ssh, 1) - ssh) * dyh * hu);
                 // (rdis + rdis) / 2 (kLds: the LDS row holds it halved)
-                const double fric = (kLds ? x.cst<kLds>(RC_RDSELF, 0) : x.cst<kLds>(RC_RDSELF, 0) / 2.0) * x.up.s<PH>(1) * dxt *
-                                    dyh * hu;
-                const double grx = x.rhsx + slx + rxd + rxa - fric + (x.cx.s<PH>(1) + x.cx.s<PH>(0)) / 4.0;
+                double grx;
+                if constexpr (kShort) {   // (rxd and fric are +-0: see MarchStep)
+                    grx = x.rhsx + slx + rxa + (x.cx.s<PH>(1) + x.cx.s<PH>(0)) / 4.0;
+                } else {
+                    const double fric = (kLds == 1 ? x.cst<kFull>(RC_RDSELF, 0) : x.cst<kFull>(RC_RDSELF, 0) / 2.0) *
+                                        x.up.s<PH>(1) * dxt * dyh * hu;
+                    grx = x.rhsx + slx + rxd + rxa - fric + (x.cx.s<PH>(1) + x.cx.s<PH>(0)) / 4.0;
+                }
                 un = (x.up.s<PH>(1) * bp0 + grx) / (bp);
             }
             {
@@ -2363,10 +2497,15 @@ struct MarchStep {
                 const double bp0 = qtau(x, x.hv1.s<PH>(1) * dyt * dxh / 2.0);
                 const double sly = -(g * (x.ssh.s<PH>(2) - ssh) * dxh * hv);
                 // (rdis + rdis(n+1)) / 2 (kLds: halved in the LDS row)
-                const double fric = (kLds ? x.cst<kLds>(RC_RDNEXT, 0) : x.cst<kLds>(RC_RDNEXT, 0) / 2.0) * x.vp.s<PH>(1) * dxh *
-                                    dyt * hv;
                 const double c1 = x.rr.s<PH>(1) * (u_n + u);
-                const double gry = x.rhsy + sly + ryd + rya - fric - (c1 + shz(c1, -1)) / 4.0;
+                double gry;
+                if constexpr (kShort) {
+                    gry = x.rhsy + sly + rya - (c1 + shz(c1, -1)) / 4.0;
+                } else {
+                    const double fric = (kLds == 1 ? x.cst<kFull>(RC_RDNEXT, 0) : x.cst<kFull>(RC_RDNEXT, 0) / 2.0) *
+                                        x.vp.s<PH>(1) * dxh * dyt * hv;
+                    gry = x.rhsy + sly + ryd + rya - fric - (c1 + shz(c1, -1)) / 4.0;
+                }
                 vn = (x.vp.s<PH>(1) * bp0 + gry) / (bp);
             }
         }
@@ -2385,9 +2524,9 @@ struct MarchStep {
             o.vort = x.vort.s<PH>(1); o.sts = x.sts.s<PH>(1); o.stt = x.stt.s<PH>(1);
             o.rxa = rxa; o.rxd = rxd; o.rya = rya; o.ryd = ryd;
         }
-        // check_ssh_err counts each point once: the re-run (E) corrects the first pass's count
+        // check_ssh_err counts each point once: a re-run (RE) corrects the first pass's count
         const bool bd = o.lu && !(sshn < 10000.0 && sshn > -10000.0);
-        if (__builtin_expect(x.nbp && x.cnt && bd != (E && bad), 0)) atomicAdd(x.nbp, bd ? 1 : -1);
+        if (__builtin_expect(x.nbp && x.cnt && bd != (RE && bad), 0)) atomicAdd(x.nbp, bd ? 1 : -1);
         bad = bd;
     }
 
@@ -2440,12 +2579,15 @@ struct MarchStep {
     // row constants in LDS: the known-constant variant (the general one keeps scalar loads of the row
     // table -- with its loaded h_r, mu, forcing and fallback values the LDS operands spill VGPRs:
     // 0.83 vs 0.64 ms at 4096^2)
-    static constexpr bool kLds = ZF;
+    // (StepRegs::cst's table: 0 scalar loads, 1 the LDS table, 2 the inviscid bodies' LDS table; kFull: where
+    // the ten constants that table leaves out come from)
+    static constexpr int kLds = NV ? 2 : ZF ? 1 : 0;
+    static constexpr int kFull = NV ? 0 : kLds;
     // the march unrolled over the register ring (StepRegs::Win) -- the known-constant variant; the
     // general one (loaded h_r, mu, forcing, fallback values) keeps the rotating loop: unrolled,
     // its scalar and vector registers spill
     static constexpr bool kUnroll = ZF;
-    static constexpr bool kPrologue = kLds;
+    static constexpr bool kPrologue = kLds != 0;
     // the row constants of the workgroup's rows into LDS (rows fit: launch_step's tiles have at
     // most OCN_STEP_ROWS rows)
     __device__ void prologue(const MarchRect &R, int ty) const
@@ -2463,11 +2605,16 @@ struct MarchStep {
             const double mu0 = kc[1], muh = (mu0 + mu0 + mu0 + mu0) / 4.0;
 #pragma unroll
             for (int k = 0; k < kRowC; ++k) {
-                double v = row_const(t.rows, t.nrows, r, k);
-                if (k == RC_DY2 || k == RC_DX2) v = v * mu0;
-                else if (k == RC_DXB2 || k == RC_DYB2) v = v * muh;
-                else if (k == RC_RDSELF || k == RC_RDNEXT) v = v / 2.0;
-                g_step_rc[i * kRowC + k] = v;
+                if constexpr (NV) {   // its 17 columns (no product with mu or r_diss among them)
+                    (void)muh;
+                    if (nv_col(k) >= 0) g_step_rc_nv[i * kRowCNV + nv_col(k)] = row_const(t.rows, t.nrows, r, k);
+                } else {
+                    double v = row_const(t.rows, t.nrows, r, k);
+                    if (k == RC_DY2 || k == RC_DX2) v = v * mu0;
+                    else if (k == RC_DXB2 || k == RC_DYB2) v = v * muh;
+                    else if (k == RC_RDSELF || k == RC_RDNEXT) v = v / 2.0;
+                    g_step_rc[i * kRowC + k] = v;
+                }
             }
         }
         if (threadIdx.x == 0) g_step_rlo = (unsigned)lo;
@@ -2510,7 +2657,8 @@ struct MarchStep {
         x.nbp = RO == 2 ? nbad2 : nbad;
         x.cnt = true;
         x.pj = L.j;
-        if (kLds) x.lds = (const __attribute__((address_space(3))) double *)g_step_rc;
+        if constexpr (NV) x.lds = (const __attribute__((address_space(3))) double *)g_step_rc_nv;
+        else if constexpr (kLds != 0) x.lds = (const __attribute__((address_space(3))) double *)g_step_rc;
         x.rows = (const __attribute__((address_space(4))) float *)t.rows;
         x.rcp = (const __attribute__((address_space(4))) double *)(t.rows + recip_offset(t.nrows));
         x.nrows = t.nrows;
@@ -2536,6 +2684,10 @@ struct MarchStep {
             }
             x.hr.s<0>(2) = ZF && !HR ? x.hr0 : ld(t.f(OCN_HHQ_REST), c1);
             x.bits.s<0>(2) = ld(t.bits, c1);
+            if constexpr (NV) {   // these rows' part in the guard (the uniform h_r once)
+                x.big = !HR && !(__builtin_fabs(x.hr0) < 0x1p300);
+                guard(x, x.up.s<0>(2), x.ssh.s<0>(2), x.shp.s<0>(2), x.u.s<0>(2), x.vp.s<0>(1), 0.0, x.hr.s<0>(2));
+            }
         }
         Fallback fb;
         fallback<0, RO>(x, fb, L.m, n0 + 1, 2);
@@ -2546,8 +2698,10 @@ struct MarchStep {
         if constexpr (PAIR && RO == 1 && kPrologue) pair_barrier();
         if (kLds) x.rlo = g_step_rlo;
         // the shared stress quotients of rows n0 (vp/dxh) and n0+1 (up/dxt)
-        x.qb = x.vp.s<0>(1) / x.cst<kLds>(RC_DXH, 0);
-        x.qc = x.up.s<0>(2) / x.cst<kLds>(RC_DXT, 1);
+        if constexpr (!NV) {
+            x.qb = x.vp.s<0>(1) / x.cst<kLds>(RC_DXH, 0);
+            x.qc = x.up.s<0>(2) / x.cst<kLds>(RC_DXT, 1);
+        }
         weights<0>(x, 1);
         if (RO != 1) store_out(Out{}, 0u);   // every lane dropped: the loop entry has six stores after its loads too
         // PAIR consumer: its first ring reads (rows nb - 2 .. nb, finished by the producers 2 barriers
@@ -2612,20 +2766,37 @@ struct MarchStep {
             int acc = 0;
             double qb, qc;
             derive<false, PH>(x, fb, acc, qb, qc);
-            if (__builtin_expect(__builtin_amdgcn_ballot_w64(acc < kUdivMinExp) != 0, 0))
+            bool again = __builtin_amdgcn_ballot_w64(acc < kUdivMinExp) != 0;
+            if constexpr (NV) {   // a marked wave (guard): the range checks of the stresses' dividends too, so that
+                // it re-runs the rows the full body re-runs
+                if (__builtin_expect(!again && __builtin_amdgcn_ballot_w64(x.big) != 0, 0)) {
+                    int a5 = 0;
+                    exp_check(a5, x.up.s<PH>(2)); exp_check(a5, x.vp.s<PH>(2)); exp_check(a5, x.up.s<PH>(3));
+                    again = __builtin_amdgcn_ballot_w64(a5 < kUdivMinExp) != 0;
+                }
+            }
+            if (__builtin_expect(again, 0))
                 derive<true, PH>(x, fb, acc, qb, qc);
             acc = 0;
             if (WARM) {
                 if (n == nb - 1) face<PH>(x);
             } else {
                 bool bad = false;
-                step<false, PH>(x, L, n, acc, bad, o);
-                if (__builtin_expect(__builtin_amdgcn_ballot_w64(acc < kUdivMinExp) != 0, 0))
-                    step<true, PH>(x, L, n, acc, bad, o);
+                step<false, PH, false>(x, L, n, acc, bad, o);
+                bool exact = __builtin_amdgcn_ballot_w64(acc < kUdivMinExp) != 0;
+                if constexpr (NV) {   // a marked wave: the row again in full, as the full body runs it (udiv, its checks)
+                    if (__builtin_expect(!exact && __builtin_amdgcn_ballot_w64(x.big) != 0, 0)) {
+                        acc = 0;
+                        step<false, PH, true, true>(x, L, n, acc, bad, o);
+                        exact = __builtin_amdgcn_ballot_w64(acc < kUdivMinExp) != 0;
+                    }
+                }
+                if (__builtin_expect(exact, 0))
+                    step<true, PH, true>(x, L, n, acc, bad, o);
                 x.fyx = o.fyx;
                 x.fyy = o.fyy;
                 x.vht = o.vht;
-                if (ZF) x.a2t = o.a2t;
+                if (ZF && !NV) x.a2t = o.a2t;
             }
             x.qb = qb;
             x.qc = qc;
@@ -2655,6 +2826,9 @@ struct MarchStep {
         return n >= ne;
     }
 };
+template <bool P2, bool LAST = false, bool ZF = false, bool X2 = false, bool HR = false, bool PAIR = false,
+          bool WT = false>
+struct MarchStep : MarchStepT<P2, LAST, ZF, X2, HR, PAIR, WT, false> {};
 #undef OCN_MD
 
 #define CHECK(...)                                                \
@@ -2879,7 +3053,12 @@ struct FallbackCheck {
     OCN_HD void operator()(int m, int n) const
     {
         const Pt c = geo(&b)(m, n), c0 = geo(&b)(r.m0, r.n0);
-        if (m == r.m0 && n == r.n0) { kc[0] = ld(hr, c0); kc[1] = ld(mu, c0); }
+        if (m == r.m0 && n == r.n0) {
+            kc[0] = ld(hr, c0); kc[1] = ld(mu, c0);
+            // the word after the verdict (the host's alone, OnepassKC::nv; the launches' gates read the verdict
+            // word as they did): the one value of mu is not +0.0
+            if (fbits64(ld(mu, c0)) != 0) OCN_ATOMIC_OR(flag + 1, 1);
+        }
         if (fbits64(ld(hr, c)) != fbits64(ld(hr, c0))) OCN_ATOMIC_OR(flag, 1);   // bit 0: h_r varies
         if (m < r.m0 - 1 || m > r.m1 + 1 || n < r.n0 - 1 || n > r.n1 + 1) return;   // the ring of r +- 2
         if (fbits64(ld(mu, c)) != fbits64(ld(mu, c0))) OCN_ATOMIC_OR(flag, 2);
@@ -3369,6 +3548,18 @@ int launch_onepass_pair(const ocn_block *b, void *const *ptr, int nptr, const Co
     g.ntiles = g.r[0].tiles;
     int ex;
     const bool p2 = std::frexp(tau, &ex) == 0.5 && ex > -1020 && ex < 1020;   // tau = 2^k
+    if (kc.nv && !last && (kc.mode == OCN_KC_KNOWN || kc.mode == OCN_KC_KNOWN_HR)) {   // the inviscid bodies (MarchStepT NV)
+#define OCN_PAIR_NV(P, H)                                                                                        \
+    return issue_march(g, MarchStepT<P, false, true, false, H, true, false, true>{*b, t, sw, tau, nbad1, sshp_out,   \
+                                                                                  up_out, vp_out, kc.kc, nullptr, 0, \
+                                                                                  0u, nbad2}, s)
+        const bool hr = kc.mode == OCN_KC_KNOWN_HR;
+        if (p2 && hr) OCN_PAIR_NV(true, true);
+        if (hr) OCN_PAIR_NV(false, true);
+        if (p2) OCN_PAIR_NV(true, false);
+        OCN_PAIR_NV(false, false);
+#undef OCN_PAIR_NV
+    }
 #define OCN_PAIR_LAUNCH(P, L, Z, H)                                                                              \
     return issue_march(g, MarchStep<P, L, Z, false, H, true>{*b, t, sw, tau, nbad1, sshp_out, up_out, vp_out,        \
                                                              kc.kc, nullptr, 0, 0u, nbad2}, s)
@@ -3436,6 +3627,17 @@ int launch_onepass_pair_x4(const ocn_block *bx, void *const *ptr, int nptr, cons
         return issue_march(g, body, s);
     };
     const bool p2 = std::frexp(tau, &ex) == 0.5 && ex > -1020 && ex < 1020;   // tau = 2^k
+    if (kc.nv) {   // the inviscid bodies (MarchStepT NV)
+        const bool hr = kc.mode == OCN_KC_KNOWN_HR;
+#define OCN_X4_NV(P, H)                                                                                              \
+    return go(MarchStepT<P, false, true, true, H, true, false, true>{*bx, t, sw, tau, nbad1, sshp_out, up_out, vp_out, \
+                                                                    kc.kc, nullptr, 0, own, nbad2})
+        if (p2 && hr) OCN_X4_NV(true, true);
+        if (hr) OCN_X4_NV(false, true);
+        if (p2) OCN_X4_NV(true, false);
+        OCN_X4_NV(false, false);
+#undef OCN_X4_NV
+    }
     if (kc.mode == OCN_KC_KNOWN_HR) {   // h_r read (a topography: the rest depth varies), its 4 rings exchanged
         if (p2)
             return go(MarchStep<true, false, true, true, true, true>{*bx, t, sw, tau, nbad1, sshp_out, up_out, vp_out,
@@ -3488,6 +3690,7 @@ __global__ void k_rows_x4(float *rows4, unsigned nrows4, const float *rows, unsi
     for (int k = 0; k < kNumRowFields; ++k)
         v[k] = e >= 0 ? ext[e * kNumRowFields + k] : rows[(unsigned)k * nrows + (r - kXRing)];
     if (!write_table_row(rows4, nrows4, r, v)) atomicOr(flags, (int)OCN_COMPACT_DIVISOR_RANGE);
+    if (!row_inviscid(v)) atomicOr(flags, (int)OCN_COMPACT_VISCOUS_ROW);
 }
 
 int launch_x4_tables(const ocn_block *g, const uint8_t *bits, const float *rows, const float *ext, uint8_t *bits4,

@@ -867,7 +867,9 @@ enum { OCN_COMPACT_MASK_NOT_BINARY = 1, OCN_COMPACT_METRIC_NOT_ROW_CONSTANT = 2,
        OCN_COMPACT_RING_SEA = 4,     // not a failure: a8 / a9 write somewhere on the halo ring
        OCN_COMPACT_DIVISOR_RANGE = 8,     // not a failure: a divisor outside [2^-60, 2^60], or llu / llv / luh
                                           // set where lu_lv_init would not (no one-pass step)
-       OCN_COMPACT_EDGE_RING_SEA = 16 };  // not a failure: a8 writes on the ring of a side no neighbour fills
+       OCN_COMPACT_EDGE_RING_SEA = 16,    // not a failure: a8 writes on the ring of a side no neighbour fills
+       OCN_COMPACT_VISCOUS_ROW = 32 };    // not a failure: a row's r_diss is not +0.0f, or one of its metrics or
+                                          // stress ratios is not finite (no inviscid bodies: row_inviscid)
 
 // Which halo points of a block a neighbour block owns (they are its interior points, filled by the
 // exchanges): bit (cx * 3 + cy) with cx = 0 / 1 / 2 for m < nx_start / inside / m > nx_end and cy
@@ -893,6 +895,18 @@ OCN_HD inline bool write_table_row(float *rows, unsigned nrows, unsigned r, cons
         range &= g[k] >= 0x1p-60f && g[k] <= 0x1p60f;   // positive; false for NaN
     }
     return range;
+}
+
+// The inviscid bodies' condition on a row (sw_kernels.hip MarchStep NV) from its metric values
+// v[OCN_DX .. OCN_R_DISS]: r_diss's bits zero, so that the friction's factor is +0.0, and every metric
+// and stress ratio (write_table_row's) finite, so that no dropped product is 0 * inf
+OCN_HD inline bool row_inviscid(const float *v)
+{
+    auto finite = [](float a) { return (fbits(a) & 0x7f800000u) != 0x7f800000u; };
+    bool ok = fbits(v[OCN_R_DISS - OCN_DX]) == 0u;
+    for (int k = 0; k < kNumRowFields; ++k) ok &= finite(v[k]);
+    const float dx = v[0], dy = v[OCN_DY - OCN_DX], dxb = v[OCN_DXB - OCN_DX], dyb = v[OCN_DYB - OCN_DX];
+    return ok && finite(dy / dx) && finite(dx / dy) && finite(dxb / dyb) && finite(dyb / dxb);
 }
 
 // Thread grid = whole bnd range.  Mask bytes everywhere; row values from column nx_start-1
@@ -949,6 +963,7 @@ struct Prepare {
         }
         // the row values, and the same real(4) divisions as stress_components_math on them
         if (m == ms && !write_table_row(rows, nrows, q.r, v)) OCN_ATOMIC_OR(flags, (int)OCN_COMPACT_DIVISOR_RANGE);
+        if (m == ms && !row_inviscid(v)) OCN_ATOMIC_OR(flags, (int)OCN_COMPACT_VISCOUS_ROW);
         if (vary) OCN_ATOMIC_OR(flags, (int)OCN_COMPACT_METRIC_NOT_ROW_CONSTANT);
     }
 };

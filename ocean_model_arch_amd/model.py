@@ -307,6 +307,17 @@ class OceanModel:
         """Whether the last step() co-launched a march and a tracer step."""
         return self.option(_lib.OPT_CO_LAUNCH) == 2
 
+    def set_inviscid(self, on: bool = True):
+        """Pair launches without the viscous and bottom-friction terms where mu and r_diss are found
+        zero everywhere (default on, OCN_OPT_INVISCID); same results bit for bit."""
+        check(lib().ocn_ctx_set_option(self.ctx, _lib.OPT_INVISCID, int(on)), "ocn_ctx_set_option")
+        return self
+
+    @property
+    def onepass_inviscid(self) -> bool:
+        """Whether the last step() ran pair launches of the inviscid bodies."""
+        return self.option(_lib.OPT_INVISCID) == 2
+
     def set_multi_spin(self, polls: int):
         """Diagnostics: the multi-step launch's grid barrier gives up after `polls` polls (default
         1 << 20, about 0.5 s); the next synchronize() then raises OCN_ERR_HIP."""

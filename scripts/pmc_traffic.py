@@ -24,7 +24,8 @@ import sys
 from collections import defaultdict
 
 STAGE = {"KFusedA": "fused_a", "KFusedB": "fused_b", "MarchFusedB": "fused_b", "KFusedC1": "fused_c1",
-         "KHhInit": "hh_init", "MarchHhInit": "hh_init", "MarchFusedA": "fused_a", "MarchCA": "fused_ca", "MarchStep": "onepass"}
+         "KHhInit": "hh_init", "MarchHhInit": "hh_init", "MarchFusedA": "fused_a", "MarchCA": "fused_ca", "MarchStep": "onepass",
+         "MarchStepT": "onepass"}   # (MarchStepT: the inviscid bodies)
 
 
 def values(root):
@@ -69,7 +70,7 @@ def main():
         m = re.search(r"ocn::(\w+)", k.replace("k_range<ocn::", "").replace("k_march<ocn::", ""))
         name = m.group(1) if m else k
         stage = STAGE.get(name)
-        t = re.search(r"MarchStep<([^>]*)>", k)
+        t = re.search(r"MarchStepT?<([^>]*)>", k)
         targs = [a.strip() for a in t.group(1).split(",")] if t else []
         if targs[5:6] == ["true"]:   # MarchStep PAIR: two steps (LAST: the second is the call's last)
             stage, name = ("onepass2_last", "MarchStep(pair, last)") if targs[1:2] == ["true"] else \

@@ -23,8 +23,10 @@ from collections import defaultdict
 
 # the known-constant one-pass kernels (P2, !LAST, ZF, !X2, h_r a constant): a single step and two
 # steps per launch (PAIR)
-KERNELS = {"onepass": "MarchStep<true, false, true, false, false, false, false>",
-           "onepass2": "MarchStep<true, false, true, false, false, true, false>"}
+# (onepass2: the inviscid body where the run launched it -- OCN_OPT_INVISCID, the default -- else the full one)
+KERNELS = {"onepass": ["MarchStep<true, false, true, false, false, false, false>"],
+           "onepass2": ["MarchStepT<true, false, true, false, false, true, false, true>",
+                        "MarchStep<true, false, true, false, false, true, false>"]}
 
 
 def summary(sq, kernel):
@@ -101,7 +103,7 @@ def main():
     ap.add_argument("--box", required=True)
     ap.add_argument("--blocks", required=True)
     a = ap.parse_args()
-    kern = {stage: s for stage, k in KERNELS.items() if (s := merged(a.sq, k))}
+    kern = {stage: s for stage, ks in KERNELS.items() if (s := next((m for k in ks if (m := merged(a.sq, k))), None))}
     if not kern:
         raise SystemExit("no dispatches of the one-pass kernels")
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
