@@ -613,6 +613,51 @@ int ocn_ens_stats_output_r4(ocn_ens *ens, int32_t k, int32_t stat, float undef, 
 typedef struct ocn_ens_extrema_t { double min, max; int64_t nonfinite, count; } ocn_ens_extrema_t;
 int ocn_ens_extrema(ocn_ens *ens, int32_t field_id, ocn_ens_extrema_t *out);
 
+/* Sampling and recombining the members on the device: what a host needs to inflate, recentre, resample or
+ * filter an ensemble between calls (each new member a linear combination of the old ones; the N x N
+ * algebra that finds the weights stays with the host).  No counterpart in the reference.  In both entries
+ * the members in use are u0 < u1 < ... < u(n-1), in member order (use[i] != 0, i < ocn_ens_size; NULL =
+ * all), as in ocn_ens_stats.
+ *
+ * ocn_ens_sample (the observation operator): host[p * n + m] = member u_m's value of real(8) field
+ * `field_id` at point p -- local block k[p], the library's 1-based global indices (i[p], j[p]), anywhere
+ * within A(bnd_x1:bnd_x2, bnd_y1:bnd_y2) of that block (halo and land included), for p < npts.  It first
+ * forms the pending call tail of every member in use (a member not in use is not touched), takes each
+ * member's array from its field table at that moment, gathers with ONE launch on the ensemble's stream
+ * and brings the npts x n doubles down through pinned memory with one wait.  Synchronous.  No pointer is
+ * handed out: options, known-constant verdicts, raw-pointer state and lazy tails stay as they were, as
+ * after ocn_ens_stats.  OCN_ERR_ARG -- nothing launched, nothing written to host -- for a null argument,
+ * npts < 1 or > 65536, a bad k, a point outside its block's array, a real(4) field or one the members do
+ * not have, no member in use.
+ *
+ * ocn_ens_transform (the recombination): w is an n x n row-major host array, w[a * n + b] the weight of
+ * old member u_a in new member u_b.  For every field of field_ids[0 .. nfields), every local block and
+ * every point of A(bnd_x1:bnd_x2, bnd_y1:bnd_y2) (row padding and the extra rings are neither read nor
+ * written), with x_a member u_a's old value -- all new values are formed from the old ones:
+ *   new_b = +0.0 if column b has no weight with a nonzero bit pattern below the sign; otherwise, over a
+ *   ascending, skipping every a whose w[a][b] is +0.0 or -0.0:
+ *     first kept term:  s = x_a * w[a][b]
+ *     later kept terms: p = x_a * w[a][b]; s = s + p     (the product rounded, then the sum)
+ *   new_b = s
+ * in IEEE double arithmetic without contraction: bitwise reproducible.  A skipped term is not formed, so a
+ * unit column is a bit-for-bit copy (-0 included; permutations and resampling are exact), and a member
+ * whose weights are all zero -- one that blew up, say -- puts no NaN into any other member.
+ * Before the launches the pending call tail of every member in use is formed; a member not in use is not
+ * touched.  Up to 32 members in use the transform is in place, one launch per field and block; beyond,
+ * the results go through staging arrays the ensemble owns (one per member in use, in the members' layout,
+ * allocated at first use, freed by ocn_ens_destroy) and are copied back on the same stream.  Afterwards
+ * each transformed field of each member in use counts as UPLOADED, with exactly ocn_ctx_upload's
+ * bookkeeping, and nothing else is re-formed: the depths, vort, the stresses and every other derived field
+ * stay as they were, as after an upload of the same fields, and the next step is whatever the library runs
+ * after uploads (a full first step that forms the depths from the new state).  A host that transforms
+ * only part of the state (ssh without sshp, say) gets what uploading that part gives.  Asynchronous on the
+ * ensemble's stream; the caller's w may be reused when the call returns.  OCN_ERR_ARG -- nothing launched,
+ * no member's state or bookkeeping touched -- for a null ensemble, list or w, nfields < 1, an id that is
+ * real(4), absent or repeated, no member in use, a weight that is not finite. */
+int ocn_ens_sample(ocn_ens *ens, int32_t field_id, const uint8_t *use, int32_t npts, const int32_t *k,
+                   const int32_t *i, const int32_t *j, double *host);
+int ocn_ens_transform(ocn_ens *ens, const int32_t *field_ids, int32_t nfields, const uint8_t *use, const double *w);
+
 const char *ocn_last_error(void);
 int ocn_abi_version(void);
 /* Build id: a hash of the library's sources and compile flags (Makefile), e.g. to tie a

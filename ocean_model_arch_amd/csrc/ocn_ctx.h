@@ -447,6 +447,9 @@ int run_step(ocn_ctx *c, double tau, const StepKind &k);
 int finish_call(ocn_ctx *c, int rc);
 int complete_open(ocn_ctx *c);
 int step_entry(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every);
+// field id counts as uploaded: ocn_ctx_upload's bookkeeping and nothing else, for an entry that has
+// rewritten the field's current array on the context's stream (ocn_ens_transform); no pending tail open
+void field_uploaded(ocn_ctx *c, int id);
 // shared: the compute stream of the ensemble `ens` the context becomes a member of (null: its own)
 int ctx_create(const ocn_basin *basin, const ocn_sw_params *sw, const ocn_decomp *dec, const int32_t *mask,
                hipStream_t shared, ocn_ens *ens, ocn_ctx **out);

@@ -1498,6 +1498,12 @@ static void fields_changed(ocn_ctx *c, Changed why, int id = -1)
     if (ptr && voted) c->r8_escaped = true;
 }
 
+void field_uploaded(ocn_ctx *c, int id)
+{
+    if (is_r4(id)) { c->static_dirty = true; c->ext_ok = false; }
+    fields_changed(c, Changed::Upload, id);
+}
+
 // An entry that may take part in a collective: the null check, then f watched under the entry's name
 template <class F> static int entry(ocn_ctx *c, const char *name, F &&f)
 {
@@ -2513,8 +2519,7 @@ int ocn_ctx_upload(ocn_ctx *c, int k, int id, const void *host)
         HIPCHK(hipSetDevice(c->dec.device));
         RC(complete_open(c));
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (is_r4(id)) { c->static_dirty = true; c->ext_ok = false; }
-        fields_changed(c, Changed::Upload, id);
+        field_uploaded(c, id);
         return upload_field(c, c->blocks[k], id, host, false);
     });
 }

@@ -1,6 +1,7 @@
 // ocn_ens.hip -- ensembles (ocn_sw.h ocn_ens_*): many members of a small basin as contexts that share
 // one compute stream, their multi-step launches issued one per group (sw_kernels.hip k_march_multi_b),
-// and the statistics over the members (ens_stats.hip).  The members' calls are planned by ocn_ctx.hip
+// the statistics over the members (ens_stats.hip), and their sampling and recombination
+// (ens_transform.hip).  The members' calls are planned by ocn_ctx.hip
 // step_impl; ocn_ens_plan.h holds the grouping policy.
 #include "ocn_ctx.h"
 #include "ocn_ens_plan.h"
@@ -33,6 +34,20 @@ struct ocn_ens {
     // ocn_ens_extrema: the blocks' interiors, the members' (field, lu) table, the per-tile partials and
     // the results, in one device allocation made at first use; h_ext: the tables and the results in pinned host memory
     void *d_ext = nullptr, *h_ext = nullptr;
+    // ocn_ens_transform: the weights transposed (ens_wt_stride x ens_wt_cols of all the members) on the
+    // device and in pinned host memory, made at first use; ev_w: the stream has read h_w (awaited before
+    // it is written again).  stage: the staging arrays of the path beyond kEnsStatsReg members, stage_n of
+    // them stage_bytes apart, each the size of the largest block's array plus its base shift
+    void *d_w = nullptr, *h_w = nullptr;
+    hipEvent_t ev_w = nullptr;
+    bool ev_w_set = false;
+    void *stage = nullptr;
+    size_t stage_bytes = 0;
+    int stage_n = 0;
+    // ocn_ens_sample: the points' table, the members' arrays per block and the results, on the device and
+    // in pinned host memory (samp_bytes each, grown when a call needs more)
+    void *d_samp = nullptr, *h_samp = nullptr;
+    size_t samp_bytes = 0;
 };
 
 // ocn_ens_plan's policy: ocn_ens_plan.h (pure host code, also built stand-alone)
@@ -71,6 +86,12 @@ int ocn_ens_destroy(ocn_ens *e)
             if (r) (void)hipFree(r);
     if (e->d_ext) (void)hipFree(e->d_ext);
     if (e->h_ext) (void)hipHostFree(e->h_ext);
+    if (e->ev_w) (void)hipEventDestroy(e->ev_w);
+    if (e->d_w) (void)hipFree(e->d_w);
+    if (e->h_w) (void)hipHostFree(e->h_w);
+    if (e->stage) (void)hipFree(e->stage);
+    if (e->d_samp) (void)hipFree(e->d_samp);
+    if (e->h_samp) (void)hipHostFree(e->h_samp);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
     return OCN_OK;
@@ -435,6 +456,127 @@ int ocn_ens_extrema(ocn_ens *e, int32_t field_id, ocn_ens_extrema_t *out)
     HIPCHK(hipStreamSynchronize(e->stream));
     memcpy(out, h + blk_b + tab_b, res_b);
     return OCN_OK;
+}
+
+// ------------------------------------------------------------------ sampling and recombination (ens_transform.hip)
+// the members in use, in member order
+static std::vector<ocn_ctx *> ens_in_use(const ocn_ens *e, const uint8_t *use)
+{
+    std::vector<ocn_ctx *> in;
+    for (size_t i = 0; i < e->m.size(); ++i)
+        if (!use || use[i]) in.push_back(e->m[i]);
+    return in;
+}
+
+int ocn_ens_sample(ocn_ens *e, int32_t field_id, const uint8_t *use, int32_t npts, const int32_t *k, const int32_t *i,
+                   const int32_t *j, double *host)
+{
+    if (!e || !k || !i || !j || !host) return set_error(OCN_ERR_ARG, "ens_sample: null argument");
+    if (npts < 1 || npts > 65536) return set_error(OCN_ERR_ARG, "ens_sample: 1..65536 points");
+    const ocn_ctx *c0 = e->m[0];
+    if (!has_r8(c0, field_id)) return set_error(OCN_ERR_ARG, "ens_sample: not a real(8) field of the members");
+    const std::vector<ocn_ctx *> in = ens_in_use(e, use);
+    if (in.empty()) return set_error(OCN_ERR_ARG, "ens_sample: no member in use");
+    const size_t n = in.size(), nblk = c0->blocks.size(), np = (size_t)npts;
+    std::vector<long> off(np);
+    for (size_t p = 0; p < np; ++p) {
+        if (k[p] < 0 || k[p] >= (int32_t)nblk) return set_error(OCN_ERR_ARG, "ens_sample: bad block index");
+        const ocn_block &g = c0->blocks[(size_t)k[p]].g;
+        if (i[p] < g.bnd_x1 || i[p] > g.bnd_x2 || j[p] < g.bnd_y1 || j[p] > g.bnd_y2)
+            return set_error(OCN_ERR_ARG, "ens_sample: a point outside its block's array");
+        off[p] = (long)(j[p] - g.bnd_y1) * (long)g.pitch + (i[p] - g.bnd_x1);
+    }
+    HIPCHK(hipSetDevice(e->device));
+    // one layout on both sides: the offsets, the blocks, the members' arrays per block (up), the results (down)
+    const size_t off_b = np * sizeof(long), blk_b = (np * sizeof(int) + 7) / 8 * 8, tab_b = nblk * n * sizeof(double *),
+                 up_b = off_b + blk_b + tab_b, res_b = np * n * sizeof(double);
+    if (e->samp_bytes < up_b + res_b) {   // (a synchronous entry: nothing in flight reads the old ones)
+        if (e->d_samp) (void)hipFree(e->d_samp);
+        if (e->h_samp) (void)hipHostFree(e->h_samp);
+        e->d_samp = e->h_samp = nullptr;
+        e->samp_bytes = 0;
+        HIPCHK(hipMalloc(&e->d_samp, up_b + res_b));
+        HIPCHK(hipHostMalloc(&e->h_samp, up_b + res_b, hipHostMallocDefault));
+        e->samp_bytes = up_b + res_b;
+    }
+    char *d = (char *)e->d_samp, *h = (char *)e->h_samp;
+    memcpy(h, off.data(), off_b);
+    for (size_t p = 0; p < np; ++p) ((int *)(h + off_b))[p] = k[p];
+    // the members in use: their pending call tails formed, their arrays as the field tables name them now
+    std::vector<const double *> src;
+    for (size_t m = 0; m < n; ++m) {
+        ocn_ctx *c = in[m];
+        RC(guarded(c, "ocn_ens_sample", [&] { return complete_open(c); }));
+        for (size_t b = 0; b < nblk; ++b)
+            ((const double **)(h + off_b + blk_b))[b * n + m] = (const double *)c->blocks[b].ptr[field_slot(field_id)];
+        src.push_back((const double *)c->blocks[0].ptr[field_slot(field_id)]);
+    }
+    HIPCHK(hipMemcpyAsync(d, h, up_b, hipMemcpyHostToDevice, e->stream));
+    RC(launch_ens_sample(src.data(), nblk > 1 ? (const double *const *)(d + off_b + blk_b) : nullptr, (int)n,
+                         (const long *)d, (const int *)(d + off_b), npts, (double *)(d + up_b), e->stream));
+    HIPCHK(hipMemcpyAsync(h + up_b, d + up_b, res_b, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    memcpy(host, h + up_b, res_b);
+    return OCN_OK;
+}
+
+int ocn_ens_transform(ocn_ens *e, const int32_t *field_ids, int32_t nfields, const uint8_t *use, const double *w)
+{
+    if (!e || !field_ids || !w) return set_error(OCN_ERR_ARG, "ens_transform: null argument");
+    if (nfields < 1) return set_error(OCN_ERR_ARG, "ens_transform: no field");
+    const ocn_ctx *c0 = e->m[0];
+    for (int32_t f = 0; f < nfields; ++f) {
+        if (!has_r8(c0, field_ids[f])) return set_error(OCN_ERR_ARG, "ens_transform: not a real(8) field of the members");
+        for (int32_t q = 0; q < f; ++q)
+            if (field_ids[q] == field_ids[f]) return set_error(OCN_ERR_ARG, "ens_transform: a field named twice");
+    }
+    const std::vector<ocn_ctx *> in = ens_in_use(e, use);
+    if (in.empty()) return set_error(OCN_ERR_ARG, "ens_transform: no member in use");
+    const int n = (int)in.size();
+    for (size_t q = 0; q < (size_t)n * n; ++q)
+        if (!std::isfinite(w[q])) return set_error(OCN_ERR_ARG, "ens_transform: a weight that is not finite");
+    HIPCHK(hipSetDevice(e->device));
+    // the buffers first (a failed allocation leaves the members as they were)
+    const int M = (int)e->m.size();
+    const size_t w_bytes = (size_t)ens_wt_stride(M) * ens_wt_cols(M) * sizeof(double);
+    if (!e->d_w) HIPCHK(hipMalloc(&e->d_w, w_bytes));
+    if (!e->h_w) HIPCHK(hipHostMalloc(&e->h_w, w_bytes, hipHostMallocDefault));
+    if (!e->ev_w) HIPCHK(hipEventCreateWithFlags(&e->ev_w, hipEventDisableTiming));
+    if (n > kEnsStatsReg && e->stage_n < n) {
+        if (e->stage) (void)hipFree(e->stage);   // (waits for the launches that use it)
+        e->stage = nullptr;
+        e->stage_n = 0;
+        size_t big = 0;
+        for (const LBlock &b : c0->blocks) big = std::max(big, field_bytes(b));
+        e->stage_bytes = (big + 512 + 255) / 256 * 256;
+        HIPCHK(hipMalloc(&e->stage, e->stage_bytes * (size_t)n));
+        e->stage_n = n;
+    }
+    for (ocn_ctx *c : in) RC(guarded(c, "ocn_ens_transform", [&] { return complete_open(c); }));
+    // the weights transposed and zero-padded, up from pinned memory ahead of the launches
+    if (e->ev_w_set) HIPCHK(hipEventSynchronize(e->ev_w));
+    const int ws = ens_wt_stride(n), wc = ens_wt_cols(n);
+    double *hw = (double *)e->h_w;
+    std::fill(hw, hw + (size_t)ws * wc, 0.0);
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b < n; ++b) hw[ens_wt_index(n, a, b)] = w[(size_t)a * n + b];
+    HIPCHK(hipMemcpyAsync(e->d_w, hw, (size_t)ws * wc * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipEventRecord(e->ev_w, e->stream));
+    e->ev_w_set = true;
+    int rc = OCN_OK;
+    std::vector<double *> mem((size_t)n);
+    for (int32_t f = 0; f < nfields && !rc; ++f)
+        for (size_t k = 0; k < c0->blocks.size() && !rc; ++k) {
+            for (int a = 0; a < n; ++a) mem[(size_t)a] = (double *)in[(size_t)a]->blocks[k].ptr[field_slot(field_ids[f])];
+            double *stage = e->stage ? (double *)((char *)e->stage + 256 + ((uintptr_t)mem[0] & 255u)) : nullptr;
+            rc = launch_ens_transform(&c0->blocks[k].g, mem.data(), n, (const double *)e->d_w, stage,
+                                      (long)(e->stage_bytes / sizeof(double)), e->stream);
+        }
+    // what ocn_ctx_upload of each of these fields leaves behind (also after a failed launch: the arrays
+    // may have changed)
+    for (ocn_ctx *c : in)
+        for (int32_t f = 0; f < nfields; ++f) field_uploaded(c, field_ids[f]);
+    return rc;
 }
 
 }  // extern "C"

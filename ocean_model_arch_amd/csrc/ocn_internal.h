@@ -238,6 +238,26 @@ struct EnsExtSrc { const double *src; const float *lu; };
 int ens_extrema_tiles(int w, int h, int *tiles_x);
 int launch_ens_extrema(const EnsExtBlock *d_blk, int nblk, const EnsExtSrc *d_tab, int members, int ntiles,
                        EnsPartial *d_part, EnsPartial *d_out, hipStream_t s);
+// Recombination of the members (ens_transform.hip; ocn_sw.h ocn_ens_transform): the n arrays mem[0 .. n)
+// (one field of one block geometry, the members in use in member order) become their linear combinations
+// by the n x n weights, at every point of A(bnd_x1:bnd_x2, bnd_y1:bnd_y2).  d_wt: the weights on the
+// device, ens_wt_stride(n) x ens_wt_cols(n) doubles, the weight of old member a in new member b at
+// ens_wt_index(n, a, b) and +0.0 everywhere else -- up to kEnsStatsReg members transposed (a column's
+// weights side by side, kEnsStatsReg apart); beyond, per pass of 8 columns one input's 8 weights side by
+// side.  Up to kEnsStatsReg members ONE launch, in place; beyond, into the staging arrays
+// stage + b * stage_stride (elements; based like mem[0]) and a second launch that copies them back.
+inline int ens_wt_stride(int n) { return n <= kEnsStatsReg ? kEnsStatsReg : n; }
+inline int ens_wt_cols(int n) { return n <= kEnsStatsReg ? n : (n + 7) / 8 * 8; }
+inline size_t ens_wt_index(int n, int a, int b)
+{
+    return n <= kEnsStatsReg ? (size_t)b * kEnsStatsReg + a : (size_t)(b / 8) * 8 * n + (size_t)a * 8 + b % 8;
+}
+int launch_ens_transform(const ocn_block *b, double *const *mem, int n, const double *d_wt, double *stage,
+                         long stage_stride, hipStream_t s);
+// out[p * n + m] = member m's value at point p (ocn_ens_sample): element d_off[p] of mem[m], or with
+// d_tab (several blocks) of d_tab[d_blk[p] * n + m].  ONE launch.
+int launch_ens_sample(const double *const *mem, const double *const *d_tab, int n, const long *d_off,
+                      const int *d_blk, int npts, double *d_out, hipStream_t s);
 // the known-constant precondition of launch_onepass over r (sw_kernels.hip FallbackCheck: the
 // fallback points and the forcing hold +0.0, h_r and mu are uniform): ORs 1 into *flag where it
 // does not hold; writes h_r and mu at (r.m0, r.n0) to kc[0], kc[1]

@@ -17,6 +17,9 @@ from .config import BasinConfig, ParallelConfig, SWConfig
 from .model import BlockInfo, OceanModel
 from .output import UNDEF
 
+# the prognostic state of the shallow-water step: what OceanEnsemble.transform recombines by default
+STATE = ("ssh", "sshp", "ubrtr", "ubrtrp", "vbrtr", "vbrtrp")
+
 
 class _Member(OceanModel):
     """An OceanModel over a handle borrowed from an ensemble: every method works; close() leaves the
@@ -205,6 +208,45 @@ class OceanEnsemble:
         check(lib().ocn_ens_extrema(self.ens, _lib.FIELD_ID[name], out), "ocn_ens_extrema")
         return [{"min": float(x.min), "max": float(x.max), "nonfinite": int(x.nonfinite), "count": int(x.count)}
                 for x in out]
+
+    # ------------------------------------------------------------ sampling and recombination
+    def _count(self, members) -> int:
+        return len(self.members) if members is None else len({int(i) for i in members})
+
+    def sample(self, name: str, points, members=None) -> np.ndarray:
+        """The members' values of real(8) field `name` at `points`, (k, i, j) triples -- local block and the
+        library's 1-based global indices, anywhere in the block's array (halo and land included): a float64
+        array (npts, n), column m the m-th of `members` in member order (None: all).  One launch and one wait
+        (ocn_ens_sample); pending call tails of the members in use are formed first."""
+        pts = np.asarray(list(points), dtype=np.int64).reshape(-1, 3)
+        k, i, j = (np.ascontiguousarray(pts[:, c], dtype=np.int32) for c in range(3))
+        out = np.zeros((len(pts), self._count(members)), dtype=np.float64)
+        check(lib().ocn_ens_sample(self.ens, _lib.FIELD_ID[name], self._use(members), len(pts), k.ctypes.data_as(C.c_void_p),
+                                   i.ctypes.data_as(C.c_void_p), j.ctypes.data_as(C.c_void_p),
+                                   out.ctypes.data_as(C.c_void_p)), "ocn_ens_sample")
+        return out
+
+    def transform(self, w, names=STATE, members=None):
+        """Every member in use becomes a linear combination of the members in use: new member b =
+        sum over a of w[a, b] x old member a, in member order, for the real(8) fields `names` on every
+        block, on the device (ocn_ens_transform; the order of operations and the treatment of zero weights
+        are in include/ocn_sw.h).  `w` is an (n, n) float64 array of finite weights, n the members in use.
+        The transformed fields count as uploaded: the next step forms everything derived from them again.
+        Asynchronous."""
+        n = self._count(members)
+        a = np.asarray(w)
+        if a.dtype != np.float64:
+            raise TypeError(f"transform: weights of dtype {a.dtype}, not float64")
+        if a.shape != (n, n):
+            raise ValueError(f"transform: weights of shape {a.shape}, not {(n, n)} for {n} members in use")
+        if not np.isfinite(a).all():
+            raise ValueError("transform: a weight that is not finite")
+        a = np.ascontiguousarray(a)
+        names = (names,) if isinstance(names, str) else tuple(names)
+        ids = (C.c_int32 * len(names))(*[_lib.FIELD_ID[nm] for nm in names])
+        check(lib().ocn_ens_transform(self.ens, ids, len(names), self._use(members), a.ctypes.data_as(C.c_void_p)),
+              "ocn_ens_transform")
+        return self
 
     @property
     def interior_cells(self) -> int:
