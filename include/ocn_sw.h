@@ -658,6 +658,48 @@ int ocn_ens_sample(ocn_ens *ens, int32_t field_id, const uint8_t *use, int32_t n
                    const int32_t *i, const int32_t *j, double *host);
 int ocn_ens_transform(ocn_ens *ens, const int32_t *field_ids, int32_t nfields, const uint8_t *use, const double *w);
 
+/* The localized serial observation update: the per-point operation of a serial square-root filter (serial
+ * EnSRF, EAKF) with a distance taper, on the device.  ocn_ens_transform applies ONE weight matrix to every
+ * point, a global analysis; here each state point is regressed on one observation's ensemble anomalies
+ * after another, scaled by a taper of its distance to the observation.  The n-sized algebra in observation
+ * space (y and z below) stays with the host.  No counterpart in the reference.
+ *
+ * The members in use are u0 < u1 < ... < u(n-1) in member order (use as in ocn_ens_stats), n >= 2.
+ * Observation k < nobs sits at the library's 1-based global indices (io[k], jo[k]), 1 <= io <= nx and
+ * 1 <= jo <= ny of the basin; it need not lie in any local block's array.  y and z are nobs x n row-major
+ * host arrays of finite doubles.  taper has ntaper finite doubles, 1 <= ntaper <= 65536, and is indexed by
+ * the squared index distance d2 = (i - io)^2 + (j - jo)^2: the host chooses the taper's shape, the device
+ * takes no square root.  Distances are in the index space of the field's own array: the half-cell stagger
+ * of u and v points against h points is ignored, and there is no wrap-around.
+ *
+ * For every field of field_ids[0 .. nfields), every local block and every point (i, j) -- global indices --
+ * of A(bnd_x1:bnd_x2, bnd_y1:bnd_y2) (row padding and the extra rings are neither read nor written), with
+ * x_m member u_m's current value, the observations taken in ascending k:
+ *   d2 = (i-io[k])^2 + (j-jo[k])^2;  if d2 >= ntaper: skip k;  rho = taper[d2];  if rho is +0.0 or -0.0: skip k
+ *   s = x_0;  s = s + x_m (m = 1 .. n-1, in that order);  mean = s / (double)n
+ *   a = (x_0 - mean) * y[k][0];  then for m = 1 .. n-1:  p = (x_m - mean) * y[k][m];  a = a + p
+ *   g = rho * a
+ *   x_m = x_m + g * z[k][m]  for every m     (the product rounded, then the sum)
+ * in IEEE double arithmetic without contraction: bitwise reproducible.  A skipped observation forms
+ * nothing; a point no observation reaches is not written; a reached point has all n values written.
+ *   Composition: two calls with the lists L1, then L2, give the bits of one call with L1 followed by L2
+ *   (so a host splits a list longer than 8192).
+ *   Halo coherence: a halo point and the neighbour block's interior point with the same global indices
+ *   get the same operations; if they held the same bits before, they hold the same bits after.
+ *   NaN or Inf: a member that holds one at a point poisons every member at that point (through the mean).
+ *   The host leaves that member out with `use`; ocn_ens_extrema tells which one it is.
+ * The bookkeeping is ocn_ens_transform's: the pending call tail of every member in use is formed first, a
+ * member not in use is not touched, afterwards each listed field of each member in use counts as UPLOADED
+ * and nothing else is re-formed.  One launch per field and block that an observation's reach meets
+ * (values in registers up to 32 members in use, in LDS beyond).  Asynchronous on the ensemble's stream;
+ * the caller's arrays may be reused when the call returns.  OCN_ERR_ARG -- nothing launched, no member's
+ * tail, state or bookkeeping touched -- for a null argument, nfields < 1, an id that is real(4), absent or
+ * repeated, n < 2, nobs < 1 or > 8192, an observation outside the basin, ntaper < 1 or > 65536, a y, z or
+ * taper value that is not finite. */
+int ocn_ens_local_update(ocn_ens *ens, const int32_t *field_ids, int32_t nfields, const uint8_t *use,
+                         int32_t nobs, const int32_t *io, const int32_t *jo,
+                         const double *y, const double *z, const double *taper, int32_t ntaper);
+
 const char *ocn_last_error(void);
 int ocn_abi_version(void);
 /* Build id: a hash of the library's sources and compile flags (Makefile), e.g. to tie a

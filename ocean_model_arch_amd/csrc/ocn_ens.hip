@@ -1,7 +1,7 @@
 // ocn_ens.hip -- ensembles (ocn_sw.h ocn_ens_*): many members of a small basin as contexts that share
 // one compute stream, their multi-step launches issued one per group (sw_kernels.hip k_march_multi_b),
-// the statistics over the members (ens_stats.hip), and their sampling and recombination
-// (ens_transform.hip).  The members' calls are planned by ocn_ctx.hip
+// the statistics over the members (ens_stats.hip), their sampling and recombination
+// (ens_transform.hip) and their localized observation update (ens_local.hip).  The members' calls are planned by ocn_ctx.hip
 // step_impl; ocn_ens_plan.h holds the grouping policy.
 #include "ocn_ctx.h"
 #include "ocn_ens_plan.h"
@@ -48,6 +48,13 @@ struct ocn_ens {
     // in pinned host memory (samp_bytes each, grown when a call needs more)
     void *d_samp = nullptr, *h_samp = nullptr;
     size_t samp_bytes = 0;
+    // ocn_ens_local_update: the y and z rows, the taper and the blocks' observation lists, on the device
+    // and in pinned host memory (lu_bytes each, grown when a call needs more); ev_lu: the stream has read
+    // h_lu (awaited before it is written again)
+    void *d_lu = nullptr, *h_lu = nullptr;
+    size_t lu_bytes = 0;
+    hipEvent_t ev_lu = nullptr;
+    bool ev_lu_set = false;
 };
 
 // ocn_ens_plan's policy: ocn_ens_plan.h (pure host code, also built stand-alone)
@@ -92,6 +99,9 @@ int ocn_ens_destroy(ocn_ens *e)
     if (e->stage) (void)hipFree(e->stage);
     if (e->d_samp) (void)hipFree(e->d_samp);
     if (e->h_samp) (void)hipHostFree(e->h_samp);
+    if (e->ev_lu) (void)hipEventDestroy(e->ev_lu);
+    if (e->d_lu) (void)hipFree(e->d_lu);
+    if (e->h_lu) (void)hipHostFree(e->h_lu);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
     return OCN_OK;
@@ -571,6 +581,101 @@ int ocn_ens_transform(ocn_ens *e, const int32_t *field_ids, int32_t nfields, con
             double *stage = e->stage ? (double *)((char *)e->stage + 256 + ((uintptr_t)mem[0] & 255u)) : nullptr;
             rc = launch_ens_transform(&c0->blocks[k].g, mem.data(), n, (const double *)e->d_w, stage,
                                       (long)(e->stage_bytes / sizeof(double)), e->stream);
+        }
+    // what ocn_ctx_upload of each of these fields leaves behind (also after a failed launch: the arrays
+    // may have changed)
+    for (ocn_ctx *c : in)
+        for (int32_t f = 0; f < nfields; ++f) field_uploaded(c, field_ids[f]);
+    return rc;
+}
+
+// ------------------------------------------------------------------ localized observation update (ens_local.hip)
+int ocn_ens_local_update(ocn_ens *e, const int32_t *field_ids, int32_t nfields, const uint8_t *use, int32_t nobs,
+                         const int32_t *io, const int32_t *jo, const double *y, const double *z, const double *taper,
+                         int32_t ntaper)
+{
+    if (!e || !field_ids || !io || !jo || !y || !z || !taper) return set_error(OCN_ERR_ARG, "ens_local_update: null argument");
+    if (nfields < 1) return set_error(OCN_ERR_ARG, "ens_local_update: no field");
+    const ocn_ctx *c0 = e->m[0];
+    for (int32_t f = 0; f < nfields; ++f) {
+        if (!has_r8(c0, field_ids[f])) return set_error(OCN_ERR_ARG, "ens_local_update: not a real(8) field of the members");
+        for (int32_t q = 0; q < f; ++q)
+            if (field_ids[q] == field_ids[f]) return set_error(OCN_ERR_ARG, "ens_local_update: a field named twice");
+    }
+    const std::vector<ocn_ctx *> in = ens_in_use(e, use);
+    if (in.size() < 2) return set_error(OCN_ERR_ARG, "ens_local_update: fewer than two members in use");
+    if (nobs < 1 || nobs > 8192) return set_error(OCN_ERR_ARG, "ens_local_update: 1..8192 observations");
+    if (ntaper < 1 || ntaper > 65536) return set_error(OCN_ERR_ARG, "ens_local_update: a taper of 1..65536 entries");
+    const int n = (int)in.size();
+    for (int32_t k = 0; k < nobs; ++k)
+        if (io[k] < 1 || io[k] > c0->basin.nx || jo[k] < 1 || jo[k] > c0->basin.ny)
+            return set_error(OCN_ERR_ARG, "ens_local_update: an observation outside the basin");
+    for (size_t q = 0; q < (size_t)nobs * n; ++q)
+        if (!std::isfinite(y[q]) || !std::isfinite(z[q])) return set_error(OCN_ERR_ARG, "ens_local_update: a y or z that is not finite");
+    for (int32_t q = 0; q < ntaper; ++q)
+        if (!std::isfinite(taper[q])) return set_error(OCN_ERR_ARG, "ens_local_update: a taper entry that is not finite");
+    int reach = 0;   // the largest r with r * r < ntaper
+    while ((reach + 1) * (reach + 1) < ntaper) ++reach;
+    // each block's list: the observations whose box meets the block's array, in the caller's order
+    const size_t nblk = c0->blocks.size();
+    std::vector<std::vector<EnsLuObs>> lists(nblk);
+    size_t list_n = 0;
+    for (size_t b = 0; b < nblk; ++b) {
+        const ocn_block &g = c0->blocks[b].g;
+        for (int32_t k = 0; k < nobs; ++k)
+            if (io[k] + reach >= g.bnd_x1 && io[k] - reach <= g.bnd_x2 && jo[k] + reach >= g.bnd_y1 && jo[k] - reach <= g.bnd_y2)
+                lists[b].push_back(EnsLuObs{io[k], jo[k], k, 0});
+        while (lists[b].size() % kLuGroup) lists[b].push_back(ens_lu_filler());
+        list_n += lists[b].size();
+    }
+    HIPCHK(hipSetDevice(e->device));
+    // the buffers first (a failed allocation leaves the members as they were): rows, taper, lists
+    const size_t rows_b = (size_t)nobs * ens_lu_row(n) * sizeof(double), tap_b = ((size_t)ntaper * sizeof(double) + 255) / 256 * 256,
+                 need = 2 * rows_b + tap_b + list_n * sizeof(EnsLuObs);
+    if (!e->ev_lu) HIPCHK(hipEventCreateWithFlags(&e->ev_lu, hipEventDisableTiming));
+    if (e->lu_bytes < need) {
+        if (e->ev_lu_set) HIPCHK(hipEventSynchronize(e->ev_lu));
+        if (e->d_lu) (void)hipFree(e->d_lu);   // (waits for the launches that use it)
+        if (e->h_lu) (void)hipHostFree(e->h_lu);
+        e->d_lu = e->h_lu = nullptr;
+        e->lu_bytes = 0;
+        const size_t grown = (need + 65535) / 65536 * 65536;
+        HIPCHK(hipMalloc(&e->d_lu, grown));
+        HIPCHK(hipHostMalloc(&e->h_lu, grown, hipHostMallocDefault));
+        e->lu_bytes = grown;
+    }
+    for (ocn_ctx *c : in) RC(guarded(c, "ocn_ens_local_update", [&] { return complete_open(c); }));
+    // the tables up from pinned memory ahead of the launches
+    if (e->ev_lu_set) HIPCHK(hipEventSynchronize(e->ev_lu));
+    char *h = (char *)e->h_lu, *d = (char *)e->d_lu;
+    const size_t row = ens_lu_row(n);
+    double *hy = (double *)h, *hz = (double *)(h + rows_b);
+    std::fill(hy, hy + 2 * (size_t)nobs * row, 0.0);   // (the padding of the rows: read, never used)
+    for (int32_t k = 0; k < nobs; ++k)
+        for (int m = 0; m < n; ++m) {
+            hy[(size_t)k * row + m] = y[(size_t)k * n + m];
+            hz[(size_t)k * row + m] = z[(size_t)k * n + m];
+        }
+    memcpy(h + 2 * rows_b, taper, (size_t)ntaper * sizeof(double));
+    std::vector<size_t> list_at(nblk);
+    size_t at = 2 * rows_b + tap_b;
+    for (size_t b = 0; b < nblk; ++b) {
+        list_at[b] = at;
+        if (!lists[b].empty()) memcpy(h + at, lists[b].data(), lists[b].size() * sizeof(EnsLuObs));
+        at += lists[b].size() * sizeof(EnsLuObs);
+    }
+    HIPCHK(hipMemcpyAsync(d, h, need, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipEventRecord(e->ev_lu, e->stream));
+    e->ev_lu_set = true;
+    int rc = OCN_OK;
+    std::vector<double *> mem((size_t)n);
+    for (int32_t f = 0; f < nfields && !rc; ++f)
+        for (size_t k = 0; k < nblk && !rc; ++k) {
+            if (lists[k].empty()) continue;   // no observation reaches this block
+            for (int a = 0; a < n; ++a) mem[(size_t)a] = (double *)in[(size_t)a]->blocks[k].ptr[field_slot(field_ids[f])];
+            rc = launch_ens_local(&c0->blocks[k].g, mem.data(), n, (const EnsLuObs *)(d + list_at[k]),
+                                  (int)(lists[k].size() / kLuGroup), (const double *)d, (const double *)(d + rows_b),
+                                  (const double *)(d + 2 * rows_b), ntaper, reach, e->stream);
         }
     // what ocn_ctx_upload of each of these fields leaves behind (also after a failed launch: the arrays
     // may have changed)

@@ -258,6 +258,20 @@ int launch_ens_transform(const ocn_block *b, double *const *mem, int n, const do
 // d_tab (several blocks) of d_tab[d_blk[p] * n + m].  ONE launch.
 int launch_ens_sample(const double *const *mem, const double *const *d_tab, int n, const long *d_off,
                       const int *d_blk, int npts, double *d_out, hipStream_t s);
+// The localized serial observation update (ens_local.hip; ocn_sw.h ocn_ens_local_update) of the n arrays
+// mem[0 .. n) (one field of one block geometry, the members in use in member order), in place, at the
+// points of A(bnd_x1:bnd_x2, bnd_y1:bnd_y2) the block's observations reach.  d_list: ngroups x kLuGroup
+// entries, the block's observations in the caller's order (io, jo global; k the row of d_y and d_z), the
+// last group filled up with ens_lu_filler(); d_y, d_z: the rows, ens_lu_row(n) doubles apart; d_taper:
+// ntaper doubles; reach: the largest r with r * r < ntaper.  ONE launch; beyond kEnsStatsReg members the
+// values live in n x 512 B of dynamic LDS.
+constexpr int kLuGroup = 4;   // list entries a wave reads and tests at a time
+constexpr int kLuRow = 8;     // the y and z rows are padded to a multiple of this many doubles
+struct EnsLuObs { int32_t io, jo, k, pad; };
+inline EnsLuObs ens_lu_filler() { return EnsLuObs{-(1 << 30), -(1 << 30), 0, 0}; }   // (its box meets no wave)
+inline size_t ens_lu_row(int n) { return (size_t)(n + kLuRow - 1) / kLuRow * kLuRow; }
+int launch_ens_local(const ocn_block *b, double *const *mem, int n, const EnsLuObs *d_list, int ngroups, const double *d_y,
+                     const double *d_z, const double *d_taper, int ntaper, int reach, hipStream_t s);
 // the known-constant precondition of launch_onepass over r (sw_kernels.hip FallbackCheck: the
 // fallback points and the forcing hold +0.0, h_r and mu are uniform): ORs 1 into *flag where it
 // does not hold; writes h_r and mu at (r.m0, r.n0) to kc[0], kc[1]

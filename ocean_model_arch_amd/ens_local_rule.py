@@ -1,0 +1,156 @@
+"""The localized serial observation update in numpy (include/ocn_sw.h ocn_ens_local_update): the rule the
+device applies, restated on whole arrays with the members and the observations in loop order, the
+observation-space loop of a serial ensemble square-root filter built on it, and the taper tables.
+
+numpy's elementwise subtract, multiply, add and divide are single IEEE double operations per element and
+nothing here is fused, so `local_rule` gives the device's bits.  OceanEnsemble.assimilate tracks the
+ensemble at the observed points with it; tests/ens_local_ref.py hands the same function to the tests, which
+check it against a scalar loop.  Pure numpy: no device, no library.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+MAX_OBS = 8192        # ocn_ens_local_update: observations per call
+MAX_TAPER = 65536     # ... and taper entries
+
+
+def reach_of(ntaper: int) -> int:
+    """The largest r with r * r < ntaper: no point farther than this from an observation, along either
+    axis, is within its taper."""
+    r = 0
+    while (r + 1) * (r + 1) < ntaper:
+        r += 1
+    return r
+
+
+def _update(xs, rho, yk, zk):
+    """The rule at points that all take observation k: xs the members' values there, rho their (nonzero)
+    taper values.  Returns the new values."""
+    n = len(xs)
+    s = xs[0]
+    for m in range(1, n):
+        s = s + xs[m]
+    mean = s / float(n)
+    a = (xs[0] - mean) * yk[0]
+    for m in range(1, n):
+        p = (xs[m] - mean) * yk[m]
+        a = a + p
+    g = rho * a
+    return [xs[m] + g * zk[m] for m in range(n)]
+
+
+def local_rule(x, gi, gj, io, jo, y, z, taper):
+    """The members' arrays after the observations (io[k], jo[k]), k ascending, with the rows y[k], z[k] and
+    the taper table indexed by the squared index distance.
+
+    x: the n >= 2 members' arrays in member order, all of one shape.  Either 2-D arrays with gi and gj the
+    1-D global indices of their rows and columns (consecutive integers: a block's array), or arrays of any
+    shape with gi and gj index arrays of that shape (scattered points).  Fresh arrays: the inputs are not
+    written."""
+    x = [np.array(a, dtype=np.float64, order="F", copy=True) for a in x]
+    n = len(x)
+    io, jo = np.asarray(io, dtype=np.int64).ravel(), np.asarray(jo, dtype=np.int64).ravel()
+    y, z = np.asarray(y, dtype=np.float64).reshape(len(io), n), np.asarray(z, dtype=np.float64).reshape(len(io), n)
+    taper = np.asarray(taper, dtype=np.float64).ravel()
+    nt = len(taper)
+    assert n >= 2 and nt >= 1
+    gi, gj = np.asarray(gi, dtype=np.int64), np.asarray(gj, dtype=np.int64)
+    grid = x[0].ndim == 2 and gi.ndim == 1 and gj.ndim == 1 and gi.shape + gj.shape == x[0].shape
+    if grid:
+        assert (np.diff(gi) == 1).all() and (np.diff(gj) == 1).all()
+        reach = reach_of(nt)
+    else:
+        assert gi.shape == x[0].shape and gj.shape == x[0].shape
+    with np.errstate(all="ignore"):
+        for k in range(len(io)):
+            if grid:   # the part of the array within the observation's box
+                a0, a1 = max(int(io[k]) - reach - int(gi[0]), 0), min(int(io[k]) + reach - int(gi[0]) + 1, len(gi))
+                b0, b1 = max(int(jo[k]) - reach - int(gj[0]), 0), min(int(jo[k]) + reach - int(gj[0]) + 1, len(gj))
+                if a0 >= a1 or b0 >= b1:
+                    continue
+                view = [a[a0:a1, b0:b1] for a in x]
+                d2 = ((gi[a0:a1] - io[k]) ** 2)[:, None] + ((gj[b0:b1] - jo[k]) ** 2)[None, :]
+            else:
+                view = x
+                d2 = (gi - io[k]) ** 2 + (gj - jo[k]) ** 2
+            rho = np.zeros(d2.shape)
+            within = d2 < nt
+            rho[within] = taper[d2[within]]
+            act = rho != 0.0           # +0.0 and -0.0 alike: the observation is skipped there
+            if not act.any():
+                continue
+            new = _update([v[act] for v in view], rho[act], y[k], z[k])
+            for v, a in zip(view, new):
+                v[act] = a
+    return x
+
+
+def ensrf_obs_space(hx, obs_ij, values, variances, taper):
+    """The observation-space loop of a serial ensemble square-root filter (Whitaker & Hamill 2002) with a
+    taper: from hx, the (nobs, n) members' values at the observed points (i, j) = obs_ij[k], the observed
+    values and the observation error variances, the rows Y[k], Z[k] that ocn_ens_local_update needs, and
+    what the ensemble holds at the observed points afterwards.
+
+    For k in order, with yv the CURRENT row k:  ybar = mean(yv), y' = yv - ybar, s = sum(y'^2) / (n - 1),
+    D = s + r_k, d = value_k - ybar, alpha = 1 / (1 + sqrt(r_k / D));  Y[k] = y',
+    Z[k][m] = (d - alpha y'_m) / ((n - 1) D);  then every row -- the observed points are state points like
+    any other -- takes observation k by `local_rule`, so the rows stay bit for bit what the device's
+    fields hold there.  Returns (Y, Z, info): info["hx"] the final rows, "innovations" the d of each step,
+    "prior_spread" / "posterior_spread" the rows' standard deviations (n - 1) before and after."""
+    hx = np.array(hx, dtype=np.float64, copy=True)
+    nobs, n = hx.shape
+    ij = np.asarray(obs_ij, dtype=np.int64).reshape(nobs, 2)
+    values, variances = np.asarray(values, dtype=np.float64).ravel(), np.asarray(variances, dtype=np.float64).ravel()
+    if n < 2 or len(values) != nobs or len(variances) != nobs:
+        raise ValueError("ensrf_obs_space: hx (nobs, n >= 2) with nobs values and variances")
+    if not (variances > 0.0).all() or not np.isfinite(variances).all() or not np.isfinite(values).all():
+        raise ValueError("ensrf_obs_space: finite values and positive finite variances")
+    Y, Z = np.zeros((nobs, n)), np.zeros((nobs, n))
+    innov = np.zeros(nobs)
+    prior = hx.std(axis=1, ddof=1)
+    for k in range(nobs):
+        yv = hx[k]
+        ybar = float(np.sum(yv)) / n
+        yp = yv - ybar
+        s = float(np.sum(yp * yp)) / (n - 1)
+        r = float(variances[k])
+        D = s + r
+        d = float(values[k]) - ybar
+        alpha = 1.0 / (1.0 + np.sqrt(r / D))
+        Y[k] = yp
+        Z[k] = (d - alpha * yp) / ((n - 1) * D)
+        innov[k] = d
+        cols = local_rule([hx[:, m] for m in range(n)], ij[:, 0], ij[:, 1], ij[k:k + 1, 0], ij[k:k + 1, 1],
+                          Y[k:k + 1], Z[k:k + 1], taper)
+        hx = np.stack(cols, axis=1)
+    return Y, Z, {"hx": hx, "innovations": innov, "prior_spread": prior, "posterior_spread": hx.std(axis=1, ddof=1)}
+
+
+def taper_table(radius: float, kind: str = "gaspari_cohn") -> np.ndarray:
+    """The taper over the squared index distance d2 = 0, 1, ... with compact support at `radius` grid
+    points: entry d2 is the taper at distance sqrt(d2), the table ends before d2 = radius^2 (a point at
+    `radius` or beyond is out of reach), entry 0 is 1.0 and the entries never increase.
+
+    "gaspari_cohn": the fifth-order piecewise rational function of Gaspari & Cohn (1999, eq. 4.10) with
+    half-width radius / 2, so that it reaches zero at `radius`; "boxcar": 1.0 within the radius."""
+    radius = float(radius)
+    if not 0.0 <= radius <= 256.0:
+        raise ValueError(f"taper_table: radius {radius} outside 0..256 (at most {MAX_TAPER} entries)")
+    nt = max(1, min(MAX_TAPER, int(np.ceil(radius * radius))))
+    if kind == "boxcar":
+        return np.ones(nt)
+    if kind != "gaspari_cohn":
+        raise ValueError(f"taper_table: unknown kind {kind!r}")
+    if nt == 1:
+        return np.ones(1)
+    r = np.sqrt(np.arange(nt, dtype=np.longdouble)) / np.longdouble(radius / 2.0)
+    inner = (((-0.25 * r + 0.5) * r + 0.625) * r - 5.0 / np.longdouble(3.0)) * r * r + 1.0
+    ro = np.maximum(r, 1.0)   # (the outer branch divides by r)
+    outer = ((((ro / 12.0 - 0.5) * ro + 0.625) * ro + 5.0 / np.longdouble(3.0)) * ro - 5.0) * ro + 4.0 - 2.0 / (3.0 * ro)
+    t = np.where(r <= 1.0, inner, outer).astype(np.float64)
+    # the polynomial's rounding near the edge of the support, where it cancels to almost nothing, must
+    # not make the table negative or let it rise
+    t = np.minimum.accumulate(np.clip(t, 0.0, 1.0))
+    t[0] = 1.0
+    return t

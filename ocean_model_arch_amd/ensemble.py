@@ -11,10 +11,11 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, ens_local_rule
 from ._lib import check, lib
 from .config import BasinConfig, ParallelConfig, SWConfig
 from .model import BlockInfo, OceanModel
+from .ens_local_rule import taper_table  # noqa: F401  (ensemble.taper_table)
 from .output import UNDEF
 
 # the prognostic state of the shallow-water step: what OceanEnsemble.transform recombines by default
@@ -247,6 +248,73 @@ class OceanEnsemble:
         check(lib().ocn_ens_transform(self.ens, ids, len(names), self._use(members), a.ctypes.data_as(C.c_void_p)),
               "ocn_ens_transform")
         return self
+
+    # ------------------------------------------------------------ localized observation update
+    def local_update(self, y, z, obs_ij, taper, names=STATE, members=None):
+        """The per-point operation of a serial square-root filter with a taper, on the device
+        (ocn_ens_local_update; the rule, its order of operations and its properties are in include/ocn_sw.h):
+        for one observation after another, each point of the real(8) fields `names` within the taper's reach
+        is regressed on the row y[k] of observation-space anomalies and moved along z[k].  `y`, `z`: (nobs, n)
+        float64 arrays of finite values, n the members in use; `obs_ij`: (nobs, 2) 1-based global indices
+        within the basin; `taper`: float64 table over the squared index distance (taper_table).  At most
+        8192 observations a call: a longer list is split, the calls compose bit for bit.  The updated fields
+        count as uploaded.  Asynchronous."""
+        n = self._count(members)
+        ya, za, ta = np.asarray(y), np.asarray(z), np.asarray(taper)
+        for what, a in (("y", ya), ("z", za), ("taper", ta)):
+            if a.dtype != np.float64:
+                raise TypeError(f"local_update: {what} of dtype {a.dtype}, not float64")
+        ij = np.asarray(obs_ij)
+        if ij.dtype.kind not in "iu":
+            raise TypeError(f"local_update: observation indices of dtype {ij.dtype}, not integers")
+        if ij.ndim != 2 or ij.shape[1] != 2 or len(ij) < 1:
+            raise ValueError(f"local_update: observation indices of shape {ij.shape}, not (nobs, 2)")
+        nobs = len(ij)
+        if ya.shape != (nobs, n) or za.shape != (nobs, n):
+            raise ValueError(f"local_update: y and z of shapes {ya.shape} and {za.shape}, not {(nobs, n)} for {nobs} "
+                             f"observations and {n} members in use")
+        if ta.ndim != 1 or not 1 <= len(ta) <= ens_local_rule.MAX_TAPER:
+            raise ValueError(f"local_update: a taper of shape {ta.shape}, not 1..{ens_local_rule.MAX_TAPER} entries")
+        if not (np.isfinite(ya).all() and np.isfinite(za).all() and np.isfinite(ta).all()):
+            raise ValueError("local_update: a y, z or taper value that is not finite")
+        ya, za, ta = np.ascontiguousarray(ya), np.ascontiguousarray(za), np.ascontiguousarray(ta)
+        io, jo = np.ascontiguousarray(ij[:, 0], dtype=np.int32), np.ascontiguousarray(ij[:, 1], dtype=np.int32)
+        names = (names,) if isinstance(names, str) else tuple(names)
+        ids = (C.c_int32 * len(names))(*[_lib.FIELD_ID[nm] for nm in names])
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        check(lib().ocn_ens_local_update(self.ens, ids, len(names), self._use(members), nobs, ptr(io), ptr(jo), ptr(ya),
+                                         ptr(za), ptr(ta), len(ta)), "ocn_ens_local_update")
+        return self
+
+    def block_of(self, i: int, j: int) -> int:
+        """A local block that holds the global point (i, j): the one whose interior does, else the first
+        whose array does (a point of the basin's outer rings)."""
+        blocks = self.members[0].blocks
+        for b in blocks:
+            if b.nx_start <= i <= b.nx_end and b.ny_start <= j <= b.ny_end:
+                return b.k
+        for b in blocks:
+            if b.bnd_x1 <= i <= b.bnd_x2 and b.bnd_y1 <= j <= b.bnd_y2:
+                return b.k
+        raise ValueError(f"point ({i}, {j}) lies in no local block's array")
+
+    def assimilate(self, name: str, obs_ij, values, variances, taper, names=STATE, members=None) -> dict:
+        """A serial ensemble square-root filter (Whitaker & Hamill 2002) with localization: observations
+        `values` of real(8) field `name` at the 1-based global points `obs_ij`, with error variances
+        `variances`, assimilated one after another into the fields `names` of the members in use.
+        sample() brings the members' values at the observed points down once; the observation-space loop
+        (ens_local_rule.ensrf_obs_space) runs on the host and follows the ensemble at those points with the
+        device's own rule; one local_update() does the rest on the device (several for more than 8192
+        observations).  Returns {"innovations", "prior_spread", "posterior_spread", "hx"}: "hx", the (nobs, n)
+        values at the observed points afterwards, is bit for bit what sample() then gives if `name` is among
+        `names`."""
+        ij = np.asarray(obs_ij, dtype=np.int64).reshape(-1, 2)
+        hx = self.sample(name, [(self.block_of(int(i), int(j)), int(i), int(j)) for i, j in ij], members=members)
+        Y, Z, info = ens_local_rule.ensrf_obs_space(hx, ij, values, variances, taper)
+        for k0 in range(0, len(ij), ens_local_rule.MAX_OBS):
+            k1 = k0 + ens_local_rule.MAX_OBS
+            self.local_update(Y[k0:k1], Z[k0:k1], ij[k0:k1], np.asarray(taper, dtype=np.float64), names=names, members=members)
+        return info
 
     @property
     def interior_cells(self) -> int:
