@@ -568,7 +568,7 @@ int ocn_ens_info(ocn_ens *ens, ocn_ens_info_t *out);
  * OCN_ENS_OPT_MAX_GROUP (measurements; 0 = none): at most this many of the members planned in a call go
  * to ocn_ens_plan together (in member order), so that several shorter launches can be timed against
  * one taller one (scripts/ens_bench.py). */
-enum { OCN_ENS_OPT_CAPACITY = 1, OCN_ENS_OPT_MAX_GROUP = 2 };
+enum { OCN_ENS_OPT_CAPACITY = 1, OCN_ENS_OPT_MAX_GROUP = 2, OCN_ENS_OPT_ASSIM_TIMING = 3 };
 int ocn_ens_set_option(ocn_ens *ens, int32_t key, int64_t value);
 
 /* Statistics over the members, formed on the device (the members' fields lie side by side in device
@@ -662,7 +662,8 @@ int ocn_ens_transform(ocn_ens *ens, const int32_t *field_ids, int32_t nfields, c
  * EnSRF, EAKF) with a distance taper, on the device.  ocn_ens_transform applies ONE weight matrix to every
  * point, a global analysis; here each state point is regressed on one observation's ensemble anomalies
  * after another, scaled by a taper of its distance to the observation.  The n-sized algebra in observation
- * space (y and z below) stays with the host.  No counterpart in the reference.
+ * space (y and z below) is the caller's here; ocn_ens_assimilate (below) forms it on the device, so a whole
+ * analysis may stay there.  No counterpart in the reference.
  *
  * The members in use are u0 < u1 < ... < u(n-1) in member order (use as in ocn_ens_stats), n >= 2.
  * Observation k < nobs sits at the library's 1-based global indices (io[k], jo[k]), 1 <= io <= nx and
@@ -699,6 +700,57 @@ int ocn_ens_transform(ocn_ens *ens, const int32_t *field_ids, int32_t nfields, c
 int ocn_ens_local_update(ocn_ens *ens, const int32_t *field_ids, int32_t nfields, const uint8_t *use,
                          int32_t nobs, const int32_t *io, const int32_t *jo,
                          const double *y, const double *z, const double *taper, int32_t ntaper);
+
+/* The serial ensemble square-root filter (Whitaker & Hamill 2002) with a taper, whole, on the device: the
+ * gather at the observed points, the observation-space loop that forms the rows y and z, and
+ * ocn_ens_local_update's field update with them, on the ensemble's stream with no host wait in between.
+ * No counterpart in the reference.
+ *
+ * Members, field_ids, use, io, jo, taper and ntaper are ocn_ens_local_update's, n >= 2.  Observation j < nobs
+ * is `value[j]`, with error variance `variance[j]` (finite, > 0), of real(8) field `obs_field` (which need
+ * not be among field_ids) at (io[j], jo[j]), read in the local block whose interior holds the point, else
+ * the first whose array A(bnd_x1:bnd_x2, bnd_y1:bnd_y2) does.
+ *   Prologue: hx[j][m] = member u_m's value at observation j (what ocn_ens_sample returns for it);
+ *     prior_spread[j] = SPREAD(hx[j]) by ocn_ens_stats' definitions (ordered sum, / (double)n, d = x - mean,
+ *     q = d0 * d0, q = q + d * d, / (double)(n-1), sqrt).
+ *   Loop, k ascending, on the CURRENT row x = hx[k]:
+ *     s1 = x_0;  s1 = s1 + x_m (m = 1 .. n-1);  ybar = s1 / (double)n;  y'_m = x_m - ybar
+ *     q = y'_0 * y'_0;  then p = y'_m * y'_m, q = q + p;  s = q / (double)(n-1)
+ *     D = s + r_k;  d = value_k - ybar;  t = r_k / D;  alpha = 1.0 / (1.0 + sqrt(t));  c = (double)(n-1) * D
+ *     Y[k][m] = y'_m;  Z[k][m] = (d - alpha * y'_m) / c;  innovation[k] = d
+ *     every row j (k itself included) then takes observation k by ocn_ens_local_update's rule, as the state
+ *     point (io[j], jo[j]) with rho = taper[(io[j]-io[k])^2 + (jo[j]-jo[k])^2] (skipped if out of range or
+ *     +-0.0): the rows stay what the fields hold at the observed points if obs_field is among field_ids.
+ *   Epilogue: posterior_spread[j] = SPREAD(final hx[j]); the fields field_ids of every block take the nobs
+ *     observations with the rows Y, Z: the bits ocn_ens_local_update(..., Y, Z, ...) gives, with all of that
+ *     entry's bookkeeping (tails of the members in use formed first, a member not in use untouched, each
+ *     listed field UPLOADED afterwards, nothing else re-formed).
+ * IEEE double arithmetic without contraction, every product rounded before the sum, IEEE division and
+ * sqrt: bitwise reproducible (ens_local_rule.ensrf_obs_space_ordered restates it in numpy).  A non-finite
+ * row value, D or d propagates, as in the update; `nonfinite` counts the observations whose D or d was not
+ * finite, and the remedy is the update's: ocn_ens_extrema, then `use`.
+ * Launches: one for the prologue, the loop and the epilogue together, whatever n and nobs, then the
+ * update's one per field and block an observation's reach meets.  Asynchronous on the ensemble's stream; the
+ * caller's arrays may be reused when the call returns.  OCN_ERR_ARG -- nothing launched, no member's tail,
+ * state or bookkeeping touched, the earlier results kept -- for every case ocn_ens_local_update refuses
+ * (its y and z apart), an obs_field that is real(4) or absent, a value that is not finite, a variance that
+ * is not finite and > 0, an observation in no local block's array.
+ *
+ * The results stay in the ensemble's buffers until the next ocn_ens_assimilate.  ocn_ens_assimilate_info:
+ * the last successful call's counts.  ocn_ens_assimilate_result: one of its arrays into `host` -- HX (the
+ * final rows), Y, Z: nobs x n row-major, unpadded; INNOVATION, PRIOR_SPREAD, POSTERIOR_SPREAD: nobs.  Both
+ * wait for the stream; OCN_ERR_ARG for a null argument, an unknown `what`, or no successful call yet.
+ * Measurements: with OCN_ENS_OPT_ASSIM_TIMING 1 (ocn_ens_set_option; default 0) a call records events around its
+ * stages, and SPANS gives host[0], host[1] = the milliseconds of the observation-space launch and of the
+ * update's launches of that call (OCN_ERR_ARG if the last call was not timed). */
+int ocn_ens_assimilate(ocn_ens *ens, int32_t obs_field, const int32_t *field_ids, int32_t nfields, const uint8_t *use,
+                       int32_t nobs, const int32_t *io, const int32_t *jo, const double *value, const double *variance,
+                       const double *taper, int32_t ntaper);
+typedef struct ocn_ens_assim_info_t { int32_t nobs, n; int64_t nonfinite; } ocn_ens_assim_info_t;
+int ocn_ens_assimilate_info(ocn_ens *ens, ocn_ens_assim_info_t *out);
+enum { OCN_ENS_ASSIM_HX = 0, OCN_ENS_ASSIM_Y = 1, OCN_ENS_ASSIM_Z = 2, OCN_ENS_ASSIM_INNOVATION = 3,
+       OCN_ENS_ASSIM_PRIOR_SPREAD = 4, OCN_ENS_ASSIM_POSTERIOR_SPREAD = 5, OCN_ENS_ASSIM_SPANS = 6 };
+int ocn_ens_assimilate_result(ocn_ens *ens, int32_t what, double *host);
 
 const char *ocn_last_error(void);
 int ocn_abi_version(void);

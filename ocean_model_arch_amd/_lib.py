@@ -105,13 +105,18 @@ CTX_SYMBOLS = ["ocn_decompose", "ocn_halo_schedule", "ocn_ctx_create", "ocn_ctx_
 ENS_SYMBOLS = ["ocn_ens_plan", "ocn_ens_create", "ocn_ens_destroy", "ocn_ens_size", "ocn_ens_member",
                "ocn_ens_init_state", "ocn_ens_step", "ocn_ens_complete", "ocn_ens_synchronize", "ocn_ens_info",
                "ocn_ens_set_option", "ocn_ens_stats", "ocn_ens_stats_download", "ocn_ens_stats_output_r4",
-               "ocn_ens_extrema", "ocn_ens_sample", "ocn_ens_transform", "ocn_ens_local_update"]
+               "ocn_ens_extrema", "ocn_ens_sample", "ocn_ens_transform", "ocn_ens_local_update",
+               "ocn_ens_assimilate", "ocn_ens_assimilate_info", "ocn_ens_assimilate_result"]
 ALL_SYMBOLS = KERNEL_SYMBOLS + CTX_SYMBOLS + ENS_SYMBOLS
 ENS_MAX_MEMBERS = 256          # OCN_ENS_MAX_MEMBERS
 ENS_OPT_CAPACITY = 1
 ENS_OPT_MAX_GROUP = 2
+ENS_OPT_ASSIM_TIMING = 3
 # OCN_ENS_STAT_* (ocn_ens_stats), in the order of their bits
 ENS_STATS = {"mean": 1, "var": 2, "spread": 4, "min": 8, "max": 16}
+# OCN_ENS_ASSIM_* (ocn_ens_assimilate_result)
+ENS_ASSIM_SPANS = 6            # (measurements: OCN_ENS_OPT_ASSIM_TIMING)
+ENS_ASSIM = {"hx": 0, "y": 1, "z": 2, "innovations": 3, "prior_spread": 4, "posterior_spread": 5}
 
 
 class OcnLibraryError(RuntimeError):
@@ -186,6 +191,10 @@ class OcnEnsInfo(C.Structure):
 
 class OcnEnsExtrema(C.Structure):
     _fields_ = [("min", C.c_double), ("max", C.c_double), ("nonfinite", C.c_int64), ("count", C.c_int64)]
+
+
+class OcnEnsAssimInfo(C.Structure):
+    _fields_ = [("nobs", C.c_int32), ("n", C.c_int32), ("nonfinite", C.c_int64)]
 
 
 HALO_LOCAL, HALO_SEND, HALO_RECV = 0, 1, 2
@@ -277,6 +286,10 @@ def lib() -> C.CDLL:
     L.ocn_ens_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.ocn_ens_local_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    L.ocn_ens_assimilate.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    L.ocn_ens_assimilate_info.argtypes = [C.c_void_p, C.POINTER(OcnEnsAssimInfo)]
+    L.ocn_ens_assimilate_result.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     _lib = L
     return L
 

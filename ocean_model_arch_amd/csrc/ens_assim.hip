@@ -1,0 +1,190 @@
+// ens_assim.hip -- the observation-space loop of the serial ensemble square-root filter on the device
+// (ocn_sw.h ocn_ens_assimilate): from the members' arrays to the rows Y and Z that k_ens_local reads.
+//
+// k_ens_obs_space: ONE launch of ONE workgroup of kAsThreads threads.  The dependency is serial
+// (observation k reads what observations 0 .. k-1 left at its point), so the work of one observation is
+// spread over the threads and the observations follow each other behind workgroup barriers.
+//   prologue  hx[j][m] = element off[j] of tab[blk[j] * n + m] (member u_m's array of the block that holds
+//             observation j), gathered by all threads; the padding of the hx, Y and Z rows is written +0.0
+//             (k_ens_local reads it and never uses it); prior[j] = SPREAD(hx[j]).
+//   loop      k ascending, x = the CURRENT row hx[k]:
+//               s1 = x_0; s1 = s1 + x_m;  ybar = s1 / (double)n;  y'_m = x_m - ybar
+//               q = y'_0 y'_0; p = y'_m y'_m, q = q + p;  s = q / (double)(n-1)
+//               D = s + r_k;  d = value_k - ybar;  t = r_k / D;  alpha = 1.0 / (1.0 + sqrt(t));  c = (double)(n-1) D
+//               Y[k][m] = y'_m;  Z[k][m] = (d - alpha y'_m) / c;  innovation[k] = d
+//             thread m copies x_m into LDS; barrier; every lane forms ybar .. c from that copy of row k (the
+//             same address in every lane, the operations ordered: the same bits in every lane, no
+//             broadcast); thread m forms and stores Y[k][m] and Z[k][m], to the rows' table and to LDS -- the
+//             n divisions side by side, not one after another in every lane.  Barrier.  Row j belongs to
+//             thread j mod kAsThreads; its thread takes observation k by k_ens_local's rule with
+//             rho = taper[(io[j]-io[k])^2 + (jo[j]-jo[k])^2], after integer compares on |io[j]-io[k]| and
+//             |jo[j]-jo[k]| against `reach` have rejected what is out of range, reading Y[k] and Z[k] from
+//             LDS.  Barrier.
+//             THREE barriers per observation: after the copy of row k (2 n dependent additions on loads
+//             that each wait for L2 were about half of the kernel's time; from LDS they are not), after Y[k] and
+//             Z[k] (which also keeps the owner of row k from updating it while another wave still reads it),
+//             and after the rows' update, which publishes them to the next observation.  (One barrier
+//             would have every lane form the n quotients of Z[k] for itself.)
+//   epilogue  posterior[j] = SPREAD(final hx[j]);  *nonfinite = the observations whose D or d was not finite.
+// SPREAD is ens_stats.hip's: ordered sum, / (double)n, d = x - mean, q = d0 d0, q = q + d d, / (double)(n-1),
+// sqrt.  -ffp-contract=off and IEEE division / sqrt (Makefile): the bits of
+// ens_local_rule.ensrf_obs_space_ordered.  Member loops run to n, never over padded zero terms (s + 0 turns
+// a -0.0 sum into +0.0).  The rows live in the ensemble's table in global memory (L2-resident: 8192 rows of
+// 256 members are 16 MiB at most, a test's a few KiB), ens_lu_row(n) doubles apart, the layout k_ens_local
+// reads Y and Z in; a thread streams its row through registers kAsChunk members at a time behind constant
+// indices, so nothing goes to scratch, and there is ONE path for every n and nobs.
+// No atomics, no grid barrier, no inline assembly; plain stores.
+#include "ocn_internal.h"
+
+namespace ocn {
+
+// SPREAD of the n values at x
+__device__ __forceinline__ double as_spread(const double *x, int n)
+{
+    double s = x[0];
+    for (int m = 1; m < n; ++m) s = s + x[m];
+    const double mean = s / (double)n;
+    const double d0 = x[0] - mean;
+    double q = d0 * d0;
+    for (int m = 1; m < n; ++m) {
+        const double d = x[m] - mean;
+        q = q + d * d;
+    }
+    return sqrt(q / (double)(n - 1));
+}
+
+// members of a row in flight per thread (32 gained nothing at 64 members and lost half at 8: 256 VGPRs)
+constexpr int kAsChunk = 8;
+static_assert(kAsChunk == kLuRow, "a chunk's loads may run into the row's padding, never beyond it");
+static_assert(OCN_ENS_MAX_MEMBERS % kAsChunk == 0, "... nor beyond the LDS copy of row k");
+
+__global__ __launch_bounds__(kAsThreads) void k_ens_obs_space(const EnsAsArgs a)
+{
+    __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
+    const int tid = (int)threadIdx.x, n = a.n, nobs = a.nobs;
+    const long row = a.row;
+    const double dn = (double)n, dn1 = (double)(n - 1);
+
+    // prologue: the gather, the padding, the prior spread
+    for (long q = tid; q < (long)nobs * row; q += kAsThreads) {
+        const int j = (int)(q / row), m = (int)(q % row);
+        if (m < n) {
+            a.hx[q] = a.tab[(long)a.blk[j] * n + m][a.off[j]];
+        } else {
+            a.hx[q] = 0.0; a.y[q] = 0.0; a.z[q] = 0.0;
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < nobs; j += kAsThreads) a.prior[j] = as_spread(a.hx + (long)j * row, n);
+
+    long bad = 0;   // (thread 0's count)
+    for (int k = 0; k < nobs; ++k) {
+        // row k into LDS, one member per thread: every lane then walks it at LDS latency, not at L2's
+        for (int m = tid; m < n; m += kAsThreads) xk[m] = a.hx[(long)k * row + m];
+        __syncthreads();
+        const double *x = xk;
+        double s1 = 0.0, q = 0.0;
+        for (int m0 = 0; m0 < n; m0 += kAsChunk) {   // (chunks as in the rows' update below)
+            double v[kAsChunk];
+#pragma unroll
+            for (int e = 0; e < kAsChunk; ++e) v[e] = x[m0 + e];
+#pragma unroll
+            for (int e = 0; e < kAsChunk; ++e)
+                if (m0 + e < n) s1 = m0 + e == 0 ? v[e] : s1 + v[e];
+        }
+        const double ybar = s1 / dn;
+        for (int m0 = 0; m0 < n; m0 += kAsChunk) {
+            double v[kAsChunk];
+#pragma unroll
+            for (int e = 0; e < kAsChunk; ++e) v[e] = x[m0 + e];
+#pragma unroll
+            for (int e = 0; e < kAsChunk; ++e)
+                if (m0 + e < n) {
+                    const double ym = v[e] - ybar;
+                    const double p = ym * ym;
+                    q = m0 + e == 0 ? p : q + p;
+                }
+        }
+        const double s = q / dn1;
+        const double r = a.variance[k];
+        const double D = s + r;
+        const double d = a.value[k] - ybar;
+        const double t = r / D;
+        const double alpha = 1.0 / (1.0 + sqrt(t));
+        const double c = dn1 * D;
+        for (int m = tid; m < n; m += kAsThreads) {
+            const double ym = x[m] - ybar;
+            const double zm = (d - alpha * ym) / c;
+            yk[m] = ym; zk[m] = zm;
+            a.y[(long)k * row + m] = ym;
+            a.z[(long)k * row + m] = zm;
+        }
+        if (tid == 0) {
+            a.innovation[k] = d;
+            if (!(isfinite(D) && isfinite(d))) ++bad;
+        }
+        __syncthreads();   // Y[k], Z[k] in LDS; every lane has read row k
+        const int iok = a.io[k], jok = a.jo[k];
+        for (int j = tid; j < nobs; j += kAsThreads) {
+            const int di = a.io[j] - iok, dj = a.jo[j] - jok;   // (both within the basin: no overflow)
+            if (di > a.reach || -di > a.reach || dj > a.reach || -dj > a.reach) continue;
+            const int d2 = di * di + dj * dj;                   // (reach <= 255)
+            if (d2 >= a.ntaper) continue;
+            const double rho = a.taper[d2];
+            if (rho != 0.0) {   // (not +0.0 / -0.0; the table's entries are finite)
+                // the row through registers kAsChunk members at a time: a chunk's loads go out together, the
+                // operations follow in member order (constant indices after unrolling: no scratch)
+                double *xj = a.hx + (long)j * row;
+                double sj = 0.0, acc = 0.0;
+                for (int m0 = 0; m0 < n; m0 += kAsChunk) {
+                    double v[kAsChunk];
+#pragma unroll
+                    for (int e = 0; e < kAsChunk; ++e)
+                        v[e] = xj[m0 + e];   // (the row's padding is there to be read)
+#pragma unroll
+                    for (int e = 0; e < kAsChunk; ++e)
+                        if (m0 + e < n) sj = m0 + e == 0 ? v[e] : sj + v[e];
+                }
+                const double mean = sj / dn;
+                for (int m0 = 0; m0 < n; m0 += kAsChunk) {
+                    double v[kAsChunk];
+#pragma unroll
+                    for (int e = 0; e < kAsChunk; ++e)
+                        v[e] = xj[m0 + e];   // (the row's padding is there to be read)
+#pragma unroll
+                    for (int e = 0; e < kAsChunk; ++e)
+                        if (m0 + e < n) {
+                            const double p = (v[e] - mean) * yk[m0 + e];
+                            acc = m0 + e == 0 ? p : acc + p;
+                        }
+                }
+                const double g = rho * acc;
+                for (int m0 = 0; m0 < n; m0 += kAsChunk) {
+                    double v[kAsChunk];
+#pragma unroll
+                    for (int e = 0; e < kAsChunk; ++e)
+                        v[e] = xj[m0 + e];   // (the row's padding is there to be read)
+#pragma unroll
+                    for (int e = 0; e < kAsChunk; ++e)
+                        if (m0 + e < n) xj[m0 + e] = v[e] + g * zk[m0 + e];
+                }
+            }
+        }
+        __syncthreads();   // the rows as observation k leaves them; yk, zk free
+    }
+
+    for (int j = tid; j < nobs; j += kAsThreads) a.posterior[j] = as_spread(a.hx + (long)j * row, n);
+    if (tid == 0) *a.nonfinite = bad;
+}
+
+int launch_ens_obs_space(const EnsAsArgs &a, hipStream_t s)
+{
+    if (a.n < 2 || a.n > OCN_ENS_MAX_MEMBERS || a.nobs < 1 || a.ntaper < 1 || a.reach < 0 || a.reach > 255 ||
+        a.row != (long)ens_lu_row(a.n) || !a.tab || !a.off || !a.blk || !a.io || !a.jo || !a.value || !a.variance ||
+        !a.taper || !a.hx || !a.y || !a.z || !a.innovation || !a.prior || !a.posterior || !a.nonfinite)
+        return set_error(OCN_ERR_ARG, "ens_obs_space: member count, tables or reach");
+    hipLaunchKernelGGL(k_ens_obs_space, dim3(1), dim3(kAsThreads), 0, s, a);
+    return check_launch();
+}
+
+}  // namespace ocn

@@ -1,7 +1,8 @@
 // ocn_ens.hip -- ensembles (ocn_sw.h ocn_ens_*): many members of a small basin as contexts that share
 // one compute stream, their multi-step launches issued one per group (sw_kernels.hip k_march_multi_b),
 // the statistics over the members (ens_stats.hip), their sampling and recombination
-// (ens_transform.hip) and their localized observation update (ens_local.hip).  The members' calls are planned by ocn_ctx.hip
+// (ens_transform.hip), their localized observation update (ens_local.hip) and the serial filter's
+// observation-space loop in front of it (ens_assim.hip).  The members' calls are planned by ocn_ctx.hip
 // step_impl; ocn_ens_plan.h holds the grouping policy.
 #include "ocn_ctx.h"
 #include "ocn_ens_plan.h"
@@ -55,6 +56,19 @@ struct ocn_ens {
     size_t lu_bytes = 0;
     hipEvent_t ev_lu = nullptr;
     bool ev_lu_set = false;
+    // ocn_ens_assimilate: the call's tables (taper, lists, values, variances, offsets, indices, blocks, the
+    // members' arrays per block), then the device-formed rows hx, y, z and the innovation, prior and
+    // posterior vectors and the count, on the device and in pinned host memory (as_bytes each, grown when a
+    // call needs more; the results come down into h_as at the offsets they have in d_as); ev_as: the stream
+    // has read h_as's tables.  as_last: the last successful call's results (nobs 0: none yet)
+    void *d_as = nullptr, *h_as = nullptr;
+    size_t as_bytes = 0;
+    hipEvent_t ev_as = nullptr;
+    bool ev_as_set = false;
+    struct AsLast { int nobs = 0, n = 0; size_t row = 0, hx_at = 0, vec_at = 0, count_at = 0; bool timed = false; } as_last;
+    // OCN_ENS_OPT_ASSIM_TIMING: events around the observation-space launch and the update's launches
+    bool as_timing = false;
+    hipEvent_t ev_t[3] = {nullptr, nullptr, nullptr};
 };
 
 // ocn_ens_plan's policy: ocn_ens_plan.h (pure host code, also built stand-alone)
@@ -102,6 +116,11 @@ int ocn_ens_destroy(ocn_ens *e)
     if (e->ev_lu) (void)hipEventDestroy(e->ev_lu);
     if (e->d_lu) (void)hipFree(e->d_lu);
     if (e->h_lu) (void)hipHostFree(e->h_lu);
+    if (e->ev_as) (void)hipEventDestroy(e->ev_as);
+    for (hipEvent_t t : e->ev_t)
+        if (t) (void)hipEventDestroy(t);
+    if (e->d_as) (void)hipFree(e->d_as);
+    if (e->h_as) (void)hipHostFree(e->h_as);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
     return OCN_OK;
@@ -315,6 +334,10 @@ int ocn_ens_set_option(ocn_ens *e, int32_t key, int64_t value)
     case OCN_ENS_OPT_MAX_GROUP:
         if (value < 0) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_MAX_GROUP: >= 0");
         e->max_group = value;
+        return OCN_OK;
+    case OCN_ENS_OPT_ASSIM_TIMING:
+        if (value != 0 && value != 1) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_ASSIM_TIMING: 0 or 1");
+        e->as_timing = value != 0;
         return OCN_OK;
     default: return set_error(OCN_ERR_ARG, "unknown ensemble option");
     }
@@ -590,35 +613,44 @@ int ocn_ens_transform(ocn_ens *e, const int32_t *field_ids, int32_t nfields, con
 }
 
 // ------------------------------------------------------------------ localized observation update (ens_local.hip)
-int ocn_ens_local_update(ocn_ens *e, const int32_t *field_ids, int32_t nfields, const uint8_t *use, int32_t nobs,
-                         const int32_t *io, const int32_t *jo, const double *y, const double *z, const double *taper,
-                         int32_t ntaper)
+// What ocn_ens_local_update and ocn_ens_assimilate check alike: the fields, the members in use, the counts,
+// the observations within the basin, the taper.  `who` opens the message.
+static int ens_lu_check(const ocn_ens *e, const std::string &who, const int32_t *field_ids, int32_t nfields,
+                        const std::vector<ocn_ctx *> &in, int32_t nobs, const int32_t *io, const int32_t *jo,
+                        const double *taper, int32_t ntaper)
 {
-    if (!e || !field_ids || !io || !jo || !y || !z || !taper) return set_error(OCN_ERR_ARG, "ens_local_update: null argument");
-    if (nfields < 1) return set_error(OCN_ERR_ARG, "ens_local_update: no field");
+    if (nfields < 1) return set_error(OCN_ERR_ARG, who + ": no field");
     const ocn_ctx *c0 = e->m[0];
     for (int32_t f = 0; f < nfields; ++f) {
-        if (!has_r8(c0, field_ids[f])) return set_error(OCN_ERR_ARG, "ens_local_update: not a real(8) field of the members");
+        if (!has_r8(c0, field_ids[f])) return set_error(OCN_ERR_ARG, who + ": not a real(8) field of the members");
         for (int32_t q = 0; q < f; ++q)
-            if (field_ids[q] == field_ids[f]) return set_error(OCN_ERR_ARG, "ens_local_update: a field named twice");
+            if (field_ids[q] == field_ids[f]) return set_error(OCN_ERR_ARG, who + ": a field named twice");
     }
-    const std::vector<ocn_ctx *> in = ens_in_use(e, use);
-    if (in.size() < 2) return set_error(OCN_ERR_ARG, "ens_local_update: fewer than two members in use");
-    if (nobs < 1 || nobs > 8192) return set_error(OCN_ERR_ARG, "ens_local_update: 1..8192 observations");
-    if (ntaper < 1 || ntaper > 65536) return set_error(OCN_ERR_ARG, "ens_local_update: a taper of 1..65536 entries");
-    const int n = (int)in.size();
+    if (in.size() < 2) return set_error(OCN_ERR_ARG, who + ": fewer than two members in use");
+    if (nobs < 1 || nobs > 8192) return set_error(OCN_ERR_ARG, who + ": 1..8192 observations");
+    if (ntaper < 1 || ntaper > 65536) return set_error(OCN_ERR_ARG, who + ": a taper of 1..65536 entries");
     for (int32_t k = 0; k < nobs; ++k)
         if (io[k] < 1 || io[k] > c0->basin.nx || jo[k] < 1 || jo[k] > c0->basin.ny)
-            return set_error(OCN_ERR_ARG, "ens_local_update: an observation outside the basin");
-    for (size_t q = 0; q < (size_t)nobs * n; ++q)
-        if (!std::isfinite(y[q]) || !std::isfinite(z[q])) return set_error(OCN_ERR_ARG, "ens_local_update: a y or z that is not finite");
+            return set_error(OCN_ERR_ARG, who + ": an observation outside the basin");
     for (int32_t q = 0; q < ntaper; ++q)
-        if (!std::isfinite(taper[q])) return set_error(OCN_ERR_ARG, "ens_local_update: a taper entry that is not finite");
-    int reach = 0;   // the largest r with r * r < ntaper
+        if (!std::isfinite(taper[q])) return set_error(OCN_ERR_ARG, who + ": a taper entry that is not finite");
+    return OCN_OK;
+}
+
+static int ens_lu_reach(int32_t ntaper)   // the largest r with r * r < ntaper
+{
+    int reach = 0;
     while ((reach + 1) * (reach + 1) < ntaper) ++reach;
-    // each block's list: the observations whose box meets the block's array, in the caller's order
+    return reach;
+}
+
+// each block's list: the observations whose box meets the block's array, in the caller's order, filled up
+// to groups of kLuGroup.  Returns the entries of all lists.
+static size_t ens_lu_lists(const ocn_ctx *c0, int32_t nobs, const int32_t *io, const int32_t *jo, int reach,
+                           std::vector<std::vector<EnsLuObs>> &lists)
+{
     const size_t nblk = c0->blocks.size();
-    std::vector<std::vector<EnsLuObs>> lists(nblk);
+    lists.assign(nblk, {});
     size_t list_n = 0;
     for (size_t b = 0; b < nblk; ++b) {
         const ocn_block &g = c0->blocks[b].g;
@@ -628,6 +660,57 @@ int ocn_ens_local_update(ocn_ens *e, const int32_t *field_ids, int32_t nfields, 
         while (lists[b].size() % kLuGroup) lists[b].push_back(ens_lu_filler());
         list_n += lists[b].size();
     }
+    return list_n;
+}
+
+// the lists into the pinned table h from byte `at` on, one after another: list_at[b] the first byte of block b's
+static void ens_lu_put_lists(const std::vector<std::vector<EnsLuObs>> &lists, char *h, size_t at, std::vector<size_t> &list_at)
+{
+    list_at.resize(lists.size());
+    for (size_t b = 0; b < lists.size(); ++b) {
+        list_at[b] = at;
+        if (!lists[b].empty()) memcpy(h + at, lists[b].data(), lists[b].size() * sizeof(EnsLuObs));
+        at += lists[b].size() * sizeof(EnsLuObs);
+    }
+}
+
+// one launch per field and block that an observation reaches (d: the device table the lists are in), then
+// what ocn_ctx_upload of each of these fields leaves behind (also after a failed launch: the arrays may
+// have changed)
+static int ens_lu_launches(const std::vector<ocn_ctx *> &in, const int32_t *field_ids, int32_t nfields,
+                           const std::vector<std::vector<EnsLuObs>> &lists, const char *d, const std::vector<size_t> &list_at,
+                           const double *d_y, const double *d_z, const double *d_taper, int32_t ntaper, int reach, hipStream_t s)
+{
+    const ocn_ctx *c0 = in[0];
+    const int n = (int)in.size();
+    int rc = OCN_OK;
+    std::vector<double *> mem((size_t)n);
+    for (int32_t f = 0; f < nfields && !rc; ++f)
+        for (size_t k = 0; k < lists.size() && !rc; ++k) {
+            if (lists[k].empty()) continue;   // no observation reaches this block
+            for (int a = 0; a < n; ++a) mem[(size_t)a] = (double *)in[(size_t)a]->blocks[k].ptr[field_slot(field_ids[f])];
+            rc = launch_ens_local(&c0->blocks[k].g, mem.data(), n, (const EnsLuObs *)(d + list_at[k]),
+                                  (int)(lists[k].size() / kLuGroup), d_y, d_z, d_taper, ntaper, reach, s);
+        }
+    for (ocn_ctx *c : in)
+        for (int32_t f = 0; f < nfields; ++f) field_uploaded(c, field_ids[f]);
+    return rc;
+}
+
+int ocn_ens_local_update(ocn_ens *e, const int32_t *field_ids, int32_t nfields, const uint8_t *use, int32_t nobs,
+                         const int32_t *io, const int32_t *jo, const double *y, const double *z, const double *taper,
+                         int32_t ntaper)
+{
+    if (!e || !field_ids || !io || !jo || !y || !z || !taper) return set_error(OCN_ERR_ARG, "ens_local_update: null argument");
+    const ocn_ctx *c0 = e->m[0];
+    const std::vector<ocn_ctx *> in = ens_in_use(e, use);
+    RC(ens_lu_check(e, "ens_local_update", field_ids, nfields, in, nobs, io, jo, taper, ntaper));
+    const int n = (int)in.size();
+    for (size_t q = 0; q < (size_t)nobs * n; ++q)
+        if (!std::isfinite(y[q]) || !std::isfinite(z[q])) return set_error(OCN_ERR_ARG, "ens_local_update: a y or z that is not finite");
+    const int reach = ens_lu_reach(ntaper);
+    std::vector<std::vector<EnsLuObs>> lists;
+    const size_t list_n = ens_lu_lists(c0, nobs, io, jo, reach, lists);
     HIPCHK(hipSetDevice(e->device));
     // the buffers first (a failed allocation leaves the members as they were): rows, taper, lists
     const size_t rows_b = (size_t)nobs * ens_lu_row(n) * sizeof(double), tap_b = ((size_t)ntaper * sizeof(double) + 255) / 256 * 256,
@@ -657,31 +740,174 @@ int ocn_ens_local_update(ocn_ens *e, const int32_t *field_ids, int32_t nfields, 
             hz[(size_t)k * row + m] = z[(size_t)k * n + m];
         }
     memcpy(h + 2 * rows_b, taper, (size_t)ntaper * sizeof(double));
-    std::vector<size_t> list_at(nblk);
-    size_t at = 2 * rows_b + tap_b;
-    for (size_t b = 0; b < nblk; ++b) {
-        list_at[b] = at;
-        if (!lists[b].empty()) memcpy(h + at, lists[b].data(), lists[b].size() * sizeof(EnsLuObs));
-        at += lists[b].size() * sizeof(EnsLuObs);
-    }
+    std::vector<size_t> list_at;
+    ens_lu_put_lists(lists, h, 2 * rows_b + tap_b, list_at);
     HIPCHK(hipMemcpyAsync(d, h, need, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipEventRecord(e->ev_lu, e->stream));
     e->ev_lu_set = true;
-    int rc = OCN_OK;
-    std::vector<double *> mem((size_t)n);
-    for (int32_t f = 0; f < nfields && !rc; ++f)
-        for (size_t k = 0; k < nblk && !rc; ++k) {
-            if (lists[k].empty()) continue;   // no observation reaches this block
-            for (int a = 0; a < n; ++a) mem[(size_t)a] = (double *)in[(size_t)a]->blocks[k].ptr[field_slot(field_ids[f])];
-            rc = launch_ens_local(&c0->blocks[k].g, mem.data(), n, (const EnsLuObs *)(d + list_at[k]),
-                                  (int)(lists[k].size() / kLuGroup), (const double *)d, (const double *)(d + rows_b),
-                                  (const double *)(d + 2 * rows_b), ntaper, reach, e->stream);
+    return ens_lu_launches(in, field_ids, nfields, lists, d, list_at, (const double *)d, (const double *)(d + rows_b),
+                           (const double *)(d + 2 * rows_b), ntaper, reach, e->stream);
+}
+
+// ------------------------------------------------------------------ the serial filter on the device (ens_assim.hip)
+// Launches per call: kAsLaunches for the observation-space stage (k_ens_obs_space, whatever n and nobs), then
+// ocn_ens_local_update's: one per listed field and block that an observation reaches.
+constexpr int kAsLaunches = 1;
+static_assert(kAsLaunches == 1, "ocn_sw.h and DESIGN.md state this count");
+
+int ocn_ens_assimilate(ocn_ens *e, int32_t obs_field, const int32_t *field_ids, int32_t nfields, const uint8_t *use,
+                       int32_t nobs, const int32_t *io, const int32_t *jo, const double *value, const double *variance,
+                       const double *taper, int32_t ntaper)
+{
+    if (!e || !field_ids || !io || !jo || !value || !variance || !taper) return set_error(OCN_ERR_ARG, "ens_assimilate: null argument");
+    const ocn_ctx *c0 = e->m[0];
+    const std::vector<ocn_ctx *> in = ens_in_use(e, use);
+    RC(ens_lu_check(e, "ens_assimilate", field_ids, nfields, in, nobs, io, jo, taper, ntaper));
+    if (!has_r8(c0, obs_field)) return set_error(OCN_ERR_ARG, "ens_assimilate: the observed field is not a real(8) field of the members");
+    for (int32_t k = 0; k < nobs; ++k) {
+        if (!std::isfinite(value[k])) return set_error(OCN_ERR_ARG, "ens_assimilate: a value that is not finite");
+        if (!std::isfinite(variance[k]) || !(variance[k] > 0.0))
+            return set_error(OCN_ERR_ARG, "ens_assimilate: a variance that is not finite and positive");
+    }
+    const size_t n = in.size(), nblk = c0->blocks.size(), no = (size_t)nobs;
+    // each observation's block -- the one whose interior holds the point, else the first whose array does --
+    // and its element there
+    std::vector<long> off(no);
+    std::vector<int> blk(no);
+    for (size_t k = 0; k < no; ++k) {
+        int at = -1;
+        for (size_t b = 0; b < nblk && at < 0; ++b) {
+            const ocn_block &g = c0->blocks[b].g;
+            if (io[k] >= g.nx_start && io[k] <= g.nx_end && jo[k] >= g.ny_start && jo[k] <= g.ny_end) at = (int)b;
         }
-    // what ocn_ctx_upload of each of these fields leaves behind (also after a failed launch: the arrays
-    // may have changed)
-    for (ocn_ctx *c : in)
-        for (int32_t f = 0; f < nfields; ++f) field_uploaded(c, field_ids[f]);
+        for (size_t b = 0; b < nblk && at < 0; ++b) {
+            const ocn_block &g = c0->blocks[b].g;
+            if (io[k] >= g.bnd_x1 && io[k] <= g.bnd_x2 && jo[k] >= g.bnd_y1 && jo[k] <= g.bnd_y2) at = (int)b;
+        }
+        if (at < 0) return set_error(OCN_ERR_ARG, "ens_assimilate: an observation in no local block's array");
+        const ocn_block &g = c0->blocks[(size_t)at].g;
+        blk[k] = at;
+        off[k] = (long)(jo[k] - g.bnd_y1) * (long)g.pitch + (io[k] - g.bnd_x1);
+    }
+    const int reach = ens_lu_reach(ntaper);
+    std::vector<std::vector<EnsLuObs>> lists;
+    const size_t list_n = ens_lu_lists(c0, nobs, io, jo, reach, lists);
+    HIPCHK(hipSetDevice(e->device));
+    // one layout on both sides, every part on a 256-B line: the tables that go up, then what the device forms
+    auto part = [](size_t at, size_t bytes) { return at + (bytes + 255) / 256 * 256; };
+    const size_t row = ens_lu_row((int)n), rows_b = no * row * sizeof(double);
+    const size_t tap_at = 0, list_at0 = part(tap_at, (size_t)ntaper * sizeof(double)), val_at = part(list_at0, list_n * sizeof(EnsLuObs)),
+                 var_at = part(val_at, no * 8), off_at = part(var_at, no * 8), io_at = part(off_at, no * sizeof(long)),
+                 jo_at = part(io_at, no * 4), blk_at = part(jo_at, no * 4), tab_at = part(blk_at, no * 4),
+                 up_b = part(tab_at, nblk * n * sizeof(double *)), hx_at = up_b, y_at = part(hx_at, rows_b),
+                 z_at = part(y_at, rows_b), vec_at = part(z_at, rows_b), count_at = part(vec_at, 3 * no * 8),
+                 need = part(count_at, sizeof(long));
+    // the buffers first (a failed allocation leaves the members as they were, and no earlier result)
+    if (!e->ev_as) HIPCHK(hipEventCreateWithFlags(&e->ev_as, hipEventDisableTiming));
+    const bool timed = e->as_timing;
+    for (int i = 0; i < 3 && timed; ++i)
+        if (!e->ev_t[i]) HIPCHK(hipEventCreate(&e->ev_t[i]));
+    if (e->as_bytes < need) {
+        if (e->ev_as_set) HIPCHK(hipEventSynchronize(e->ev_as));
+        if (e->d_as) (void)hipFree(e->d_as);   // (waits for the launches that use it)
+        if (e->h_as) (void)hipHostFree(e->h_as);
+        e->d_as = e->h_as = nullptr;
+        e->as_bytes = 0;
+        e->as_last = ocn_ens::AsLast{};
+        const size_t grown = (need + 65535) / 65536 * 65536;
+        HIPCHK(hipMalloc(&e->d_as, grown));
+        HIPCHK(hipHostMalloc(&e->h_as, grown, hipHostMallocDefault));
+        e->as_bytes = grown;
+    }
+    for (ocn_ctx *c : in) RC(guarded(c, "ocn_ens_assimilate", [&] { return complete_open(c); }));
+    // the tables up from pinned memory in one copy, ahead of the launches; the members' arrays as the field
+    // tables name them now
+    if (e->ev_as_set) HIPCHK(hipEventSynchronize(e->ev_as));
+    char *h = (char *)e->h_as, *d = (char *)e->d_as;
+    memcpy(h + tap_at, taper, (size_t)ntaper * sizeof(double));
+    std::vector<size_t> list_at;
+    ens_lu_put_lists(lists, h, list_at0, list_at);
+    memcpy(h + val_at, value, no * 8);
+    memcpy(h + var_at, variance, no * 8);
+    memcpy(h + off_at, off.data(), no * sizeof(long));
+    memcpy(h + io_at, io, no * 4);
+    memcpy(h + jo_at, jo, no * 4);
+    memcpy(h + blk_at, blk.data(), no * 4);
+    for (size_t b = 0; b < nblk; ++b)
+        for (size_t m = 0; m < n; ++m)
+            ((const double **)(h + tab_at))[b * n + m] = (const double *)in[m]->blocks[b].ptr[field_slot(obs_field)];
+    e->as_last = ocn_ens::AsLast{};   // (the results of the call before are overwritten from here on)
+    HIPCHK(hipMemcpyAsync(d, h, up_b, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipEventRecord(e->ev_as, e->stream));
+    e->ev_as_set = true;
+    EnsAsArgs a{};
+    a.tab = (const double *const *)(d + tab_at); a.off = (const long *)(d + off_at); a.blk = (const int *)(d + blk_at);
+    a.io = (const int *)(d + io_at); a.jo = (const int *)(d + jo_at);
+    a.value = (const double *)(d + val_at); a.variance = (const double *)(d + var_at); a.taper = (const double *)(d + tap_at);
+    a.hx = (double *)(d + hx_at); a.y = (double *)(d + y_at); a.z = (double *)(d + z_at);
+    a.innovation = (double *)(d + vec_at); a.prior = a.innovation + no; a.posterior = a.prior + no;
+    a.nonfinite = (long *)(d + count_at);
+    a.row = (long)row; a.n = (int)n; a.nobs = nobs; a.ntaper = ntaper; a.reach = reach;
+    if (timed) HIPCHK(hipEventRecord(e->ev_t[0], e->stream));
+    RC(launch_ens_obs_space(a, e->stream));
+    if (timed) HIPCHK(hipEventRecord(e->ev_t[1], e->stream));
+    const int rc = ens_lu_launches(in, field_ids, nfields, lists, d, list_at, a.y, a.z, a.taper, ntaper, reach, e->stream);
+    if (timed) HIPCHK(hipEventRecord(e->ev_t[2], e->stream));
+    if (!rc) e->as_last = ocn_ens::AsLast{nobs, (int)n, row, hx_at, vec_at, count_at, timed};
     return rc;
+}
+
+// bytes [at, at + bytes) of the last call's results into the pinned copy, with one wait
+static int ens_as_down(ocn_ens *e, size_t at, size_t bytes)
+{
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipMemcpyAsync((char *)e->h_as + at, (const char *)e->d_as + at, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return OCN_OK;
+}
+
+int ocn_ens_assimilate_info(ocn_ens *e, ocn_ens_assim_info_t *out)
+{
+    if (!e || !out) return set_error(OCN_ERR_ARG, "ens_assimilate_info: null argument");
+    const ocn_ens::AsLast &l = e->as_last;
+    if (l.nobs < 1) return set_error(OCN_ERR_ARG, "ens_assimilate_info: no successful ocn_ens_assimilate yet");
+    RC(ens_as_down(e, l.count_at, sizeof(long)));
+    out->nobs = l.nobs;
+    out->n = l.n;
+    out->nonfinite = (int64_t) * (const long *)((const char *)e->h_as + l.count_at);
+    return OCN_OK;
+}
+
+int ocn_ens_assimilate_result(ocn_ens *e, int32_t what, double *host)
+{
+    if (!e || !host) return set_error(OCN_ERR_ARG, "ens_assimilate_result: null argument");
+    const ocn_ens::AsLast &l = e->as_last;
+    if (l.nobs < 1) return set_error(OCN_ERR_ARG, "ens_assimilate_result: no successful ocn_ens_assimilate yet");
+    const size_t no = (size_t)l.nobs, n = (size_t)l.n;
+    if (what >= OCN_ENS_ASSIM_HX && what <= OCN_ENS_ASSIM_Z) {   // hx, y, z: one after another, each on a 256-B line
+        const size_t rows_b = (no * l.row * sizeof(double) + 255) / 256 * 256, at = l.hx_at + (size_t)(what - OCN_ENS_ASSIM_HX) * rows_b;
+        RC(ens_as_down(e, at, no * l.row * sizeof(double)));
+        const double *src = (const double *)((const char *)e->h_as + at);
+        for (size_t k = 0; k < no; ++k) memcpy(host + k * n, src + k * l.row, n * sizeof(double));
+        return OCN_OK;
+    }
+    if (what >= OCN_ENS_ASSIM_INNOVATION && what <= OCN_ENS_ASSIM_POSTERIOR_SPREAD) {
+        const size_t at = l.vec_at + (size_t)(what - OCN_ENS_ASSIM_INNOVATION) * no * 8;
+        RC(ens_as_down(e, at, no * 8));
+        memcpy(host, (const char *)e->h_as + at, no * 8);
+        return OCN_OK;
+    }
+    if (what == OCN_ENS_ASSIM_SPANS && l.timed) {   // (measurements: the two spans between the call's events, ms)
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipEventSynchronize(e->ev_t[2]));
+        float ms[2] = {0.f, 0.f};
+        HIPCHK(hipEventElapsedTime(&ms[0], e->ev_t[0], e->ev_t[1]));
+        HIPCHK(hipEventElapsedTime(&ms[1], e->ev_t[1], e->ev_t[2]));
+        host[0] = (double)ms[0];
+        host[1] = (double)ms[1];
+        return OCN_OK;
+    }
+    return set_error(OCN_ERR_ARG, "ens_assimilate_result: what = OCN_ENS_ASSIM_*");
 }
 
 }  // extern "C"

@@ -272,6 +272,20 @@ inline EnsLuObs ens_lu_filler() { return EnsLuObs{-(1 << 30), -(1 << 30), 0, 0};
 inline size_t ens_lu_row(int n) { return (size_t)(n + kLuRow - 1) / kLuRow * kLuRow; }
 int launch_ens_local(const ocn_block *b, double *const *mem, int n, const EnsLuObs *d_list, int ngroups, const double *d_y,
                      const double *d_z, const double *d_taper, int ntaper, int reach, hipStream_t s);
+// The observation-space loop of the serial filter (ens_assim.hip; ocn_sw.h ocn_ens_assimilate), every
+// pointer on the device.  tab[b * n + m]: member u_m's array of the observed field on block b; observation j
+// is element off[j] of block blk[j]'s arrays, at the global indices (io[j], jo[j]).  hx, y, z: nobs rows,
+// row = ens_lu_row(n) doubles apart (hx: gathered, then followed through the loop; y, z: formed; their
+// padding written +0.0); innovation, prior, posterior: nobs doubles; nonfinite: one count.  ONE launch of
+// ONE workgroup of kAsThreads threads, whatever n and nobs.
+constexpr int kAsThreads = 256;
+struct EnsAsArgs {
+    const double *const *tab; const long *off; const int *blk, *io, *jo;
+    const double *value, *variance, *taper;
+    double *hx, *y, *z, *innovation, *prior, *posterior; long *nonfinite;
+    long row; int n, nobs, ntaper, reach;
+};
+int launch_ens_obs_space(const EnsAsArgs &a, hipStream_t s);
 // the known-constant precondition of launch_onepass over r (sw_kernels.hip FallbackCheck: the
 // fallback points and the forcing hold +0.0, h_r and mu are uniform): ORs 1 into *flag where it
 // does not hold; writes h_r and mu at (r.m0, r.n0) to kc[0], kc[1]

@@ -5,7 +5,9 @@ observation-space loop of a serial ensemble square-root filter built on it, and 
 numpy's elementwise subtract, multiply, add and divide are single IEEE double operations per element and
 nothing here is fused, so `local_rule` gives the device's bits.  OceanEnsemble.assimilate tracks the
 ensemble at the observed points with it; tests/ens_local_ref.py hands the same function to the tests, which
-check it against a scalar loop.  Pure numpy: no device, no library.
+check it against a scalar loop.  `ensrf_obs_space_ordered` is that loop as ocn_ens_assimilate runs it on the
+device: its sums in member order (tests/ens_assim_ref.py hands it to the tests).  Pure numpy: no device, no
+library.
 """
 from __future__ import annotations
 
@@ -125,6 +127,78 @@ def ensrf_obs_space(hx, obs_ij, values, variances, taper):
                           Y[k:k + 1], Z[k:k + 1], taper)
         hx = np.stack(cols, axis=1)
     return Y, Z, {"hx": hx, "innovations": innov, "prior_spread": prior, "posterior_spread": hx.std(axis=1, ddof=1)}
+
+
+def _spread(row):
+    """SPREAD of ocn_ens_stats over one row: ordered sum, / n, d = x - mean, q = d0 d0, q = q + d d,
+    / (n - 1), sqrt."""
+    n = len(row)
+    s = row[0]
+    for m in range(1, n):
+        s = s + row[m]
+    mean = s / np.float64(n)
+    d = row[0] - mean
+    q = d * d
+    for m in range(1, n):
+        d = row[m] - mean
+        q = q + d * d
+    return np.sqrt(q / np.float64(n - 1))
+
+
+def ensrf_obs_space_ordered(hx, obs_ij, values, variances, taper):
+    """ocn_ens_assimilate's observation-space loop (include/ocn_sw.h) in numpy, with explicit member loops:
+    `ensrf_obs_space` with its two np.sum calls -- whose reduction order is numpy's own -- replaced by sums in
+    member order, and the spreads by ocn_ens_stats' ordered definitions.  Every operation is one IEEE double
+    operation on numpy float64 scalars, nothing is fused: the device's bits.
+
+    For k in order, with x the CURRENT row k:  s1 = x_0, s1 = s1 + x_m;  ybar = s1 / n;  y'_m = x_m - ybar;
+    q = y'_0 y'_0, p = y'_m y'_m, q = q + p;  s = q / (n - 1);  D = s + r_k;  d = value_k - ybar;  t = r_k / D;
+    alpha = 1 / (1 + sqrt(t));  c = (n - 1) D;  Y[k][m] = y'_m, Z[k][m] = (d - alpha y'_m) / c;  then every row
+    takes observation k by `local_rule`.  Returns (Y, Z, info) as `ensrf_obs_space` does; a non-finite row
+    value, D or d propagates, and info["nonfinite"] counts the observations whose D or d was not finite."""
+    hx = np.array(hx, dtype=np.float64, copy=True)
+    nobs, n = hx.shape
+    ij = np.asarray(obs_ij, dtype=np.int64).reshape(nobs, 2)
+    values, variances = np.asarray(values, dtype=np.float64).ravel(), np.asarray(variances, dtype=np.float64).ravel()
+    if n < 2 or len(values) != nobs or len(variances) != nobs:
+        raise ValueError("ensrf_obs_space_ordered: hx (nobs, n >= 2) with nobs values and variances")
+    if not (variances > 0.0).all() or not np.isfinite(variances).all() or not np.isfinite(values).all():
+        raise ValueError("ensrf_obs_space_ordered: finite values and positive finite variances")
+    Y, Z = np.zeros((nobs, n)), np.zeros((nobs, n))
+    innov = np.zeros(nobs)
+    nonfinite = 0
+    dn, dn1, one = np.float64(n), np.float64(n - 1), np.float64(1.0)
+    with np.errstate(all="ignore"):
+        prior = np.array([_spread(hx[j]) for j in range(nobs)])
+        for k in range(nobs):
+            x = hx[k]
+            s1 = x[0]
+            for m in range(1, n):
+                s1 = s1 + x[m]
+            ybar = s1 / dn
+            yp = [x[m] - ybar for m in range(n)]
+            q = yp[0] * yp[0]
+            for m in range(1, n):
+                p = yp[m] * yp[m]
+                q = q + p
+            s = q / dn1
+            r = variances[k]
+            D = s + r
+            d = values[k] - ybar
+            t = r / D
+            alpha = one / (one + np.sqrt(t))
+            c = dn1 * D
+            for m in range(n):
+                Y[k, m] = yp[m]
+                Z[k, m] = (d - alpha * yp[m]) / c
+            innov[k] = d
+            if not (np.isfinite(D) and np.isfinite(d)):
+                nonfinite += 1
+            cols = local_rule([hx[:, m] for m in range(n)], ij[:, 0], ij[:, 1], ij[k:k + 1, 0], ij[k:k + 1, 1],
+                              Y[k:k + 1], Z[k:k + 1], taper)
+            hx = np.stack(cols, axis=1)
+        post = np.array([_spread(hx[j]) for j in range(nobs)])
+    return Y, Z, {"hx": hx, "innovations": innov, "prior_spread": prior, "posterior_spread": post, "nonfinite": nonfinite}
 
 
 def taper_table(radius: float, kind: str = "gaspari_cohn") -> np.ndarray:

@@ -298,7 +298,7 @@ class OceanEnsemble:
                 return b.k
         raise ValueError(f"point ({i}, {j}) lies in no local block's array")
 
-    def assimilate(self, name: str, obs_ij, values, variances, taper, names=STATE, members=None) -> dict:
+    def assimilate(self, name: str, obs_ij, values, variances, taper, names=STATE, members=None, device: bool = False) -> dict:
         """A serial ensemble square-root filter (Whitaker & Hamill 2002) with localization: observations
         `values` of real(8) field `name` at the 1-based global points `obs_ij`, with error variances
         `variances`, assimilated one after another into the fields `names` of the members in use.
@@ -307,7 +307,17 @@ class OceanEnsemble:
         device's own rule; one local_update() does the rest on the device (several for more than 8192
         observations).  Returns {"innovations", "prior_spread", "posterior_spread", "hx"}: "hx", the (nobs, n)
         values at the observed points afterwards, is bit for bit what sample() then gives if `name` is among
-        `names`."""
+        `names`.
+
+        device=True: the whole analysis on the device (ocn_ens_assimilate: gather, observation-space loop and
+        field update on the ensemble's stream, no wait in between; its sums are in member order --
+        ens_local_rule.ensrf_obs_space_ordered -- so beyond a handful of members its last bits are not the
+        host path's).  The same four keys, read back afterwards (one wait), plus "nonfinite", the observations
+        whose innovation or innovation variance was not finite.  More than 8192 observations are split into
+        calls of 8192 only if `name` is among `names` (the next call's gather then reads what the previous
+        update left: the split composes); otherwise ValueError."""
+        if device:
+            return self._assimilate_device(name, obs_ij, values, variances, taper, names, members)
         ij = np.asarray(obs_ij, dtype=np.int64).reshape(-1, 2)
         hx = self.sample(name, [(self.block_of(int(i), int(j)), int(i), int(j)) for i, j in ij], members=members)
         Y, Z, info = ens_local_rule.ensrf_obs_space(hx, ij, values, variances, taper)
@@ -315,6 +325,77 @@ class OceanEnsemble:
             k1 = k0 + ens_local_rule.MAX_OBS
             self.local_update(Y[k0:k1], Z[k0:k1], ij[k0:k1], np.asarray(taper, dtype=np.float64), names=names, members=members)
         return info
+
+    def _assimilate_device(self, name, obs_ij, values, variances, taper, names, members) -> dict:
+        n = self._count(members)
+        ij = np.asarray(obs_ij)
+        if ij.dtype.kind not in "iu":
+            raise TypeError(f"assimilate: observation indices of dtype {ij.dtype}, not integers")
+        if ij.ndim != 2 or ij.shape[1] != 2 or len(ij) < 1:
+            raise ValueError(f"assimilate: observation indices of shape {ij.shape}, not (nobs, 2)")
+        nobs = len(ij)
+        va = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
+        ra = np.ascontiguousarray(np.asarray(variances, dtype=np.float64).ravel())
+        ta = np.ascontiguousarray(np.asarray(taper, dtype=np.float64))
+        if len(va) != nobs or len(ra) != nobs:
+            raise ValueError(f"assimilate: {len(va)} values and {len(ra)} variances for {nobs} observations")
+        if ta.ndim != 1 or not 1 <= len(ta) <= ens_local_rule.MAX_TAPER:
+            raise ValueError(f"assimilate: a taper of shape {ta.shape}, not 1..{ens_local_rule.MAX_TAPER} entries")
+        names = (names,) if isinstance(names, str) else tuple(names)
+        if nobs > ens_local_rule.MAX_OBS and name not in names:
+            raise ValueError(f"assimilate: {nobs} observations of {name!r}, which is not among the updated fields {names}: "
+                             f"calls of {ens_local_rule.MAX_OBS} would not compose")
+        ids = (C.c_int32 * len(names))(*[_lib.FIELD_ID[nm] for nm in names])
+        io, jo = np.ascontiguousarray(ij[:, 0], dtype=np.int32), np.ascontiguousarray(ij[:, 1], dtype=np.int32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        L = lib()
+        parts = {k: [] for k in ("hx", "innovations", "prior_spread", "posterior_spread")}
+        nonfinite = 0
+        for k0 in range(0, nobs, ens_local_rule.MAX_OBS):
+            k1 = min(k0 + ens_local_rule.MAX_OBS, nobs)
+            i_, j_, v_, r_ = (np.ascontiguousarray(a[k0:k1]) for a in (io, jo, va, ra))
+            check(L.ocn_ens_assimilate(self.ens, _lib.FIELD_ID[name], ids, len(names), self._use(members), k1 - k0, ptr(i_),
+                                       ptr(j_), ptr(v_), ptr(r_), ptr(ta), len(ta)), "ocn_ens_assimilate")
+            for key in parts:
+                a = np.zeros((k1 - k0, n) if key == "hx" else k1 - k0, dtype=np.float64)
+                check(L.ocn_ens_assimilate_result(self.ens, _lib.ENS_ASSIM[key], ptr(a)), "ocn_ens_assimilate_result")
+                parts[key].append(a)
+            info = _lib.OcnEnsAssimInfo()
+            check(L.ocn_ens_assimilate_info(self.ens, C.byref(info)), "ocn_ens_assimilate_info")
+            nonfinite += int(info.nonfinite)
+        out = {k: np.concatenate(v) for k, v in parts.items()}
+        # (a row of an earlier call that a later call's observations reach: its final values are the fields')
+        if nobs > ens_local_rule.MAX_OBS:
+            out["hx"] = self.sample(name, [(self.block_of(int(i), int(j)), int(i), int(j)) for i, j in ij], members=members)
+            with np.errstate(all="ignore"):
+                out["posterior_spread"] = np.array([ens_local_rule._spread(r) for r in out["hx"]])
+        out["nonfinite"] = nonfinite
+        return out
+
+    def set_assim_timing(self, on: bool = True):
+        """Measurements: assimilate(device=True) records events around its two stages (assimilate_spans)."""
+        check(lib().ocn_ens_set_option(self.ens, _lib.ENS_OPT_ASSIM_TIMING, int(bool(on))), "ocn_ens_set_option")
+        return self
+
+    def assimilate_spans(self) -> dict:
+        """The last timed assimilate(device=True) call: the milliseconds of its observation-space launch and of
+        its update launches, between events on the ensemble's stream."""
+        ms = (C.c_double * 2)()
+        check(lib().ocn_ens_assimilate_result(self.ens, _lib.ENS_ASSIM_SPANS, ms), "ocn_ens_assimilate_result")
+        return {"obs_space_ms": float(ms[0]), "update_ms": float(ms[1])}
+
+    def assimilate_results(self, what=("y", "z")) -> dict:
+        """Arrays of the last assimilate(device=True) call (ocn_ens_assimilate_result; one wait each): any of
+        "hx", "y", "z" (nobs, n) and "innovations", "prior_spread", "posterior_spread" (nobs)."""
+        info = _lib.OcnEnsAssimInfo()
+        check(lib().ocn_ens_assimilate_info(self.ens, C.byref(info)), "ocn_ens_assimilate_info")
+        out = {}
+        for key in ((what,) if isinstance(what, str) else tuple(what)):
+            a = np.zeros((info.nobs, info.n) if key in ("hx", "y", "z") else info.nobs, dtype=np.float64)
+            check(lib().ocn_ens_assimilate_result(self.ens, _lib.ENS_ASSIM[key], a.ctypes.data_as(C.c_void_p)),
+                  "ocn_ens_assimilate_result")
+            out[key] = a
+        return out
 
     @property
     def interior_cells(self) -> int:
