@@ -752,6 +752,61 @@ enum { OCN_ENS_ASSIM_HX = 0, OCN_ENS_ASSIM_Y = 1, OCN_ENS_ASSIM_Z = 2, OCN_ENS_A
        OCN_ENS_ASSIM_PRIOR_SPREAD = 4, OCN_ENS_ASSIM_POSTERIOR_SPREAD = 5, OCN_ENS_ASSIM_SPANS = 6 };
 int ocn_ens_assimilate_result(ocn_ens *ens, int32_t what, double *host);
 
+/* Covariance inflation on the device: what keeps a square-root filter's spread from collapsing over the
+ * cycles.  ocn_ens_transform can apply ONE factor to every point (n^2 work per point, and it inflates the
+ * points no observation reached as well); relaxation to prior spread (RTPS, Whitaker & Hamill 2012) needs a
+ * factor per point: the analysis spread is pulled back toward the spread the ensemble had before the
+ * analysis.  A cycle is ocn_ens_step, ocn_ens_spread_save, ocn_ens_assimilate, ocn_ens_inflate, ocn_ens_step:
+ * asynchronous calls on the ensemble's stream with no host wait.  No counterpart in the reference.
+ *
+ * In both entries the members in use are u0 < u1 < ... < u(n-1) in member order (use as in ocn_ens_stats),
+ * n >= 2, the fields are field_ids[0 .. nfields), real(8) only, every local block is processed at every
+ * point of A(bnd_x1:bnd_x2, bnd_y1:bnd_y2) (row padding and the extra rings are neither read nor written),
+ * the pending call tail of every member in use is formed first and a member not in use is not touched.
+ *
+ * ocn_ens_spread_save: for each listed field and block, SPREAD by ocn_ens_stats' definition, bit for bit,
+ * over the members in use, into a buffer the ensemble owns (one per field and block, in the members' layout,
+ * allocated at first use, freed by ocn_ens_destroy), and it remembers per field which members were in use.
+ * It writes no member: nothing counts as uploaded.  One launch per field and block.  A saved spread stays
+ * valid until the next save of that field.
+ *
+ * ocn_ens_inflate: per field, block and point, with x_m member u_m's value -- each line one IEEE double
+ * operation, no contraction, products rounded before sums, IEEE division and sqrt:
+ *   s = x_0;  s = s + x_m (m = 1 .. n-1);  mean = s / (double)n
+ *   d_m = x_m - mean
+ *   q = d_0 d_0;  p = d_m d_m, q = q + p (m = 1 .. n-1);  var = q / (double)(n-1);  sa = sqrt(var)
+ *   CONST:  f = alpha                          (applies where sa > 0 and sa is finite)
+ *   RTPS:   sb = the saved spread at the point (applies where sa > 0, sa finite and sb finite)
+ *           t = sb - sa;  r = t / sa;  g = alpha * r;  f = 1.0 + g
+ *   where the rule applies and f != 1.0:  p = f * d_m;  x_m = mean + p  for every m
+ * Everywhere else the point is not written and its recorded factor is 1.0: land, where every member holds
+ * the same value (sa = 0); a point where any member holds NaN or Inf (sa is NaN); f exactly 1.0.  So
+ *   alpha = 0 in RTPS and alpha = 1 in CONST leave every bit of every member as it was (RTPS: wherever r is
+ *   finite; t / sa overflows only where sa is below sb x 2^-1023, an analysis spread in the denormals under an
+ *   O(1) prior spread, and 0 x Inf is then NaN: the rule is applied as written);
+ *   a NaN in one member never spreads to the others;
+ *   a halo point and the neighbour block's interior point with the same global indices get the same
+ *   operations: if they and the saved spreads held the same bits before, they hold the same bits after.
+ * The factor applied, or 1.0, is stored at every point of the array in a second buffer the ensemble owns (one
+ * per field and block, as above).  One launch per field and block (values in registers up to 32 members in
+ * use; beyond, the members are read once per pass: sum, variance, update).  Afterwards each listed field of
+ * each member in use counts as UPLOADED, with exactly ocn_ens_transform's bookkeeping.
+ *
+ * Both asynchronous on the ensemble's stream.  ocn_ens_inflate_download: the whole array of block k of one of
+ * the two buffers of real(8) field field_id (PRIOR_SPREAD: the last ocn_ens_spread_save's; FACTOR: the last
+ * ocn_ens_inflate's), in ocn_ctx_download's layout; synchronous.
+ * OCN_ERR_ARG -- nothing launched, no member's tail, state or bookkeeping touched, the buffers as they were --
+ * for a null ensemble, list or host array, nfields < 1, an id that is real(4), absent or repeated, fewer than
+ * two members in use, a bad k, an unknown mode or `what`, an alpha that is not finite, RTPS with alpha < 0.
+ * OCN_ERR_STATE, likewise with nothing touched, for RTPS on a field with no saved spread or one saved over a
+ * different set of members, and for a download of a buffer that was never formed. */
+int ocn_ens_spread_save(ocn_ens *ens, const int32_t *field_ids, int32_t nfields, const uint8_t *use);
+enum { OCN_ENS_INFLATE_CONST = 0, OCN_ENS_INFLATE_RTPS = 1 };
+int ocn_ens_inflate(ocn_ens *ens, const int32_t *field_ids, int32_t nfields, const uint8_t *use,
+                    int32_t mode, double alpha);
+enum { OCN_ENS_INFLATE_PRIOR_SPREAD = 0, OCN_ENS_INFLATE_FACTOR = 1 };
+int ocn_ens_inflate_download(ocn_ens *ens, int32_t k, int32_t field_id, int32_t what, double *host);
+
 const char *ocn_last_error(void);
 int ocn_abi_version(void);
 /* Build id: a hash of the library's sources and compile flags (Makefile), e.g. to tie a

@@ -106,7 +106,8 @@ ENS_SYMBOLS = ["ocn_ens_plan", "ocn_ens_create", "ocn_ens_destroy", "ocn_ens_siz
                "ocn_ens_init_state", "ocn_ens_step", "ocn_ens_complete", "ocn_ens_synchronize", "ocn_ens_info",
                "ocn_ens_set_option", "ocn_ens_stats", "ocn_ens_stats_download", "ocn_ens_stats_output_r4",
                "ocn_ens_extrema", "ocn_ens_sample", "ocn_ens_transform", "ocn_ens_local_update",
-               "ocn_ens_assimilate", "ocn_ens_assimilate_info", "ocn_ens_assimilate_result"]
+               "ocn_ens_assimilate", "ocn_ens_assimilate_info", "ocn_ens_assimilate_result", "ocn_ens_spread_save",
+               "ocn_ens_inflate", "ocn_ens_inflate_download"]
 ALL_SYMBOLS = KERNEL_SYMBOLS + CTX_SYMBOLS + ENS_SYMBOLS
 ENS_MAX_MEMBERS = 256          # OCN_ENS_MAX_MEMBERS
 ENS_OPT_CAPACITY = 1
@@ -117,6 +118,9 @@ ENS_STATS = {"mean": 1, "var": 2, "spread": 4, "min": 8, "max": 16}
 # OCN_ENS_ASSIM_* (ocn_ens_assimilate_result)
 ENS_ASSIM_SPANS = 6            # (measurements: OCN_ENS_OPT_ASSIM_TIMING)
 ENS_ASSIM = {"hx": 0, "y": 1, "z": 2, "innovations": 3, "prior_spread": 4, "posterior_spread": 5}
+# OCN_ENS_INFLATE_* (ocn_ens_inflate's mode; ocn_ens_inflate_download's what)
+ENS_INFLATE_MODE = {"const": 0, "rtps": 1}
+ENS_INFLATE_WHAT = {"prior_spread": 0, "factor": 1}
 
 
 class OcnLibraryError(RuntimeError):
@@ -290,6 +294,9 @@ def lib() -> C.CDLL:
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.ocn_ens_assimilate_info.argtypes = [C.c_void_p, C.POINTER(OcnEnsAssimInfo)]
     L.ocn_ens_assimilate_result.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.ocn_ens_spread_save.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    L.ocn_ens_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double]
+    L.ocn_ens_inflate_download.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     _lib = L
     return L
 

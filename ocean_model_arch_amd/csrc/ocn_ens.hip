@@ -1,8 +1,9 @@
 // ocn_ens.hip -- ensembles (ocn_sw.h ocn_ens_*): many members of a small basin as contexts that share
 // one compute stream, their multi-step launches issued one per group (sw_kernels.hip k_march_multi_b),
 // the statistics over the members (ens_stats.hip), their sampling and recombination
-// (ens_transform.hip), their localized observation update (ens_local.hip) and the serial filter's
-// observation-space loop in front of it (ens_assim.hip).  The members' calls are planned by ocn_ctx.hip
+// (ens_transform.hip), their localized observation update (ens_local.hip), the serial filter's
+// observation-space loop in front of it (ens_assim.hip) and the inflation of their spread
+// (ens_inflate.hip).  The members' calls are planned by ocn_ctx.hip
 // step_impl; ocn_ens_plan.h holds the grouping policy.
 #include "ocn_ctx.h"
 #include "ocn_ens_plan.h"
@@ -69,6 +70,18 @@ struct ocn_ens {
     // OCN_ENS_OPT_ASSIM_TIMING: events around the observation-space launch and the update's launches
     bool as_timing = false;
     hipEvent_t ev_t[3] = {nullptr, nullptr, nullptr};
+    // ocn_ens_spread_save / ocn_ens_inflate: per field named so far, per local block, the saved spread
+    // (buf[0]) and the factor applied (buf[1]), based like the members' arrays (raw: the allocations, made at
+    // first use); formed[i]: buf[i] holds a successful call's result on every block; in_use: the members of
+    // the save, one byte each
+    struct Inflate {
+        int32_t field = 0;
+        std::vector<void *> raw[2];
+        std::vector<double *> buf[2];
+        bool formed[2] = {false, false};
+        std::vector<uint8_t> in_use;
+    };
+    std::vector<Inflate> inflate;
 };
 
 // ocn_ens_plan's policy: ocn_ens_plan.h (pure host code, also built stand-alone)
@@ -121,6 +134,10 @@ int ocn_ens_destroy(ocn_ens *e)
         if (t) (void)hipEventDestroy(t);
     if (e->d_as) (void)hipFree(e->d_as);
     if (e->h_as) (void)hipHostFree(e->h_as);
+    for (ocn_ens::Inflate &q : e->inflate)
+        for (std::vector<void *> &raw : q.raw)
+            for (void *r : raw)
+                if (r) (void)hipFree(r);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
     return OCN_OK;
@@ -610,6 +627,139 @@ int ocn_ens_transform(ocn_ens *e, const int32_t *field_ids, int32_t nfields, con
     for (ocn_ctx *c : in)
         for (int32_t f = 0; f < nfields; ++f) field_uploaded(c, field_ids[f]);
     return rc;
+}
+
+// ------------------------------------------------------------------ inflation (ens_inflate.hip)
+// What ocn_ens_spread_save and ocn_ens_inflate check alike: the list, the fields, the members in use (`in`,
+// and one byte per member in `mask`).  `who` opens the message.
+static int ens_inf_check(const ocn_ens *e, const std::string &who, const int32_t *field_ids, int32_t nfields,
+                         const uint8_t *use, std::vector<ocn_ctx *> &in, std::vector<uint8_t> &mask)
+{
+    if (!e || !field_ids) return set_error(OCN_ERR_ARG, who + ": null argument");
+    if (nfields < 1) return set_error(OCN_ERR_ARG, who + ": no field");
+    const ocn_ctx *c0 = e->m[0];
+    for (int32_t f = 0; f < nfields; ++f) {
+        if (!has_r8(c0, field_ids[f])) return set_error(OCN_ERR_ARG, who + ": not a real(8) field of the members");
+        for (int32_t q = 0; q < f; ++q)
+            if (field_ids[q] == field_ids[f]) return set_error(OCN_ERR_ARG, who + ": a field named twice");
+    }
+    in = ens_in_use(e, use);
+    if (in.size() < 2) return set_error(OCN_ERR_ARG, who + ": fewer than two members in use");
+    mask.assign(e->m.size(), 0);
+    for (size_t i = 0; i < e->m.size(); ++i) mask[i] = (!use || use[i]) ? 1 : 0;
+    return OCN_OK;
+}
+
+static ocn_ens::Inflate *ens_inf_find(ocn_ens *e, int32_t field)
+{
+    for (ocn_ens::Inflate &q : e->inflate)
+        if (q.field == field) return &q;
+    return nullptr;
+}
+
+// buffer `which` (0: saved spread, 1: factor) of every listed field on every block, made where it is missing
+static int ens_inf_buffers(ocn_ens *e, const int32_t *field_ids, int32_t nfields, int which)
+{
+    const ocn_ctx *c0 = e->m[0];
+    const size_t nblk = c0->blocks.size();
+    for (int32_t f = 0; f < nfields; ++f) {
+        if (!ens_inf_find(e, field_ids[f])) {
+            e->inflate.emplace_back();
+            ocn_ens::Inflate &q = e->inflate.back();
+            q.field = field_ids[f];
+            for (int i = 0; i < 2; ++i) { q.raw[i].assign(nblk, nullptr); q.buf[i].assign(nblk, nullptr); }
+        }
+        ocn_ens::Inflate *q = ens_inf_find(e, field_ids[f]);
+        for (size_t k = 0; k < nblk; ++k) {
+            if (q->raw[which][k]) continue;
+            const LBlock &b = c0->blocks[k];
+            const size_t lead = (size_t)((uintptr_t)b.ptr[field_slot(field_ids[f])] & 255u);   // (as ocn_ens_stats' buffers)
+            HIPCHK(hipMalloc(&q->raw[which][k], field_bytes(b) + 512));
+            q->buf[which][k] = (double *)((char *)q->raw[which][k] + 256 + lead);
+        }
+    }
+    return OCN_OK;
+}
+
+int ocn_ens_spread_save(ocn_ens *e, const int32_t *field_ids, int32_t nfields, const uint8_t *use)
+{
+    std::vector<ocn_ctx *> in;
+    std::vector<uint8_t> mask;
+    RC(ens_inf_check(e, "ens_spread_save", field_ids, nfields, use, in, mask));
+    HIPCHK(hipSetDevice(e->device));
+    // the buffers first (a failed allocation leaves the members and the earlier saves as they were)
+    RC(ens_inf_buffers(e, field_ids, nfields, 0));
+    for (ocn_ctx *c : in) RC(guarded(c, "ocn_ens_spread_save", [&] { return complete_open(c); }));
+    const ocn_ctx *c0 = e->m[0];
+    int rc = OCN_OK;
+    std::vector<const double *> src(in.size());
+    for (int32_t f = 0; f < nfields && !rc; ++f) {
+        ocn_ens::Inflate *q = ens_inf_find(e, field_ids[f]);
+        q->formed[0] = false;
+        for (size_t k = 0; k < c0->blocks.size() && !rc; ++k) {
+            for (size_t a = 0; a < in.size(); ++a) src[a] = (const double *)in[a]->blocks[k].ptr[field_slot(field_ids[f])];
+            double *const out[5] = {nullptr, nullptr, q->buf[0][k], nullptr, nullptr};   // (SPREAD alone)
+            rc = launch_ens_stats(&c0->blocks[k].g, src.data(), (int)src.size(), true, out, e->stream);
+        }
+        if (!rc) { q->formed[0] = true; q->in_use = mask; }
+    }
+    return rc;
+}
+
+int ocn_ens_inflate(ocn_ens *e, const int32_t *field_ids, int32_t nfields, const uint8_t *use, int32_t mode, double alpha)
+{
+    std::vector<ocn_ctx *> in;
+    std::vector<uint8_t> mask;
+    RC(ens_inf_check(e, "ens_inflate", field_ids, nfields, use, in, mask));
+    if (mode != OCN_ENS_INFLATE_CONST && mode != OCN_ENS_INFLATE_RTPS) return set_error(OCN_ERR_ARG, "ens_inflate: mode = OCN_ENS_INFLATE_*");
+    if (!std::isfinite(alpha)) return set_error(OCN_ERR_ARG, "ens_inflate: an alpha that is not finite");
+    if (mode == OCN_ENS_INFLATE_RTPS && alpha < 0.0) return set_error(OCN_ERR_ARG, "ens_inflate: RTPS with alpha < 0");
+    for (int32_t f = 0; f < nfields && mode == OCN_ENS_INFLATE_RTPS; ++f) {
+        const ocn_ens::Inflate *q = ens_inf_find(e, field_ids[f]);
+        if (!q || !q->formed[0]) return set_error(OCN_ERR_STATE, "ens_inflate: RTPS on a field with no saved spread (ocn_ens_spread_save)");
+        if (q->in_use != mask) return set_error(OCN_ERR_STATE, "ens_inflate: the spread was saved over a different set of members");
+    }
+    HIPCHK(hipSetDevice(e->device));
+    // the buffers first (a failed allocation leaves the members as they were)
+    RC(ens_inf_buffers(e, field_ids, nfields, 1));
+    for (ocn_ctx *c : in) RC(guarded(c, "ocn_ens_inflate", [&] { return complete_open(c); }));
+    const ocn_ctx *c0 = e->m[0];
+    const int n = (int)in.size();
+    int rc = OCN_OK;
+    std::vector<double *> mem((size_t)n);
+    for (int32_t f = 0; f < nfields && !rc; ++f) {
+        ocn_ens::Inflate *q = ens_inf_find(e, field_ids[f]);
+        q->formed[1] = false;
+        for (size_t k = 0; k < c0->blocks.size() && !rc; ++k) {
+            for (int a = 0; a < n; ++a) mem[(size_t)a] = (double *)in[(size_t)a]->blocks[k].ptr[field_slot(field_ids[f])];
+            rc = launch_ens_inflate(&c0->blocks[k].g, mem.data(), n, mode, alpha,
+                                    mode == OCN_ENS_INFLATE_RTPS ? q->buf[0][k] : nullptr, q->buf[1][k], e->stream);
+        }
+        if (!rc) q->formed[1] = true;
+    }
+    // what ocn_ctx_upload of each of these fields leaves behind (also after a failed launch: the arrays
+    // may have changed)
+    for (ocn_ctx *c : in)
+        for (int32_t f = 0; f < nfields; ++f) field_uploaded(c, field_ids[f]);
+    return rc;
+}
+
+int ocn_ens_inflate_download(ocn_ens *e, int32_t k, int32_t field_id, int32_t what, double *host)
+{
+    if (!e || !host) return set_error(OCN_ERR_ARG, "ens_inflate_download: null argument");
+    const ocn_ctx *c0 = e->m[0];
+    if (k < 0 || k >= (int32_t)c0->blocks.size()) return set_error(OCN_ERR_ARG, "ens_inflate_download: bad block index");
+    if (!has_r8(c0, field_id)) return set_error(OCN_ERR_ARG, "ens_inflate_download: not a real(8) field of the members");
+    if (what != OCN_ENS_INFLATE_PRIOR_SPREAD && what != OCN_ENS_INFLATE_FACTOR)
+        return set_error(OCN_ERR_ARG, "ens_inflate_download: what = OCN_ENS_INFLATE_PRIOR_SPREAD or OCN_ENS_INFLATE_FACTOR");
+    const ocn_ens::Inflate *q = ens_inf_find(e, field_id);
+    if (!q || !q->formed[what]) return set_error(OCN_ERR_STATE, "ens_inflate_download: that buffer of this field was never formed");
+    HIPCHK(hipSetDevice(e->device));
+    const ocn_block &g = c0->blocks[(size_t)k].g;
+    const size_t w = (size_t)(g.bnd_x2 - g.bnd_x1 + 1), rows = (size_t)(g.bnd_y2 - g.bnd_y1 + 1);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy2D(host, w * 8, q->buf[what][(size_t)k], (size_t)g.pitch * 8, w * 8, rows, hipMemcpyDeviceToHost));
+    return OCN_OK;
 }
 
 // ------------------------------------------------------------------ localized observation update (ens_local.hip)

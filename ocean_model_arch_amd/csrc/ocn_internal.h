@@ -286,6 +286,13 @@ struct EnsAsArgs {
     long row; int n, nobs, ntaper, reach;
 };
 int launch_ens_obs_space(const EnsAsArgs &a, hipStream_t s);
+// Covariance inflation (ens_inflate.hip; ocn_sw.h ocn_ens_inflate) of the n arrays mem[0 .. n) (one field of
+// one block geometry, the members in use in member order, n >= 2), in place, at every point of
+// A(bnd_x1:bnd_x2, bnd_y1:bnd_y2).  mode: OCN_ENS_INFLATE_*; d_spread: the saved spread (RTPS; else unused);
+// d_factor: the factor applied, or 1.0, at every point; both based like the members' arrays.  ONE launch;
+// beyond kEnsStatsReg members the members are read once per pass.
+int launch_ens_inflate(const ocn_block *b, double *const *mem, int n, int mode, double alpha, const double *d_spread,
+                       double *d_factor, hipStream_t s);
 // the known-constant precondition of launch_onepass over r (sw_kernels.hip FallbackCheck: the
 // fallback points and the forcing hold +0.0, h_r and mu are uniform): ORs 1 into *flag where it
 // does not hold; writes h_r and mu at (r.m0, r.n0) to kc[0], kc[1]

@@ -286,6 +286,53 @@ class OceanEnsemble:
                                          ptr(za), ptr(ta), len(ta)), "ocn_ens_local_update")
         return self
 
+    # ------------------------------------------------------------ inflation
+    def _ids(self, names):
+        names = (names,) if isinstance(names, str) else tuple(names)
+        return names, (C.c_int32 * len(names))(*[_lib.FIELD_ID[nm] for nm in names])
+
+    def spread_save(self, names=STATE, members=None):
+        """Keeps the per-point spread of the real(8) fields `names` over `members` (indices; None: all, at
+        least two) in buffers the ensemble owns, on every block (ocn_ens_spread_save: ocn_ens_stats' spread,
+        bit for bit): the prior spread that inflate(mode="rtps") relaxes to.  No member is written.
+        Asynchronous."""
+        names, ids = self._ids(names)
+        check(lib().ocn_ens_spread_save(self.ens, ids, len(names), self._use(members)), "ocn_ens_spread_save")
+        return self
+
+    def inflate(self, alpha: float, mode: str = "rtps", names=STATE, members=None):
+        """Covariance inflation of the real(8) fields `names` over `members` on the device, per point
+        (ocn_ens_inflate; the rule and its order of operations are in include/ocn_sw.h): the anomalies
+        about the ensemble mean are scaled by f.  mode="const": f = alpha everywhere the members differ.
+        mode="rtps" (relaxation to prior spread): f = 1 + alpha (sb - sa) / sa with sa the spread now and sb
+        the one spread_save() kept for the same members, so that the new spread is alpha sb + (1 - alpha) sa;
+        alpha >= 0.  A point where the members agree (land) or one holds NaN or Inf is not written.  The
+        inflated fields count as uploaded.  Asynchronous."""
+        if mode not in _lib.ENS_INFLATE_MODE:
+            raise ValueError(f"inflate: mode {mode!r}, not one of {sorted(_lib.ENS_INFLATE_MODE)}")
+        if isinstance(alpha, (str, bytes)) or np.ndim(alpha) != 0:
+            raise TypeError(f"inflate: alpha {alpha!r}, not a number")
+        a = float(alpha)
+        if not np.isfinite(a):
+            raise ValueError("inflate: an alpha that is not finite")
+        if mode == "rtps" and a < 0.0:
+            raise ValueError("inflate: rtps with alpha < 0")
+        names, ids = self._ids(names)
+        check(lib().ocn_ens_inflate(self.ens, ids, len(names), self._use(members), _lib.ENS_INFLATE_MODE[mode], a),
+              "ocn_ens_inflate")
+        return self
+
+    def inflation(self, name: str, what: str = "factor", k: int = 0) -> np.ndarray:
+        """What the last inflate() ("factor": the factor applied at every point of block k's array, 1.0 where
+        the point was not written) or the last spread_save() ("prior_spread") left for field `name`: a
+        float64 array of the block's array shape, Fortran order (ocn_ens_inflate_download).  Synchronous."""
+        if what not in _lib.ENS_INFLATE_WHAT:
+            raise ValueError(f"inflation: what {what!r}, not one of {sorted(_lib.ENS_INFLATE_WHAT)}")
+        a = np.zeros(self.members[0].blocks[k].shape, dtype=np.float64, order="F")
+        check(lib().ocn_ens_inflate_download(self.ens, k, _lib.FIELD_ID[name], _lib.ENS_INFLATE_WHAT[what],
+                                             a.ctypes.data_as(C.c_void_p)), "ocn_ens_inflate_download")
+        return a
+
     def block_of(self, i: int, j: int) -> int:
         """A local block that holds the global point (i, j): the one whose interior does, else the first
         whose array does (a point of the basin's outer rings)."""
@@ -298,7 +345,8 @@ class OceanEnsemble:
                 return b.k
         raise ValueError(f"point ({i}, {j}) lies in no local block's array")
 
-    def assimilate(self, name: str, obs_ij, values, variances, taper, names=STATE, members=None, device: bool = False) -> dict:
+    def assimilate(self, name: str, obs_ij, values, variances, taper, names=STATE, members=None, device: bool = False,
+                   rtps=None) -> dict:
         """A serial ensemble square-root filter (Whitaker & Hamill 2002) with localization: observations
         `values` of real(8) field `name` at the 1-based global points `obs_ij`, with error variances
         `variances`, assimilated one after another into the fields `names` of the members in use.
@@ -315,7 +363,21 @@ class OceanEnsemble:
         host path's).  The same four keys, read back afterwards (one wait), plus "nonfinite", the observations
         whose innovation or innovation variance was not finite.  More than 8192 observations are split into
         calls of 8192 only if `name` is among `names` (the next call's gather then reads what the previous
-        update left: the split composes); otherwise ValueError."""
+        update left: the split composes); otherwise ValueError.
+
+        rtps=alpha (a float; None: off): relaxation to prior spread around the analysis -- spread_save(names)
+        before it and inflate(alpha, "rtps", names) after it, on either path; with device=True the three calls
+        go out back to back with no wait in between.  The returned "hx" and "posterior_spread" describe the
+        analysis BEFORE the relaxation (sample() afterwards gives the relaxed values)."""
+        if rtps is not None:
+            alpha = float(rtps)
+            if not np.isfinite(alpha) or alpha < 0.0:
+                raise ValueError(f"assimilate: rtps = {rtps!r}, not a finite float >= 0")
+            self.spread_save(names, members=members)
+            info = (self._assimilate_device(name, obs_ij, values, variances, taper, names, members, defer=True) if device else
+                    self.assimilate(name, obs_ij, values, variances, taper, names=names, members=members))
+            self.inflate(alpha, "rtps", names, members=members)
+            return info() if device else info
         if device:
             return self._assimilate_device(name, obs_ij, values, variances, taper, names, members)
         ij = np.asarray(obs_ij, dtype=np.int64).reshape(-1, 2)
@@ -326,7 +388,10 @@ class OceanEnsemble:
             self.local_update(Y[k0:k1], Z[k0:k1], ij[k0:k1], np.asarray(taper, dtype=np.float64), names=names, members=members)
         return info
 
-    def _assimilate_device(self, name, obs_ij, values, variances, taper, names, members) -> dict:
+    def _assimilate_device(self, name, obs_ij, values, variances, taper, names, members, defer: bool = False):
+        """assimilate(device=True).  defer: return a function that reads the results back, so that the caller
+        may issue more work behind the analysis before the first wait (one call's results stay in the
+        ensemble's buffers until the next ocn_ens_assimilate; a split list is read back call by call as ever)."""
         n = self._count(members)
         ij = np.asarray(obs_ij)
         if ij.dtype.kind not in "iu":
@@ -351,26 +416,41 @@ class OceanEnsemble:
         L = lib()
         parts = {k: [] for k in ("hx", "innovations", "prior_spread", "posterior_spread")}
         nonfinite = 0
-        for k0 in range(0, nobs, ens_local_rule.MAX_OBS):
-            k1 = min(k0 + ens_local_rule.MAX_OBS, nobs)
-            i_, j_, v_, r_ = (np.ascontiguousarray(a[k0:k1]) for a in (io, jo, va, ra))
-            check(L.ocn_ens_assimilate(self.ens, _lib.FIELD_ID[name], ids, len(names), self._use(members), k1 - k0, ptr(i_),
-                                       ptr(j_), ptr(v_), ptr(r_), ptr(ta), len(ta)), "ocn_ens_assimilate")
+
+        def read_back(count):   # the last call's results (one wait each)
+            nonlocal nonfinite
             for key in parts:
-                a = np.zeros((k1 - k0, n) if key == "hx" else k1 - k0, dtype=np.float64)
+                a = np.zeros((count, n) if key == "hx" else count, dtype=np.float64)
                 check(L.ocn_ens_assimilate_result(self.ens, _lib.ENS_ASSIM[key], ptr(a)), "ocn_ens_assimilate_result")
                 parts[key].append(a)
             info = _lib.OcnEnsAssimInfo()
             check(L.ocn_ens_assimilate_info(self.ens, C.byref(info)), "ocn_ens_assimilate_info")
             nonfinite += int(info.nonfinite)
-        out = {k: np.concatenate(v) for k, v in parts.items()}
+
+        later = defer and nobs <= ens_local_rule.MAX_OBS
+        for k0 in range(0, nobs, ens_local_rule.MAX_OBS):
+            k1 = min(k0 + ens_local_rule.MAX_OBS, nobs)
+            i_, j_, v_, r_ = (np.ascontiguousarray(a[k0:k1]) for a in (io, jo, va, ra))
+            check(L.ocn_ens_assimilate(self.ens, _lib.FIELD_ID[name], ids, len(names), self._use(members), k1 - k0, ptr(i_),
+                                       ptr(j_), ptr(v_), ptr(r_), ptr(ta), len(ta)), "ocn_ens_assimilate")
+            if not later:
+                read_back(k1 - k0)
+        resampled = None
         # (a row of an earlier call that a later call's observations reach: its final values are the fields')
         if nobs > ens_local_rule.MAX_OBS:
-            out["hx"] = self.sample(name, [(self.block_of(int(i), int(j)), int(i), int(j)) for i, j in ij], members=members)
-            with np.errstate(all="ignore"):
-                out["posterior_spread"] = np.array([ens_local_rule._spread(r) for r in out["hx"]])
-        out["nonfinite"] = nonfinite
-        return out
+            resampled = self.sample(name, [(self.block_of(int(i), int(j)), int(i), int(j)) for i, j in ij], members=members)
+
+        def finish():
+            if later:
+                read_back(nobs)
+            out = {k: np.concatenate(v) for k, v in parts.items()}
+            if resampled is not None:
+                out["hx"] = resampled
+                with np.errstate(all="ignore"):
+                    out["posterior_spread"] = np.array([ens_local_rule._spread(r) for r in out["hx"]])
+            out["nonfinite"] = nonfinite
+            return out
+        return finish if defer else finish()
 
     def set_assim_timing(self, on: bool = True):
         """Measurements: assimilate(device=True) records events around its two stages (assimilate_spans)."""
