@@ -807,6 +807,63 @@ int ocn_ens_inflate(ocn_ens *ens, const int32_t *field_ids, int32_t nfields, con
 enum { OCN_ENS_INFLATE_PRIOR_SPREAD = 0, OCN_ENS_INFLATE_FACTOR = 1 };
 int ocn_ens_inflate_download(ocn_ens *ens, int32_t k, int32_t field_id, int32_t what, double *host);
 
+/* Correlated random perturbations of the members, drawn on the device: what makes the members of a freshly
+ * initialised ensemble differ, and the additive (model-error) inflation that goes with RTPS after each
+ * analysis.  ocn_ens_init_state, ocn_ens_perturb, ocn_ens_step, ocn_ens_spread_save, ocn_ens_assimilate,
+ * ocn_ens_inflate, ocn_ens_perturb, ocn_ens_step are asynchronous calls on the ensemble's stream with no host
+ * wait and no upload.  No counterpart in the reference.
+ *
+ * The members in use are u0 < u1 < ... < u(n-1) in member order (use as in ocn_ens_stats), n >= 1.  Each
+ * listed real(8) field field_ids[f], f < nfields, has a draw id draw[f] and a mask mask_ids[f]: a real(4)
+ * field id (OCN_LU, OCN_LCU, OCN_LLU, ...) or -1 for none.  The points are those of every local block's array
+ * A(bnd_x1:bnd_x2, bnd_y1:bnd_y2), with the library's 1-based global indices (i, j).  The random part is
+ * integer arithmetic, so its result does not depend on any order of evaluation, and a point's perturbation is
+ * a function of (seed, draw, member, i, j, reach, passes, n, centre, amplitude) alone: it does not depend on
+ * the block decomposition, and a halo point gets what the owning block's interior point gets.
+ *   White noise: (o0, o1, o2, o3) = Philox4x32-10 of the counter ((uint32_t)(int32_t)i, (uint32_t)(int32_t)j,
+ *     u_m, draw[f]) under the key (seed & 0xffffffff, seed >> 32) -- multipliers 0xD2511F53, 0xCD9E8D57, key
+ *     increments 0x9E3779B9, 0xBB67AE85, 10 rounds; u_m is the member's index in the ensemble, not its rank
+ *     among those in use.  S = the sum of the eight 16-bit halves of the four words; W_m(i, j) = S - 262140:
+ *     an integer of mean 0, |W| < 2^18.  W is defined on the whole index plane: indices outside the basin,
+ *     negative ones included, are taken as they are.
+ *   Correlation: Z_m = B_y^P B_x^P W_m with (B_x Z)(i, j) = the sum over d = -R .. R of Z(i + d, j), a box
+ *     sum, not a mean; R = reach, 0 .. OCN_ENS_PERTURB_MAX_REACH, P = passes, 0 .. OCN_ENS_PERTURB_MAX_PASSES;
+ *     R = 0 or P = 0 gives Z = W.  All values int64.  A point's Z depends on W within R P points of it.
+ *   Centring (centre != 0): T = the sum of Z_m over the members in use; D_m = n Z_m - T, so that the D_m of a
+ *     point sum to 0 exactly.  Without: D_m = Z_m.
+ *   Coefficient, on the host, once per call: q = the sum of k_t^2, k the 1-D box of width 2R+1 convolved with
+ *     itself P times (the delta for P = 0), an integer; den = kSigma * (double)q; with centring
+ *     den = den * (double)n; c = amplitude / den, with kSigma = 0x1.a20bd6fff1bdfp+15 = sqrt(2 (2^32 - 1) / 3),
+ *     the standard deviation of S.  `amplitude` is then the standard deviation of the perturbation; with
+ *     centring the expectation of the sample variance over the members (n-1 denominator) is amplitude^2.
+ *   Update, where the mask applies -- mask_ids[f] < 0, or member 0's mask field > 0.5f at the point -- each
+ *     line one IEEE double operation, no contraction:  d = (double)D_m;  p = c * d;  x_m = x_m + p.
+ *     Elsewhere the point is not stored to: land keeps its bits, -0.0 included.  A NaN or Inf stays what it
+ *     is and reaches no other member.
+ * Exactness: the call is refused unless n (2R+1)^(2P) 2^19 <= 2^53, which bounds |D| by 2^53 and makes
+ * (double)D exact: all 256 members up to R = 16 with P = 2, 13 members at R = 16 with P = 3.
+ * The bookkeeping is ocn_ens_transform's: the pending call tail of every member in use is formed first, a
+ * member not in use is not touched, afterwards each listed field of each member in use counts as UPLOADED and
+ * nothing else is re-formed.  Z goes through an int64 scratch the ensemble owns (per block, one array per
+ * member in the members' layout, allocated at first use, freed by ocn_ens_destroy).  Launches: the distinct
+ * draw ids are taken in the order of their first appearance; per draw id and block ONE noise launch forms Z
+ * for all members in use, then one launch per field of that draw id applies it -- fields that share a draw
+ * id get the same perturbation.  Asynchronous on the ensemble's stream; the caller's arrays may be reused
+ * when the call returns.
+ * ocn_ens_perturb_download: Z of the a-th member in use (a < n of that call) from the last noise launch on
+ * block k -- the last draw id of the last call -- the whole array in ocn_ctx_download's layout, int64;
+ * synchronous.
+ * OCN_ERR_ARG -- nothing launched, no member's tail, state or bookkeeping touched, the scratch as it was -- for
+ * a null argument (use apart), nfields < 1, an id that is real(4), absent or repeated, a mask id that is
+ * neither -1 nor a real(4) field, reach or passes out of range, an amplitude that is not finite and > 0,
+ * n < 1, centring with n < 2, the exactness bound; for the download a bad k or a, a null host array.
+ * OCN_ERR_STATE for a download before the first successful call. */
+enum { OCN_ENS_PERTURB_MAX_REACH = 16, OCN_ENS_PERTURB_MAX_PASSES = 3 };
+int ocn_ens_perturb(ocn_ens *ens, const int32_t *field_ids, const int32_t *mask_ids, const uint32_t *draw,
+                    int32_t nfields, const uint8_t *use, uint64_t seed, int32_t reach, int32_t passes,
+                    int32_t centre, double amplitude);
+int ocn_ens_perturb_download(ocn_ens *ens, int32_t k, int32_t a, int64_t *host);
+
 const char *ocn_last_error(void);
 int ocn_abi_version(void);
 /* Build id: a hash of the library's sources and compile flags (Makefile), e.g. to tie a

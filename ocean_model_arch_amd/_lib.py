@@ -107,7 +107,7 @@ ENS_SYMBOLS = ["ocn_ens_plan", "ocn_ens_create", "ocn_ens_destroy", "ocn_ens_siz
                "ocn_ens_set_option", "ocn_ens_stats", "ocn_ens_stats_download", "ocn_ens_stats_output_r4",
                "ocn_ens_extrema", "ocn_ens_sample", "ocn_ens_transform", "ocn_ens_local_update",
                "ocn_ens_assimilate", "ocn_ens_assimilate_info", "ocn_ens_assimilate_result", "ocn_ens_spread_save",
-               "ocn_ens_inflate", "ocn_ens_inflate_download"]
+               "ocn_ens_inflate", "ocn_ens_inflate_download", "ocn_ens_perturb", "ocn_ens_perturb_download"]
 ALL_SYMBOLS = KERNEL_SYMBOLS + CTX_SYMBOLS + ENS_SYMBOLS
 ENS_MAX_MEMBERS = 256          # OCN_ENS_MAX_MEMBERS
 ENS_OPT_CAPACITY = 1
@@ -297,6 +297,9 @@ def lib() -> C.CDLL:
     L.ocn_ens_spread_save.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.ocn_ens_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double]
     L.ocn_ens_inflate_download.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    L.ocn_ens_perturb.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_int32,
+                                  C.c_int32, C.c_int32, C.c_double]
+    L.ocn_ens_perturb_download.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     _lib = L
     return L
 

@@ -2,8 +2,8 @@
 // one compute stream, their multi-step launches issued one per group (sw_kernels.hip k_march_multi_b),
 // the statistics over the members (ens_stats.hip), their sampling and recombination
 // (ens_transform.hip), their localized observation update (ens_local.hip), the serial filter's
-// observation-space loop in front of it (ens_assim.hip) and the inflation of their spread
-// (ens_inflate.hip).  The members' calls are planned by ocn_ctx.hip
+// observation-space loop in front of it (ens_assim.hip), the inflation of their spread
+// (ens_inflate.hip) and their random perturbation (ens_perturb.hip).  The members' calls are planned by ocn_ctx.hip
 // step_impl; ocn_ens_plan.h holds the grouping policy.
 #include "ocn_ctx.h"
 #include "ocn_ens_plan.h"
@@ -82,6 +82,10 @@ struct ocn_ens {
         std::vector<uint8_t> in_use;
     };
     std::vector<Inflate> inflate;
+    // ocn_ens_perturb: per local block the int64 scratch of Z, one array per member of the ensemble stride[k]
+    // elements apart, based like the members' arrays (raw: the allocations, made at first use); n[k]: the
+    // members in use of the last noise launch on block k (0: none yet)
+    struct Perturb { std::vector<void *> raw; std::vector<long long *> z; std::vector<long> stride; std::vector<int> n; } perturb;
 };
 
 // ocn_ens_plan's policy: ocn_ens_plan.h (pure host code, also built stand-alone)
@@ -138,6 +142,8 @@ int ocn_ens_destroy(ocn_ens *e)
         for (std::vector<void *> &raw : q.raw)
             for (void *r : raw)
                 if (r) (void)hipFree(r);
+    for (void *r : e->perturb.raw)
+        if (r) (void)hipFree(r);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
     return OCN_OK;
@@ -759,6 +765,110 @@ int ocn_ens_inflate_download(ocn_ens *e, int32_t k, int32_t field_id, int32_t wh
     const size_t w = (size_t)(g.bnd_x2 - g.bnd_x1 + 1), rows = (size_t)(g.bnd_y2 - g.bnd_y1 + 1);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy2D(host, w * 8, q->buf[what][(size_t)k], (size_t)g.pitch * 8, w * 8, rows, hipMemcpyDeviceToHost));
+    return OCN_OK;
+}
+
+// ------------------------------------------------------------------ correlated perturbations (ens_perturb.hip)
+// the sum of the squares of the box of width 2R+1 convolved with itself P times (the delta for P = 0)
+static uint64_t ens_perturb_q(int reach, int passes)
+{
+    std::vector<uint64_t> k{1};
+    for (int p = 0; p < passes; ++p) {
+        std::vector<uint64_t> next(k.size() + 2 * (size_t)reach, 0);
+        for (size_t t = 0; t < k.size(); ++t)
+            for (int d = 0; d <= 2 * reach; ++d) next[t + (size_t)d] += k[t];
+        k.swap(next);
+    }
+    uint64_t q = 0;
+    for (uint64_t v : k) q += v * v;
+    return q;
+}
+
+int ocn_ens_perturb(ocn_ens *e, const int32_t *field_ids, const int32_t *mask_ids, const uint32_t *draw, int32_t nfields,
+                    const uint8_t *use, uint64_t seed, int32_t reach, int32_t passes, int32_t centre, double amplitude)
+{
+    if (!e || !field_ids || !mask_ids || !draw) return set_error(OCN_ERR_ARG, "ens_perturb: null argument");
+    if (nfields < 1) return set_error(OCN_ERR_ARG, "ens_perturb: no field");
+    const ocn_ctx *c0 = e->m[0];
+    for (int32_t f = 0; f < nfields; ++f) {
+        if (!has_r8(c0, field_ids[f])) return set_error(OCN_ERR_ARG, "ens_perturb: not a real(8) field of the members");
+        for (int32_t q = 0; q < f; ++q)
+            if (field_ids[q] == field_ids[f]) return set_error(OCN_ERR_ARG, "ens_perturb: a field named twice");
+        if (mask_ids[f] != -1 && !is_r4(mask_ids[f])) return set_error(OCN_ERR_ARG, "ens_perturb: a mask that is neither -1 nor a real(4) field");
+    }
+    if (reach < 0 || reach > OCN_ENS_PERTURB_MAX_REACH) return set_error(OCN_ERR_ARG, "ens_perturb: reach outside 0..16");
+    if (passes < 0 || passes > OCN_ENS_PERTURB_MAX_PASSES) return set_error(OCN_ERR_ARG, "ens_perturb: passes outside 0..3");
+    if (!std::isfinite(amplitude) || !(amplitude > 0.0)) return set_error(OCN_ERR_ARG, "ens_perturb: an amplitude that is not finite and > 0");
+    const std::vector<ocn_ctx *> in = ens_in_use(e, use);
+    const int n = (int)in.size();
+    if (n < 1) return set_error(OCN_ERR_ARG, "ens_perturb: no member in use");
+    if (centre && n < 2) return set_error(OCN_ERR_ARG, "ens_perturb: centring with fewer than two members in use");
+    uint64_t bound = (uint64_t)n << 19;   // n (2R+1)^(2P) 2^19: below 2^58 for every n, R and P allowed
+    for (int p = 0; p < 2 * passes; ++p) bound *= (uint64_t)(2 * reach + 1);
+    if (bound > (1ull << 53)) return set_error(OCN_ERR_ARG, "ens_perturb: n (2 reach + 1)^(2 passes) 2^19 > 2^53: not exact in double");
+    HIPCHK(hipSetDevice(e->device));
+    // the scratch first (a failed allocation leaves the members as they were)
+    const size_t M = e->m.size(), nblk = c0->blocks.size();
+    ocn_ens::Perturb &pt = e->perturb;
+    if (pt.raw.empty()) { pt.raw.assign(nblk, nullptr); pt.z.assign(nblk, nullptr); pt.stride.assign(nblk, 0); pt.n.assign(nblk, 0); }
+    for (size_t k = 0; k < nblk; ++k) {
+        if (pt.raw[k]) continue;
+        const LBlock &b = c0->blocks[k];
+        const size_t lead = (size_t)((uintptr_t)b.ptr[field_slot(OCN_SSH)] & 255u);   // (as ocn_ens_stats' buffers)
+        const size_t stride = (field_bytes(b) + 255) / 256 * 256;                     // (every member's array based alike)
+        HIPCHK(hipMalloc(&pt.raw[k], stride * M + 512));
+        pt.z[k] = (long long *)((char *)pt.raw[k] + 256 + lead);
+        pt.stride[k] = (long)(stride / 8);
+    }
+    for (ocn_ctx *c : in) RC(guarded(c, "ocn_ens_perturb", [&] { return complete_open(c); }));
+    std::vector<uint8_t> members;   // the members in use: their indices in the ensemble
+    for (size_t i = 0; i < M; ++i)
+        if (!use || use[i]) members.push_back((uint8_t)i);
+    const double q = (double)ens_perturb_q(reach, passes);
+    double den = 0x1.a20bd6fff1bdfp+15 * q;   // kSigma = sqrt(2 (2^32 - 1) / 3)
+    if (centre) den = den * (double)n;
+    const double coef = amplitude / den;
+    int rc = OCN_OK;
+    std::vector<double *> mem((size_t)n);
+    for (int32_t f0 = 0; f0 < nfields && !rc; ++f0) {
+        bool first = true;   // field f0 opens its draw id
+        for (int32_t q0 = 0; q0 < f0; ++q0) first = first && draw[q0] != draw[f0];
+        if (!first) continue;
+        for (size_t k = 0; k < nblk && !rc; ++k) {
+            const LBlock &b0 = c0->blocks[k];
+            const int lead = (int)(((uintptr_t)pt.z[k] & 255u) / 8u);
+            pt.n[k] = 0;
+            rc = launch_ens_noise(&b0.g, members.data(), n, seed, draw[f0], reach, passes, pt.z[k], pt.stride[k], lead, e->stream);
+            if (!rc) pt.n[k] = n;
+            for (int32_t f = f0; f < nfields && !rc; ++f) {
+                if (draw[f] != draw[f0]) continue;
+                for (int a = 0; a < n; ++a) mem[(size_t)a] = (double *)in[(size_t)a]->blocks[k].ptr[field_slot(field_ids[f])];
+                rc = launch_ens_perturb_apply(&b0.g, mem.data(), n, pt.z[k], pt.stride[k], centre != 0, coef,
+                                              mask_ids[f] < 0 ? nullptr : b0.f<float>(mask_ids[f]), e->stream);
+            }
+        }
+    }
+    // what ocn_ctx_upload of each of these fields leaves behind (also after a failed launch: the arrays
+    // may have changed)
+    for (ocn_ctx *c : in)
+        for (int32_t f = 0; f < nfields; ++f) field_uploaded(c, field_ids[f]);
+    return rc;
+}
+
+int ocn_ens_perturb_download(ocn_ens *e, int32_t k, int32_t a, int64_t *host)
+{
+    if (!e || !host) return set_error(OCN_ERR_ARG, "ens_perturb_download: null argument");
+    const ocn_ctx *c0 = e->m[0];
+    if (k < 0 || k >= (int32_t)c0->blocks.size()) return set_error(OCN_ERR_ARG, "ens_perturb_download: bad block index");
+    const ocn_ens::Perturb &pt = e->perturb;
+    if (pt.n.empty() || pt.n[(size_t)k] < 1) return set_error(OCN_ERR_STATE, "ens_perturb_download: no ocn_ens_perturb on this block yet");
+    if (a < 0 || a >= pt.n[(size_t)k]) return set_error(OCN_ERR_ARG, "ens_perturb_download: not a member in use of the last call");
+    HIPCHK(hipSetDevice(e->device));
+    const ocn_block &g = c0->blocks[(size_t)k].g;
+    const size_t w = (size_t)(g.bnd_x2 - g.bnd_x1 + 1), rows = (size_t)(g.bnd_y2 - g.bnd_y1 + 1);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy2D(host, w * 8, pt.z[(size_t)k] + (size_t)a * (size_t)pt.stride[(size_t)k], (size_t)g.pitch * 8, w * 8, rows,
+                       hipMemcpyDeviceToHost));
     return OCN_OK;
 }
 

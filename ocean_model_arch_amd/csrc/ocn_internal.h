@@ -293,6 +293,16 @@ int launch_ens_obs_space(const EnsAsArgs &a, hipStream_t s);
 // beyond kEnsStatsReg members the members are read once per pass.
 int launch_ens_inflate(const ocn_block *b, double *const *mem, int n, int mode, double alpha, const double *d_spread,
                        double *d_factor, hipStream_t s);
+// Correlated perturbations (ens_perturb.hip; ocn_sw.h ocn_ens_perturb).  launch_ens_noise: Z of one draw id
+// over A(bnd_x1:bnd_x2, bnd_y1:bnd_y2) of one block for the n members in use (members[a]: the a-th one's index
+// in the ensemble) into d_z, member a's array at d_z + a * zstride, based like the members' arrays (lead: the
+// lane of A(bnd_x1, :) within its 256-B line).  launch_ens_perturb_apply: the n arrays mem[0 .. n) (one field,
+// member order) take c * D from that scratch, in place, where d_mask (real(4), the block's pitch; nullptr:
+// everywhere) is > 0.5f.  ONE launch each.
+int launch_ens_noise(const ocn_block *b, const uint8_t *members, int n, uint64_t seed, uint32_t draw, int reach, int passes,
+                     long long *d_z, long zstride, int lead, hipStream_t s);
+int launch_ens_perturb_apply(const ocn_block *b, double *const *mem, int n, const long long *d_z, long zstride, bool centre,
+                             double c, const float *d_mask, hipStream_t s);
 // the known-constant precondition of launch_onepass over r (sw_kernels.hip FallbackCheck: the
 // fallback points and the forcing hold +0.0, h_r and mu are uniform): ORs 1 into *flag where it
 // does not hold; writes h_r and mu at (r.m0, r.n0) to kc[0], kc[1]

@@ -8,10 +8,11 @@ with a barrier of its own inside it.  The reference runs one model per process a
 from __future__ import annotations
 
 import ctypes as C
+import operator
 
 import numpy as np
 
-from . import _lib, ens_local_rule
+from . import _lib, ens_local_rule, ens_perturb_rule
 from ._lib import check, lib
 from .config import BasinConfig, ParallelConfig, SWConfig
 from .model import BlockInfo, OceanModel
@@ -20,6 +21,20 @@ from .output import UNDEF
 
 # the prognostic state of the shallow-water step: what OceanEnsemble.transform recombines by default
 STATE = ("ssh", "sshp", "ubrtr", "ubrtrp", "vbrtr", "vbrtrp")
+# the same in OceanEnsemble.perturb's groups: both leapfrog levels of a variable share one draw
+STATE_GROUPS = (("ssh", "sshp"), ("ubrtr", "ubrtrp"), ("vbrtr", "vbrtrp"))
+# the real(4) mask under which the step itself stores a field, by the field name's prefix (sw_stencils.h:
+# SwNextStep stores ssh / sshp under lu, ubrtr / ubrtrp under lcu, vbrtr / vbrtrp under lcv; HhUpdate and HhShift
+# store hhu under llu, hhv under llv and hhh under luh; hhq is h_r + ssh, an h-point field as ssh is)
+_MASKS = (("ssh", "lu"), ("ubrtr", "lcu"), ("vbrtr", "lcv"), ("hhq", "lu"), ("hhu", "llu"), ("hhv", "llv"), ("hhh", "luh"))
+
+
+def default_mask(name: str):
+    """OceanEnsemble.perturb's mask of real(8) field `name` when the caller names none (None: no mask)."""
+    for prefix, mask in _MASKS:
+        if name.startswith(prefix):
+            return mask
+    return None
 
 
 class _Member(OceanModel):
@@ -332,6 +347,62 @@ class OceanEnsemble:
         check(lib().ocn_ens_inflate_download(self.ens, k, _lib.FIELD_ID[name], _lib.ENS_INFLATE_WHAT[what],
                                              a.ctypes.data_as(C.c_void_p)), "ocn_ens_inflate_download")
         return a
+
+    # ------------------------------------------------------------ correlated perturbations
+    def perturb(self, amplitude: float, reach: int = 4, passes: int = 2, names=STATE_GROUPS, masks=None, seed: int = 0,
+                draw: int = 0, centre: bool = True, members=None):
+        """Adds spatially correlated random perturbations of standard deviation `amplitude` to real(8) fields
+        of `members` (indices; None: all) on the device, on every block (ocn_ens_perturb; the rule is in
+        include/ocn_sw.h, its numpy restatement in ens_perturb_rule.py): white integer noise from Philox4x32-10
+        keyed by `seed` (0 .. 2^64-1) and counted by the global point, the member and a draw id, smoothed by
+        `passes` (0..3) box sums of half-width `reach` (0..16) each way, centred over the members in use
+        (centre=True: the perturbations of a point sum to zero) and added where the field's mask is set.  The
+        result is bit for bit reproducible and independent of the block decomposition.
+        `names`: a sequence whose entries are a field name or a tuple of names that share one draw; entry g
+        gets draw id draw + g.  The default gives both leapfrog levels of a variable the same perturbation.
+        `masks`: {field name: real(4) field name, or None for no mask}; a field it does not list, and every
+        field with masks=None, gets default_mask(name), the mask under which the step itself stores the field.
+        The perturbed fields count as uploaded.  Asynchronous."""
+        if isinstance(amplitude, (str, bytes)) or np.ndim(amplitude) != 0:
+            raise TypeError(f"perturb: amplitude {amplitude!r}, not a number")
+        amp = float(amplitude)
+        if not np.isfinite(amp) or not amp > 0.0:
+            raise ValueError(f"perturb: amplitude {amplitude!r}, not finite and > 0")
+        reach, passes, seed, draw = (operator.index(v) for v in (reach, passes, seed, draw))
+        if not 0 <= reach <= ens_perturb_rule.MAX_REACH or not 0 <= passes <= ens_perturb_rule.MAX_PASSES:
+            raise ValueError(f"perturb: reach {reach} outside 0..{ens_perturb_rule.MAX_REACH} or passes {passes} outside "
+                             f"0..{ens_perturb_rule.MAX_PASSES}")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"perturb: seed {seed} outside 0..2^64-1")
+        groups = [(g,) if isinstance(g, str) else tuple(g) for g in ((names,) if isinstance(names, str) else names)]
+        flat = [nm for g in groups for nm in g]
+        if not flat or any(not g for g in groups):
+            raise ValueError("perturb: no field, or an empty group")
+        if not (0 <= draw and draw + len(groups) - 1 < 1 << 32):
+            raise ValueError(f"perturb: draw ids {draw}..{draw + len(groups) - 1} outside 0..2^32-1")
+        if masks is not None and set(masks) - set(flat):
+            raise ValueError(f"perturb: masks for {sorted(set(masks) - set(flat))}, which are not among the fields")
+        n = self._count(members)
+        if n < 1 or (centre and n < 2):
+            raise ValueError(f"perturb: {n} members in use" + (" with centring" if centre else ""))
+        if not ens_perturb_rule.exact(n, reach, passes):
+            raise ValueError(f"perturb: {n} members with reach {reach} and passes {passes}: n (2 reach + 1)^(2 passes) 2^19 "
+                             f"> 2^53, not exact in double")
+        mask_of = lambda nm: masks[nm] if masks is not None and nm in masks else default_mask(nm)   # noqa: E731
+        mids = [-1 if mask_of(nm) is None else _lib.FIELD_ID[mask_of(nm)] for nm in flat]
+        ids = (C.c_int32 * len(flat))(*[_lib.FIELD_ID[nm] for nm in flat])
+        draws = (C.c_uint32 * len(flat))(*[draw + g for g, grp in enumerate(groups) for _ in grp])
+        check(lib().ocn_ens_perturb(self.ens, ids, (C.c_int32 * len(flat))(*mids), draws, len(flat), self._use(members), seed,
+                                    reach, passes, int(bool(centre)), amp), "ocn_ens_perturb")
+        return self
+
+    def perturbation(self, a: int, k: int = 0) -> np.ndarray:
+        """Z, the smoothed integer noise before centring and scaling, of the a-th member in use from the last
+        noise launch on block k (the last draw id of the last perturb()): an int64 array of the block's array
+        shape, Fortran order (ocn_ens_perturb_download).  Synchronous."""
+        z = np.zeros(self.members[0].blocks[k].shape, dtype=np.int64, order="F")
+        check(lib().ocn_ens_perturb_download(self.ens, k, int(a), z.ctypes.data_as(C.c_void_p)), "ocn_ens_perturb_download")
+        return z
 
     def block_of(self, i: int, j: int) -> int:
         """A local block that holds the global point (i, j): the one whose interior does, else the first
