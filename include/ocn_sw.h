@@ -752,6 +752,54 @@ enum { OCN_ENS_ASSIM_HX = 0, OCN_ENS_ASSIM_Y = 1, OCN_ENS_ASSIM_Z = 2, OCN_ENS_A
        OCN_ENS_ASSIM_PRIOR_SPREAD = 4, OCN_ENS_ASSIM_POSTERIOR_SPREAD = 5, OCN_ENS_ASSIM_SPANS = 6 };
 int ocn_ens_assimilate_result(ocn_ens *ens, int32_t what, double *host);
 
+/* Observations that are not one field's value at one grid point -- an altimeter track between h points, a
+ * radial velocity cos(theta) u + sin(theta) v of interpolated values, a footprint average: a SPARSE LINEAR
+ * observation operator H, a CSR table over nobs observations.  No counterpart in the reference.
+ *   start[0 .. nobs], start[0] = 0: observation j owns the terms start[j] .. start[j+1]-1, between 1 and
+ *   OCN_ENS_OBS_MAX_TERMS of them.  Term t is (tfield[t], ti[t], tj[t], tw[t]): a real(8) field id, the
+ *   library's 1-based global indices, a weight that is finite and not +-0.0.  At most OCN_ENS_OBS_MAX_FIELDS
+ *   distinct fields among the terms of one call.  Each term's point is read in the local block whose
+ *   interior holds it, else the first whose array A(bnd_x1:bnd_x2, bnd_y1:bnd_y2) does (halo and land
+ *   included); the terms of one observation may lie in different blocks.
+ *   H_j(u) = s, where  s = x_0 * w_0;  then for the later terms in the caller's order  p = x_t * w_t;  s = s + p
+ *   (x_t member u's value at term t) in IEEE double arithmetic without contraction, every product rounded
+ *   before the sum: bitwise reproducible (ens_obs_rule.apply restates it in numpy), and a one-term row of
+ *   weight 1.0 is a bit-for-bit copy.
+ *
+ * ocn_ens_sample_h: host[j * n + m] = H_j(member u_m), the members in use in member order.  Everything else
+ * is ocn_ens_sample's: the pending call tail of every member in use is formed first, ONE launch, the
+ * nobs x n doubles come down through pinned memory with one wait, synchronous, no bookkeeping touched;
+ * OCN_ERR_ARG -- nothing launched, nothing written to host -- for a null argument, nobs < 1 or > 65536, no
+ * member in use and every table error listed below.
+ *
+ * ocn_ens_assimilate_h: ocn_ens_assimilate with the prologue hx[j][m] = H_j(member u_m) (there is no
+ * obs_field).  (io[j], jo[j]) is now the observation's ANCHOR: its localization centre in index space,
+ * anywhere within the basin, not tied to its terms (the nearest point of the field that matters most, say;
+ * the true position is then at most 0.71 cells away).  The loop and the epilogue are ocn_ens_assimilate's:
+ * row j takes observation k with rho = taper[(io[j]-io[k])^2 + (jo[j]-jo[k])^2], and the fields field_ids
+ * take the nobs observations with the rows Y, Z at the anchors, with ocn_ens_local_update's bits and
+ * bookkeeping.  The rows are an AUGMENTED STATE: nobs scalars carried through the loop by the update's rule
+ * at their anchors.  With a taper that is 1.0 everywhere they remain H of the updated fields (to rounding:
+ * the rule is linear in the state); with any other taper H of the updated fields weighs each term's point
+ * by ITS distance from observation k, the row by its anchor's, and HX is NOT what ocn_ens_sample_h gives
+ * afterwards.  A list of more than 8192 observations therefore does not compose bit for bit out of two
+ * calls, and nobs > 8192 is refused as before.  Launches: one for the prologue, the loop and the epilogue
+ * together, then the update's.  Asynchronous on the ensemble's stream; the caller's arrays may be reused when
+ * the call returns.  ocn_ens_assimilate_info and ocn_ens_assimilate_result serve the last successful call of
+ * either entry.  OCN_ERR_ARG -- nothing launched, no member's tail, state or bookkeeping touched, the earlier
+ * results kept -- for every case ocn_ens_assimilate refuses (its obs_field apart, the anchors in the
+ * observations' place) and for: start[0] != 0, an observation with 0 or more than OCN_ENS_OBS_MAX_TERMS
+ * terms, a weight that is zero or not finite, a term's field that is real(4) or absent, more than
+ * OCN_ENS_OBS_MAX_FIELDS distinct fields, a term in no local block's array. */
+#define OCN_ENS_OBS_MAX_TERMS 16
+#define OCN_ENS_OBS_MAX_FIELDS 4
+int ocn_ens_sample_h(ocn_ens *ens, const uint8_t *use, int32_t nobs, const int32_t *start, const int32_t *tfield,
+                     const int32_t *ti, const int32_t *tj, const double *tw, double *host);
+int ocn_ens_assimilate_h(ocn_ens *ens, const int32_t *field_ids, int32_t nfields, const uint8_t *use, int32_t nobs,
+                         const int32_t *io, const int32_t *jo, const int32_t *start, const int32_t *tfield,
+                         const int32_t *ti, const int32_t *tj, const double *tw, const double *value,
+                         const double *variance, const double *taper, int32_t ntaper);
+
 /* Covariance inflation on the device: what keeps a square-root filter's spread from collapsing over the
  * cycles.  ocn_ens_transform can apply ONE factor to every point (n^2 work per point, and it inflates the
  * points no observation reached as well); relaxation to prior spread (RTPS, Whitaker & Hamill 2012) needs a

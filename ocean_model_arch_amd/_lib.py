@@ -106,10 +106,13 @@ ENS_SYMBOLS = ["ocn_ens_plan", "ocn_ens_create", "ocn_ens_destroy", "ocn_ens_siz
                "ocn_ens_init_state", "ocn_ens_step", "ocn_ens_complete", "ocn_ens_synchronize", "ocn_ens_info",
                "ocn_ens_set_option", "ocn_ens_stats", "ocn_ens_stats_download", "ocn_ens_stats_output_r4",
                "ocn_ens_extrema", "ocn_ens_sample", "ocn_ens_transform", "ocn_ens_local_update",
-               "ocn_ens_assimilate", "ocn_ens_assimilate_info", "ocn_ens_assimilate_result", "ocn_ens_spread_save",
+               "ocn_ens_assimilate", "ocn_ens_assimilate_info", "ocn_ens_assimilate_result", "ocn_ens_sample_h",
+               "ocn_ens_assimilate_h", "ocn_ens_spread_save",
                "ocn_ens_inflate", "ocn_ens_inflate_download", "ocn_ens_perturb", "ocn_ens_perturb_download"]
 ALL_SYMBOLS = KERNEL_SYMBOLS + CTX_SYMBOLS + ENS_SYMBOLS
 ENS_MAX_MEMBERS = 256          # OCN_ENS_MAX_MEMBERS
+ENS_OBS_MAX_TERMS = 16         # OCN_ENS_OBS_MAX_TERMS
+ENS_OBS_MAX_FIELDS = 4         # OCN_ENS_OBS_MAX_FIELDS
 ENS_OPT_CAPACITY = 1
 ENS_OPT_MAX_GROUP = 2
 ENS_OPT_ASSIM_TIMING = 3
@@ -292,6 +295,11 @@ def lib() -> C.CDLL:
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.ocn_ens_assimilate.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    L.ocn_ens_sample_h.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]
+    L.ocn_ens_assimilate_h.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int32]
     L.ocn_ens_assimilate_info.argtypes = [C.c_void_p, C.POINTER(OcnEnsAssimInfo)]
     L.ocn_ens_assimilate_result.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.ocn_ens_spread_save.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]

@@ -34,6 +34,11 @@
 // reads Y and Z in; a thread streams its row through registers kAsChunk members at a time behind constant
 // indices, so nothing goes to scratch, and there is ONE path for every n and nobs.
 // No atomics, no grid barrier, no inline assembly; plain stores.
+//
+// A sparse linear observation operator (ocn_sw.h ocn_ens_sample_h, ocn_ens_assimilate_h): obs_apply forms
+// H_j(member u_m) from a CSR table of terms; k_ens_sample_h brings it down, one thread per (observation,
+// member); k_ens_obs_space_h is k_ens_obs_space with hx[j][m] = H_j(member u_m) in the prologue -- the two
+// are instances of one body, as_stage, and still ONE launch of ONE workgroup each.
 #include "ocn_internal.h"
 
 namespace ocn {
@@ -58,9 +63,44 @@ constexpr int kAsChunk = 8;
 static_assert(kAsChunk == kLuRow, "a chunk's loads may run into the row's padding, never beyond it");
 static_assert(OCN_ENS_MAX_MEMBERS % kAsChunk == 0, "... nor beyond the LDS copy of row k");
 
-__global__ __launch_bounds__(kAsThreads) void k_ens_obs_space(const EnsAsArgs a)
+// ------------------------------------------------------------------ a sparse linear observation operator
+// H_j(member u_m): s = x_0 * w_0, then p = x_t * w_t; s = s + p in the caller's term order, every product
+// rounded before the sum (-ffp-contract=off).  ONE function for the sample and for the filter's prologue:
+// the same bits from both.  A group's loads go out together (a term's value hangs on two dependent loads:
+// the table's pointer, then the element), the ordered multiply-adds follow behind constant indices: no
+// scratch.  The loop runs to the row's term count, never over padding (s + 0 turns a -0.0 sum into +0.0).
+constexpr int kObsGroup = 4;
+static_assert(OCN_ENS_OBS_MAX_TERMS % kObsGroup == 0, "whole groups up to the limit");
+
+__device__ __forceinline__ double obs_apply(const EnsObsOp &h, int j, int m)
 {
-    __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
+    const int t0 = h.start[j], t1 = h.start[j + 1];
+    double s = 0.0;
+    for (int t = t0; t < t1; t += kObsGroup) {
+        double x[kObsGroup], w[kObsGroup];
+#pragma unroll
+        for (int e = 0; e < kObsGroup; ++e)
+            if (t + e < t1) {
+                const EnsObsTerm q = h.term[t + e];
+                x[e] = h.tab[q.slot + m][q.off];
+                w[e] = q.w;
+            }
+#pragma unroll
+        for (int e = 0; e < kObsGroup; ++e)
+            if (t + e < t1) {
+                const double p = x[e] * w[e];
+                s = t + e == t0 ? p : s + p;
+            }
+    }
+    return s;
+}
+
+// ------------------------------------------------------------------ the observation-space stage
+// The whole stage, ONE text for k_ens_obs_space (kOp false: hx gathered at points) and k_ens_obs_space_h (kOp
+// true: hx = the operator h applied to the members): only the prologue's right-hand side differs.
+template <bool kOp>
+__device__ __forceinline__ void as_stage(const EnsAsArgs a, const EnsObsOp h, double *xk, double *yk, double *zk)
+{
     const int tid = (int)threadIdx.x, n = a.n, nobs = a.nobs;
     const long row = a.row;
     const double dn = (double)n, dn1 = (double)(n - 1);
@@ -69,7 +109,8 @@ __global__ __launch_bounds__(kAsThreads) void k_ens_obs_space(const EnsAsArgs a)
     for (long q = tid; q < (long)nobs * row; q += kAsThreads) {
         const int j = (int)(q / row), m = (int)(q % row);
         if (m < n) {
-            a.hx[q] = a.tab[(long)a.blk[j] * n + m][a.off[j]];
+            if constexpr (kOp) a.hx[q] = obs_apply(h, j, m);
+            else a.hx[q] = a.tab[(long)a.blk[j] * n + m][a.off[j]];
         } else {
             a.hx[q] = 0.0; a.y[q] = 0.0; a.z[q] = 0.0;
         }
@@ -177,6 +218,27 @@ __global__ __launch_bounds__(kAsThreads) void k_ens_obs_space(const EnsAsArgs a)
     if (tid == 0) *a.nonfinite = bad;
 }
 
+__global__ __launch_bounds__(kAsThreads) void k_ens_obs_space(const EnsAsArgs a)
+{
+    __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
+    as_stage<false>(a, EnsObsOp{}, xk, yk, zk);
+}
+
+// grid: (observations / 256, members)
+__global__ __launch_bounds__(256) void k_ens_sample_h(const EnsObsOp h, int n, int nobs, double *__restrict__ out)
+{
+    const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x), m = (int)blockIdx.y;
+    if (j >= nobs) return;
+    out[(long)j * n + m] = obs_apply(h, j, m);
+}
+
+// k_ens_obs_space with the operator in its prologue: one thread per (observation, member) in turn
+__global__ __launch_bounds__(kAsThreads) void k_ens_obs_space_h(const EnsAsArgs a, const EnsObsOp h)
+{
+    __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
+    as_stage<true>(a, h, xk, yk, zk);
+}
+
 int launch_ens_obs_space(const EnsAsArgs &a, hipStream_t s)
 {
     if (a.n < 2 || a.n > OCN_ENS_MAX_MEMBERS || a.nobs < 1 || a.ntaper < 1 || a.reach < 0 || a.reach > 255 ||
@@ -184,6 +246,24 @@ int launch_ens_obs_space(const EnsAsArgs &a, hipStream_t s)
         !a.taper || !a.hx || !a.y || !a.z || !a.innovation || !a.prior || !a.posterior || !a.nonfinite)
         return set_error(OCN_ERR_ARG, "ens_obs_space: member count, tables or reach");
     hipLaunchKernelGGL(k_ens_obs_space, dim3(1), dim3(kAsThreads), 0, s, a);
+    return check_launch();
+}
+
+int launch_ens_sample_h(const EnsObsOp &h, int n, int nobs, double *d_out, hipStream_t s)
+{
+    if (n < 1 || n > OCN_ENS_MAX_MEMBERS || nobs < 1 || !h.tab || !h.start || !h.term || !d_out)
+        return set_error(OCN_ERR_ARG, "ens_sample_h: nothing to gather");
+    hipLaunchKernelGGL(k_ens_sample_h, dim3((unsigned)((nobs + 255) / 256), (unsigned)n), dim3(256), 0, s, h, n, nobs, d_out);
+    return check_launch();
+}
+
+int launch_ens_obs_space_h(const EnsAsArgs &a, const EnsObsOp &h, hipStream_t s)
+{
+    if (a.n < 2 || a.n > OCN_ENS_MAX_MEMBERS || a.nobs < 1 || a.ntaper < 1 || a.reach < 0 || a.reach > 255 ||
+        a.row != (long)ens_lu_row(a.n) || !h.tab || !h.start || !h.term || !a.io || !a.jo || !a.value || !a.variance ||
+        !a.taper || !a.hx || !a.y || !a.z || !a.innovation || !a.prior || !a.posterior || !a.nonfinite)
+        return set_error(OCN_ERR_ARG, "ens_obs_space_h: member count, tables or reach");
+    hipLaunchKernelGGL(k_ens_obs_space_h, dim3(1), dim3(kAsThreads), 0, s, a, h);
     return check_launch();
 }
 

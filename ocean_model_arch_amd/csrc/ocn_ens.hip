@@ -1010,45 +1010,91 @@ int ocn_ens_local_update(ocn_ens *e, const int32_t *field_ids, int32_t nfields, 
 }
 
 // ------------------------------------------------------------------ the serial filter on the device (ens_assim.hip)
-// Launches per call: kAsLaunches for the observation-space stage (k_ens_obs_space, whatever n and nobs), then
-// ocn_ens_local_update's: one per listed field and block that an observation reaches.
+// Launches per call: kAsLaunches for the observation-space stage (k_ens_obs_space, or k_ens_obs_space_h behind a
+// sparse linear observation operator; whatever n and nobs), then ocn_ens_local_update's: one per listed field
+// and block that an observation reaches.
 constexpr int kAsLaunches = 1;
 static_assert(kAsLaunches == 1, "ocn_sw.h and DESIGN.md state this count");
 
-int ocn_ens_assimilate(ocn_ens *e, int32_t obs_field, const int32_t *field_ids, int32_t nfields, const uint8_t *use,
-                       int32_t nobs, const int32_t *io, const int32_t *jo, const double *value, const double *variance,
-                       const double *taper, int32_t ntaper)
+// the local block a global point is read in -- the one whose interior holds it, else the first whose array
+// does -- or -1
+static int ens_block_of(const ocn_ctx *c0, int32_t i, int32_t j)
 {
-    if (!e || !field_ids || !io || !jo || !value || !variance || !taper) return set_error(OCN_ERR_ARG, "ens_assimilate: null argument");
-    const ocn_ctx *c0 = e->m[0];
-    const std::vector<ocn_ctx *> in = ens_in_use(e, use);
-    RC(ens_lu_check(e, "ens_assimilate", field_ids, nfields, in, nobs, io, jo, taper, ntaper));
-    if (!has_r8(c0, obs_field)) return set_error(OCN_ERR_ARG, "ens_assimilate: the observed field is not a real(8) field of the members");
+    const size_t nblk = c0->blocks.size();
+    for (size_t b = 0; b < nblk; ++b) {
+        const ocn_block &g = c0->blocks[b].g;
+        if (i >= g.nx_start && i <= g.nx_end && j >= g.ny_start && j <= g.ny_end) return (int)b;
+    }
+    for (size_t b = 0; b < nblk; ++b) {
+        const ocn_block &g = c0->blocks[b].g;
+        if (i >= g.bnd_x1 && i <= g.bnd_x2 && j >= g.bnd_y1 && j <= g.bnd_y2) return (int)b;
+    }
+    return -1;
+}
+
+// What ocn_ens_assimilate and ocn_ens_assimilate_h check alike beyond ens_lu_check: the observed values
+static int ens_as_check(const std::string &who, int32_t nobs, const double *value, const double *variance)
+{
     for (int32_t k = 0; k < nobs; ++k) {
-        if (!std::isfinite(value[k])) return set_error(OCN_ERR_ARG, "ens_assimilate: a value that is not finite");
+        if (!std::isfinite(value[k])) return set_error(OCN_ERR_ARG, who + ": a value that is not finite");
         if (!std::isfinite(variance[k]) || !(variance[k] > 0.0))
-            return set_error(OCN_ERR_ARG, "ens_assimilate: a variance that is not finite and positive");
+            return set_error(OCN_ERR_ARG, who + ": a variance that is not finite and positive");
     }
+    return OCN_OK;
+}
+
+// A sparse linear observation operator (ocn_sw.h ocn_ens_sample_h), validated and resolved for n members in
+// use: its distinct fields in the order of their first term, and each term's pointer-table slot
+// (field slot * blocks + block) * n, element offset and weight.  Nothing is read beyond a bad row.
+struct EnsObsHost { std::vector<int32_t> fields; std::vector<EnsObsTerm> term; };
+
+static int ens_obs_resolve(const ocn_ctx *c0, const std::string &who, size_t n, int32_t nobs, const int32_t *start,
+                           const int32_t *tfield, const int32_t *ti, const int32_t *tj, const double *tw, EnsObsHost &h)
+{
+    if (start[0] != 0) return set_error(OCN_ERR_ARG, who + ": start[0] is not 0");
+    const size_t nblk = c0->blocks.size();
+    for (int32_t j = 0; j < nobs; ++j) {
+        const int64_t terms = (int64_t)start[j + 1] - start[j];
+        if (terms < 1 || terms > OCN_ENS_OBS_MAX_TERMS)
+            return set_error(OCN_ERR_ARG, who + ": an observation with 0 or more than 16 terms");
+        for (int32_t t = start[j]; t < start[j + 1]; ++t) {
+            if (!std::isfinite(tw[t]) || tw[t] == 0.0) return set_error(OCN_ERR_ARG, who + ": a weight that is zero or not finite");
+            if (!has_r8(c0, tfield[t])) return set_error(OCN_ERR_ARG, who + ": a term's field is not a real(8) field of the members");
+            size_t f = 0;
+            while (f < h.fields.size() && h.fields[f] != tfield[t]) ++f;
+            if (f == h.fields.size()) {
+                if (f == OCN_ENS_OBS_MAX_FIELDS) return set_error(OCN_ERR_ARG, who + ": more than 4 distinct fields");
+                h.fields.push_back(tfield[t]);
+            }
+            const int at = ens_block_of(c0, ti[t], tj[t]);
+            if (at < 0) return set_error(OCN_ERR_ARG, who + ": a term in no local block's array");
+            const ocn_block &g = c0->blocks[(size_t)at].g;
+            h.term.push_back(EnsObsTerm{(long)((f * nblk + (size_t)at) * n),
+                                        (long)(tj[t] - g.bnd_y1) * (long)g.pitch + (ti[t] - g.bnd_x1), tw[t]});
+        }
+    }
+    return OCN_OK;
+}
+
+// the pointer table of `fields` over the blocks and the members in use, as the field tables name the arrays now
+static void ens_obs_table(const std::vector<ocn_ctx *> &in, const std::vector<int32_t> &fields, const double **tab)
+{
+    const size_t n = in.size(), nblk = in[0]->blocks.size();
+    for (size_t f = 0; f < fields.size(); ++f)
+        for (size_t b = 0; b < nblk; ++b)
+            for (size_t m = 0; m < n; ++m)
+                tab[(f * nblk + b) * n + m] = (const double *)in[m]->blocks[b].ptr[field_slot(fields[f])];
+}
+
+// ocn_ens_assimilate and ocn_ens_assimilate_h behind their checks.  The prologue reads `src`, the fields of
+// the pointer table: one field at the points (off, blk), or with `start` the operator's terms.
+static int ens_as_run(ocn_ens *e, const char *entry, const std::vector<ocn_ctx *> &in, const int32_t *field_ids, int32_t nfields,
+                      int32_t nobs, const int32_t *io, const int32_t *jo, const double *value, const double *variance,
+                      const double *taper, int32_t ntaper, const std::vector<int32_t> &src, const std::vector<long> &off,
+                      const std::vector<int> &blk, const int32_t *start, const std::vector<EnsObsTerm> &term)
+{
+    const ocn_ctx *c0 = e->m[0];
     const size_t n = in.size(), nblk = c0->blocks.size(), no = (size_t)nobs;
-    // each observation's block -- the one whose interior holds the point, else the first whose array does --
-    // and its element there
-    std::vector<long> off(no);
-    std::vector<int> blk(no);
-    for (size_t k = 0; k < no; ++k) {
-        int at = -1;
-        for (size_t b = 0; b < nblk && at < 0; ++b) {
-            const ocn_block &g = c0->blocks[b].g;
-            if (io[k] >= g.nx_start && io[k] <= g.nx_end && jo[k] >= g.ny_start && jo[k] <= g.ny_end) at = (int)b;
-        }
-        for (size_t b = 0; b < nblk && at < 0; ++b) {
-            const ocn_block &g = c0->blocks[b].g;
-            if (io[k] >= g.bnd_x1 && io[k] <= g.bnd_x2 && jo[k] >= g.bnd_y1 && jo[k] <= g.bnd_y2) at = (int)b;
-        }
-        if (at < 0) return set_error(OCN_ERR_ARG, "ens_assimilate: an observation in no local block's array");
-        const ocn_block &g = c0->blocks[(size_t)at].g;
-        blk[k] = at;
-        off[k] = (long)(jo[k] - g.bnd_y1) * (long)g.pitch + (io[k] - g.bnd_x1);
-    }
     const int reach = ens_lu_reach(ntaper);
     std::vector<std::vector<EnsLuObs>> lists;
     const size_t list_n = ens_lu_lists(c0, nobs, io, jo, reach, lists);
@@ -1057,9 +1103,10 @@ int ocn_ens_assimilate(ocn_ens *e, int32_t obs_field, const int32_t *field_ids, 
     auto part = [](size_t at, size_t bytes) { return at + (bytes + 255) / 256 * 256; };
     const size_t row = ens_lu_row((int)n), rows_b = no * row * sizeof(double);
     const size_t tap_at = 0, list_at0 = part(tap_at, (size_t)ntaper * sizeof(double)), val_at = part(list_at0, list_n * sizeof(EnsLuObs)),
-                 var_at = part(val_at, no * 8), off_at = part(var_at, no * 8), io_at = part(off_at, no * sizeof(long)),
-                 jo_at = part(io_at, no * 4), blk_at = part(jo_at, no * 4), tab_at = part(blk_at, no * 4),
-                 up_b = part(tab_at, nblk * n * sizeof(double *)), hx_at = up_b, y_at = part(hx_at, rows_b),
+                 var_at = part(val_at, no * 8), off_at = part(var_at, no * 8), io_at = part(off_at, off.size() * sizeof(long)),
+                 jo_at = part(io_at, no * 4), blk_at = part(jo_at, no * 4), start_at = part(blk_at, blk.size() * 4),
+                 term_at = part(start_at, start ? (no + 1) * 4 : 0), tab_at = part(term_at, term.size() * sizeof(EnsObsTerm)),
+                 up_b = part(tab_at, src.size() * nblk * n * sizeof(double *)), hx_at = up_b, y_at = part(hx_at, rows_b),
                  z_at = part(y_at, rows_b), vec_at = part(z_at, rows_b), count_at = part(vec_at, 3 * no * 8),
                  need = part(count_at, sizeof(long));
     // the buffers first (a failed allocation leaves the members as they were, and no earlier result)
@@ -1079,7 +1126,7 @@ int ocn_ens_assimilate(ocn_ens *e, int32_t obs_field, const int32_t *field_ids, 
         HIPCHK(hipHostMalloc(&e->h_as, grown, hipHostMallocDefault));
         e->as_bytes = grown;
     }
-    for (ocn_ctx *c : in) RC(guarded(c, "ocn_ens_assimilate", [&] { return complete_open(c); }));
+    for (ocn_ctx *c : in) RC(guarded(c, entry, [&] { return complete_open(c); }));
     // the tables up from pinned memory in one copy, ahead of the launches; the members' arrays as the field
     // tables name them now
     if (e->ev_as_set) HIPCHK(hipEventSynchronize(e->ev_as));
@@ -1089,13 +1136,16 @@ int ocn_ens_assimilate(ocn_ens *e, int32_t obs_field, const int32_t *field_ids, 
     ens_lu_put_lists(lists, h, list_at0, list_at);
     memcpy(h + val_at, value, no * 8);
     memcpy(h + var_at, variance, no * 8);
-    memcpy(h + off_at, off.data(), no * sizeof(long));
     memcpy(h + io_at, io, no * 4);
     memcpy(h + jo_at, jo, no * 4);
-    memcpy(h + blk_at, blk.data(), no * 4);
-    for (size_t b = 0; b < nblk; ++b)
-        for (size_t m = 0; m < n; ++m)
-            ((const double **)(h + tab_at))[b * n + m] = (const double *)in[m]->blocks[b].ptr[field_slot(obs_field)];
+    if (start) {
+        memcpy(h + start_at, start, (no + 1) * 4);
+        memcpy(h + term_at, term.data(), term.size() * sizeof(EnsObsTerm));
+    } else {
+        memcpy(h + off_at, off.data(), no * sizeof(long));
+        memcpy(h + blk_at, blk.data(), no * 4);
+    }
+    ens_obs_table(in, src, (const double **)(h + tab_at));
     e->as_last = ocn_ens::AsLast{};   // (the results of the call before are overwritten from here on)
     HIPCHK(hipMemcpyAsync(d, h, up_b, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipEventRecord(e->ev_as, e->stream));
@@ -1109,12 +1159,99 @@ int ocn_ens_assimilate(ocn_ens *e, int32_t obs_field, const int32_t *field_ids, 
     a.nonfinite = (long *)(d + count_at);
     a.row = (long)row; a.n = (int)n; a.nobs = nobs; a.ntaper = ntaper; a.reach = reach;
     if (timed) HIPCHK(hipEventRecord(e->ev_t[0], e->stream));
-    RC(launch_ens_obs_space(a, e->stream));
+    if (start) {
+        const EnsObsOp op{a.tab, (const int *)(d + start_at), (const EnsObsTerm *)(d + term_at)};
+        RC(launch_ens_obs_space_h(a, op, e->stream));
+    } else {
+        RC(launch_ens_obs_space(a, e->stream));
+    }
     if (timed) HIPCHK(hipEventRecord(e->ev_t[1], e->stream));
     const int rc = ens_lu_launches(in, field_ids, nfields, lists, d, list_at, a.y, a.z, a.taper, ntaper, reach, e->stream);
     if (timed) HIPCHK(hipEventRecord(e->ev_t[2], e->stream));
     if (!rc) e->as_last = ocn_ens::AsLast{nobs, (int)n, row, hx_at, vec_at, count_at, timed};
     return rc;
+}
+
+int ocn_ens_assimilate(ocn_ens *e, int32_t obs_field, const int32_t *field_ids, int32_t nfields, const uint8_t *use,
+                       int32_t nobs, const int32_t *io, const int32_t *jo, const double *value, const double *variance,
+                       const double *taper, int32_t ntaper)
+{
+    if (!e || !field_ids || !io || !jo || !value || !variance || !taper) return set_error(OCN_ERR_ARG, "ens_assimilate: null argument");
+    const ocn_ctx *c0 = e->m[0];
+    const std::vector<ocn_ctx *> in = ens_in_use(e, use);
+    RC(ens_lu_check(e, "ens_assimilate", field_ids, nfields, in, nobs, io, jo, taper, ntaper));
+    if (!has_r8(c0, obs_field)) return set_error(OCN_ERR_ARG, "ens_assimilate: the observed field is not a real(8) field of the members");
+    RC(ens_as_check("ens_assimilate", nobs, value, variance));
+    // each observation's block and its element there
+    const size_t no = (size_t)nobs;
+    std::vector<long> off(no);
+    std::vector<int> blk(no);
+    for (size_t k = 0; k < no; ++k) {
+        const int at = ens_block_of(c0, io[k], jo[k]);
+        if (at < 0) return set_error(OCN_ERR_ARG, "ens_assimilate: an observation in no local block's array");
+        const ocn_block &g = c0->blocks[(size_t)at].g;
+        blk[k] = at;
+        off[k] = (long)(jo[k] - g.bnd_y1) * (long)g.pitch + (io[k] - g.bnd_x1);
+    }
+    return ens_as_run(e, "ocn_ens_assimilate", in, field_ids, nfields, nobs, io, jo, value, variance, taper, ntaper, {obs_field},
+                      off, blk, nullptr, {});
+}
+
+int ocn_ens_assimilate_h(ocn_ens *e, const int32_t *field_ids, int32_t nfields, const uint8_t *use, int32_t nobs,
+                         const int32_t *io, const int32_t *jo, const int32_t *start, const int32_t *tfield, const int32_t *ti,
+                         const int32_t *tj, const double *tw, const double *value, const double *variance, const double *taper,
+                         int32_t ntaper)
+{
+    if (!e || !field_ids || !io || !jo || !start || !tfield || !ti || !tj || !tw || !value || !variance || !taper)
+        return set_error(OCN_ERR_ARG, "ens_assimilate_h: null argument");
+    const std::vector<ocn_ctx *> in = ens_in_use(e, use);
+    RC(ens_lu_check(e, "ens_assimilate_h", field_ids, nfields, in, nobs, io, jo, taper, ntaper));
+    RC(ens_as_check("ens_assimilate_h", nobs, value, variance));
+    EnsObsHost h;
+    RC(ens_obs_resolve(e->m[0], "ens_assimilate_h", in.size(), nobs, start, tfield, ti, tj, tw, h));
+    return ens_as_run(e, "ocn_ens_assimilate_h", in, field_ids, nfields, nobs, io, jo, value, variance, taper, ntaper, h.fields,
+                      {}, {}, start, h.term);
+}
+
+// ocn_ens_sample with the operator in the points' place, in ocn_ens_sample's buffers
+int ocn_ens_sample_h(ocn_ens *e, const uint8_t *use, int32_t nobs, const int32_t *start, const int32_t *tfield,
+                     const int32_t *ti, const int32_t *tj, const double *tw, double *host)
+{
+    if (!e || !start || !tfield || !ti || !tj || !tw || !host) return set_error(OCN_ERR_ARG, "ens_sample_h: null argument");
+    if (nobs < 1 || nobs > 65536) return set_error(OCN_ERR_ARG, "ens_sample_h: 1..65536 observations");
+    const ocn_ctx *c0 = e->m[0];
+    const std::vector<ocn_ctx *> in = ens_in_use(e, use);
+    if (in.empty()) return set_error(OCN_ERR_ARG, "ens_sample_h: no member in use");
+    const size_t n = in.size(), nblk = c0->blocks.size(), no = (size_t)nobs;
+    EnsObsHost h;
+    RC(ens_obs_resolve(c0, "ens_sample_h", n, nobs, start, tfield, ti, tj, tw, h));
+    HIPCHK(hipSetDevice(e->device));
+    // one layout on both sides: the rows' starts, the terms, the members' arrays per field and block (up), the
+    // results (down)
+    const size_t start_b = ((no + 1) * 4 + 7) / 8 * 8, term_b = h.term.size() * sizeof(EnsObsTerm),
+                 tab_b = h.fields.size() * nblk * n * sizeof(double *), up_b = start_b + term_b + tab_b, res_b = no * n * sizeof(double);
+    if (e->samp_bytes < up_b + res_b) {   // (a synchronous entry: nothing in flight reads the old ones)
+        if (e->d_samp) (void)hipFree(e->d_samp);
+        if (e->h_samp) (void)hipHostFree(e->h_samp);
+        e->d_samp = e->h_samp = nullptr;
+        e->samp_bytes = 0;
+        HIPCHK(hipMalloc(&e->d_samp, up_b + res_b));
+        HIPCHK(hipHostMalloc(&e->h_samp, up_b + res_b, hipHostMallocDefault));
+        e->samp_bytes = up_b + res_b;
+    }
+    char *d = (char *)e->d_samp, *hp = (char *)e->h_samp;
+    memcpy(hp, start, (no + 1) * 4);
+    memcpy(hp + start_b, h.term.data(), term_b);
+    // the members in use: their pending call tails formed, their arrays as the field tables name them now
+    for (ocn_ctx *c : in) RC(guarded(c, "ocn_ens_sample_h", [&] { return complete_open(c); }));
+    ens_obs_table(in, h.fields, (const double **)(hp + start_b + term_b));
+    HIPCHK(hipMemcpyAsync(d, hp, up_b, hipMemcpyHostToDevice, e->stream));
+    const EnsObsOp op{(const double *const *)(d + start_b + term_b), (const int *)d, (const EnsObsTerm *)(d + start_b)};
+    RC(launch_ens_sample_h(op, (int)n, nobs, (double *)(d + up_b), e->stream));
+    HIPCHK(hipMemcpyAsync(hp + up_b, d + up_b, res_b, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    memcpy(host, hp + up_b, res_b);
+    return OCN_OK;
 }
 
 // bytes [at, at + bytes) of the last call's results into the pinned copy, with one wait

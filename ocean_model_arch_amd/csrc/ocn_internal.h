@@ -286,6 +286,17 @@ struct EnsAsArgs {
     long row; int n, nobs, ntaper, reach;
 };
 int launch_ens_obs_space(const EnsAsArgs &a, hipStream_t s);
+// A sparse linear observation operator on the device (ens_assim.hip; ocn_sw.h ocn_ens_sample_h,
+// ocn_ens_assimilate_h): observation j owns the terms start[j] .. start[j+1]-1 (1 .. OCN_ENS_OBS_MAX_TERMS of
+// them); term t is element off of tab[slot + m] for member u_m -- slot = (field slot * blocks + block) * n, tab
+// the members' arrays field by field, block by block -- times w.  The host has validated every offset.
+struct EnsObsTerm { long slot, off; double w; };
+struct EnsObsOp { const double *const *tab; const int *start; const EnsObsTerm *term; };
+// out[j * n + m] = H_j(member u_m), j < nobs.  ONE launch.
+int launch_ens_sample_h(const EnsObsOp &h, int n, int nobs, double *d_out, hipStream_t s);
+// launch_ens_obs_space with the prologue hx[j][m] = H_j(member u_m): a.tab, a.off and a.blk are not read.  ONE
+// launch of ONE workgroup of kAsThreads threads.
+int launch_ens_obs_space_h(const EnsAsArgs &a, const EnsObsOp &h, hipStream_t s);
 // Covariance inflation (ens_inflate.hip; ocn_sw.h ocn_ens_inflate) of the n arrays mem[0 .. n) (one field of
 // one block geometry, the members in use in member order, n >= 2), in place, at every point of
 // A(bnd_x1:bnd_x2, bnd_y1:bnd_y2).  mode: OCN_ENS_INFLATE_*; d_spread: the saved spread (RTPS; else unused);

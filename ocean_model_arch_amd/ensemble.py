@@ -12,7 +12,7 @@ import operator
 
 import numpy as np
 
-from . import _lib, ens_local_rule, ens_perturb_rule
+from . import _lib, ens_local_rule, ens_obs_rule, ens_perturb_rule
 from ._lib import check, lib
 from .config import BasinConfig, ParallelConfig, SWConfig
 from .model import BlockInfo, OceanModel
@@ -520,6 +520,96 @@ class OceanEnsemble:
                 with np.errstate(all="ignore"):
                     out["posterior_spread"] = np.array([ens_local_rule._spread(r) for r in out["hx"]])
             out["nonfinite"] = nonfinite
+            return out
+        return finish if defer else finish()
+
+    # ------------------------------------------------------------ off-grid observations: a sparse linear H
+    def _op_arrays(self, op):
+        """The operator's CSR arrays as the library takes them (kept alive by the caller)."""
+        if not isinstance(op, ens_obs_rule.ObsOperator):
+            raise TypeError(f"an ens_obs_rule.ObsOperator, not {type(op).__name__}")
+        return [np.ascontiguousarray(op.start, dtype=np.int32),
+                np.ascontiguousarray([_lib.FIELD_ID[nm] for nm in op.tname], dtype=np.int32),
+                np.ascontiguousarray(op.ti, dtype=np.int32), np.ascontiguousarray(op.tj, dtype=np.int32),
+                np.ascontiguousarray(op.tw, dtype=np.float64)]
+
+    def sample_h(self, op, members=None) -> np.ndarray:
+        """The sparse linear observation operator `op` (ens_obs_rule.ObsOperator: points, bilinear, combine)
+        applied to the members in use: a float64 array (nobs, n), column m the m-th of `members` in member order
+        (None: all), each entry the ordered sum of include/ocn_sw.h ocn_ens_sample_h -- ens_obs_rule.apply on the
+        members' downloads gives the same bits.  One launch and one wait; pending call tails of the members in
+        use are formed first.  At most 65536 observations a call."""
+        arrays = self._op_arrays(op)
+        out = np.zeros((op.nobs, self._count(members)), dtype=np.float64)
+        check(lib().ocn_ens_sample_h(self.ens, self._use(members), op.nobs, *[a.ctypes.data_as(C.c_void_p) for a in arrays],
+                                     out.ctypes.data_as(C.c_void_p)), "ocn_ens_sample_h")
+        return out
+
+    def assimilate_h(self, op, values, variances, taper, names=STATE, members=None, device: bool = False, rtps=None) -> dict:
+        """assimilate() for observations that are not one field at one grid point: observation j is `values[j]`,
+        with error variance `variances[j]`, of row j of the sparse linear operator `op`
+        (ens_obs_rule.ObsOperator) applied to the members; op.anchors[j], an integer point of the basin, is its
+        localization centre -- towards the other observations and towards the fields (the true position is at
+        most 0.71 cells from the nearest point).  The keys returned are assimilate()'s.
+
+        device=False: sample_h(), the observation-space loop on the host (ens_local_rule.ensrf_obs_space at the
+        anchors), one local_update() at the anchors.  device=True: ocn_ens_assimilate_h -- the operator, the loop
+        and the field update on the ensemble's stream with no wait in between -- plus "nonfinite".
+
+        The rows are an augmented state carried through the loop at their anchors.  With a taper that is 1.0
+        everywhere "hx" is what sample_h() gives afterwards, to rounding; with any other taper it is not (the
+        fields' update weighs each term's point by its own distance).  Calls therefore do not compose: more than
+        8192 observations raise ValueError on either path and are not split.
+
+        rtps=alpha: as in assimilate() -- spread_save(names) before, inflate(alpha, "rtps", names) after, with
+        device=True no wait in between."""
+        if rtps is not None:
+            alpha = float(rtps)
+            if not np.isfinite(alpha) or alpha < 0.0:
+                raise ValueError(f"assimilate_h: rtps = {rtps!r}, not a finite float >= 0")
+            self.spread_save(names, members=members)
+            info = self._assimilate_h(op, values, variances, taper, names, members, device, defer=True)
+            self.inflate(alpha, "rtps", names, members=members)
+            return info()
+        return self._assimilate_h(op, values, variances, taper, names, members, device)
+
+    def _assimilate_h(self, op, values, variances, taper, names, members, device, defer: bool = False):
+        """assimilate_h() without the relaxation.  defer: return a function that gives the results, so that the
+        caller may issue more work behind the analysis before the device path's first wait."""
+        arrays = self._op_arrays(op)
+        nobs, n = op.nobs, self._count(members)
+        if nobs > ens_local_rule.MAX_OBS:
+            raise ValueError(f"assimilate_h: {nobs} observations, more than {ens_local_rule.MAX_OBS}: the rows are an "
+                             f"augmented state, calls would not compose")
+        va = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
+        ra = np.ascontiguousarray(np.asarray(variances, dtype=np.float64).ravel())
+        ta = np.ascontiguousarray(np.asarray(taper, dtype=np.float64))
+        if len(va) != nobs or len(ra) != nobs:
+            raise ValueError(f"assimilate_h: {len(va)} values and {len(ra)} variances for {nobs} observations")
+        if ta.ndim != 1 or not 1 <= len(ta) <= ens_local_rule.MAX_TAPER:
+            raise ValueError(f"assimilate_h: a taper of shape {ta.shape}, not 1..{ens_local_rule.MAX_TAPER} entries")
+        names = (names,) if isinstance(names, str) else tuple(names)
+        if not device:
+            hx = self.sample_h(op, members=members)
+            Y, Z, info = ens_local_rule.ensrf_obs_space(hx, op.anchors, va, ra, ta)
+            self.local_update(Y, Z, op.anchors, ta, names=names, members=members)
+            return (lambda: info) if defer else info
+        ids = (C.c_int32 * len(names))(*[_lib.FIELD_ID[nm] for nm in names])
+        io, jo = (np.ascontiguousarray(op.anchors[:, c], dtype=np.int32) for c in range(2))
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        L = lib()
+        check(L.ocn_ens_assimilate_h(self.ens, ids, len(names), self._use(members), nobs, ptr(io), ptr(jo),
+                                     *[ptr(a) for a in arrays], ptr(va), ptr(ra), ptr(ta), len(ta)), "ocn_ens_assimilate_h")
+
+        def finish():   # the call's results (one wait each)
+            out = {}
+            for key in ("hx", "innovations", "prior_spread", "posterior_spread"):
+                a = np.zeros((nobs, n) if key == "hx" else nobs, dtype=np.float64)
+                check(L.ocn_ens_assimilate_result(self.ens, _lib.ENS_ASSIM[key], ptr(a)), "ocn_ens_assimilate_result")
+                out[key] = a
+            info = _lib.OcnEnsAssimInfo()
+            check(L.ocn_ens_assimilate_info(self.ens, C.byref(info)), "ocn_ens_assimilate_info")
+            out["nonfinite"] = int(info.nonfinite)
             return out
         return finish if defer else finish()
 
