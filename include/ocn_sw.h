@@ -568,7 +568,8 @@ int ocn_ens_info(ocn_ens *ens, ocn_ens_info_t *out);
  * OCN_ENS_OPT_MAX_GROUP (measurements; 0 = none): at most this many of the members planned in a call go
  * to ocn_ens_plan together (in member order), so that several shorter launches can be timed against
  * one taller one (scripts/ens_bench.py). */
-enum { OCN_ENS_OPT_CAPACITY = 1, OCN_ENS_OPT_MAX_GROUP = 2, OCN_ENS_OPT_ASSIM_TIMING = 3 };
+enum { OCN_ENS_OPT_CAPACITY = 1, OCN_ENS_OPT_MAX_GROUP = 2, OCN_ENS_OPT_ASSIM_TIMING = 3,
+       OCN_ENS_OPT_RECORD_IN_LAUNCH = 4 /* ocn_ens_step_record below: 1 (default) or 0 */ };
 int ocn_ens_set_option(ocn_ens *ens, int32_t key, int64_t value);
 
 /* Statistics over the members, formed on the device (the members' fields lie side by side in device
@@ -799,6 +800,60 @@ int ocn_ens_assimilate_h(ocn_ens *ens, const int32_t *field_ids, int32_t nfields
                          const int32_t *io, const int32_t *jo, const int32_t *start, const int32_t *tfield,
                          const int32_t *ti, const int32_t *tj, const double *tw, const double *value,
                          const double *variance, const double *taper, int32_t ntaper);
+
+/* Station time series: the members' values at tide gauges or buoys as a function of time, and the model's
+ * equivalents of observations taken during the forecast window, recorded while the members step -- INSIDE
+ * the multi-step launch where there is one.  No counterpart in the reference.
+ *
+ * ocn_ens_record_begin starts a recorder: the operator is ocn_ens_sample_h's CSR table with the same
+ * validation and the same ordered sum H_j(u), but its terms may name only the six prognostic fields (ssh,
+ * sshp, ubrtr, ubrtrp, vbrtr, vbrtrp: everything else is formed by a call's tail only); the members in use
+ * are u0 < u1 < ... < u(n-1) in member order (use as in ocn_ens_stats).  The series -- max_records x nobs x n
+ * doubles, at most 1 GiB -- lives in a buffer the ensemble owns until ocn_ens_record_end, ocn_ens_destroy
+ * or the next ocn_ens_record_begin.  Synchronous.
+ *
+ * ocn_ens_step_record(tau, nsteps, check_every) leaves every member exactly as ocn_ens_step with the same
+ * arguments would -- the same bits, the same statuses -- and counts its steps since ocn_ens_record_begin:
+ * after the counted step (r + 1) * every it writes record r,
+ *   series[(r * nobs + j) * n + m] = H_j(member u_m's state after that step),
+ * the state the CPU oracle holds after as many step(tau) calls, which is also what ocn_ens_sample_h returns
+ * after as many ocn_ens_step(tau, 1).  Asynchronous on the ensemble's stream, no host wait.  Where every
+ * member in use plans a multi-step launch for the call (an open sequence, a variant chosen on the host, one
+ * small block, check_every 0 or 1, at least 2 steps: as ocn_ens_step batches them) and lands in a group
+ * under the recording launches' own resident capacity, the records are written by the marching launch
+ * itself, after the barrier behind each due step, and the call's last step's by ONE gather launch behind it.
+ * Otherwise -- also with OCN_ENS_OPT_RECORD_IN_LAUNCH 0 (tests, measurements) -- the call is chunked: up to
+ * each due step an ocn_ens_step, then one gather launch from the members' current arrays (no tail is formed:
+ * the six fields are current after every call; the checks stay at the steps s of the call with
+ * s % check_every == 0).  The bits of the series and of the members do not
+ * depend on the route.  ocn_ens_step, ocn_ens_assimilate, ocn_ens_perturb, ocn_ens_inflate, ocn_ens_transform
+ * and uploads while a recorder is active neither count nor record: a series may span analysis windows.
+ * A member whose status at ocn_ens_synchronize is not OCN_OK has undefined columns from that call on; the
+ * other members' columns are unaffected.  Columns are not cleared beforehand.
+ *
+ * ocn_ens_record_info: in_launch is the number of records written by a marching launch itself, cumulative
+ * (which route ran).  ocn_ens_record_download: records first .. first + count - 1 to host, synchronous.
+ * ocn_ens_record_due: the schedule alone, pure (no device, as ocn_ens_plan): the 1-based steps s of a call of
+ * nsteps steps made after `counted` counted steps at which a record is due, (counted + s) % every == 0, in
+ * rising order; *count their number, the first min(cap, *count) of them in steps.
+ *
+ * OCN_ERR_ARG -- nothing stepped, launched or written, an earlier recorder kept -- for a null argument, every
+ * case ocn_ens_sample_h refuses, a term's field that is not one of the six, every < 1, max_records < 1, a
+ * series above 1 GiB, an ocn_ens_step_record whose due records would pass max_records, a download range
+ * outside the records taken, and for ocn_ens_record_due counted < 0, nsteps < 0, every < 1, cap < 0 or cap > 0
+ * without steps.  OCN_ERR_STATE for ocn_ens_step_record, ocn_ens_record_download or ocn_ens_record_end
+ * without a recorder. */
+typedef struct ocn_ens_record_info_t {
+    int32_t active, nobs, n, every, max_records, pad;
+    int64_t steps, records, in_launch;
+} ocn_ens_record_info_t;
+int ocn_ens_record_begin(ocn_ens *ens, const uint8_t *use, int32_t nobs, const int32_t *start, const int32_t *tfield,
+                         const int32_t *ti, const int32_t *tj, const double *tw, int32_t every, int32_t max_records);
+int ocn_ens_step_record(ocn_ens *ens, double tau, int32_t nsteps, int32_t check_every);
+int ocn_ens_record_info(ocn_ens *ens, ocn_ens_record_info_t *out);
+int ocn_ens_record_download(ocn_ens *ens, int32_t first, int32_t count, double *host);
+int ocn_ens_record_end(ocn_ens *ens);
+int ocn_ens_record_due(int64_t counted, int32_t nsteps, int32_t every, int32_t *steps, int32_t cap, int32_t *count);
 
 /* Covariance inflation on the device: what keeps a square-root filter's spread from collapsing over the
  * cycles.  ocn_ens_transform can apply ONE factor to every point (n^2 work per point, and it inflates the

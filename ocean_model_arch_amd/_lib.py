@@ -108,7 +108,9 @@ ENS_SYMBOLS = ["ocn_ens_plan", "ocn_ens_create", "ocn_ens_destroy", "ocn_ens_siz
                "ocn_ens_extrema", "ocn_ens_sample", "ocn_ens_transform", "ocn_ens_local_update",
                "ocn_ens_assimilate", "ocn_ens_assimilate_info", "ocn_ens_assimilate_result", "ocn_ens_sample_h",
                "ocn_ens_assimilate_h", "ocn_ens_spread_save",
-               "ocn_ens_inflate", "ocn_ens_inflate_download", "ocn_ens_perturb", "ocn_ens_perturb_download"]
+               "ocn_ens_inflate", "ocn_ens_inflate_download", "ocn_ens_perturb", "ocn_ens_perturb_download",
+               "ocn_ens_record_begin", "ocn_ens_step_record", "ocn_ens_record_info", "ocn_ens_record_download",
+               "ocn_ens_record_end", "ocn_ens_record_due"]
 ALL_SYMBOLS = KERNEL_SYMBOLS + CTX_SYMBOLS + ENS_SYMBOLS
 ENS_MAX_MEMBERS = 256          # OCN_ENS_MAX_MEMBERS
 ENS_OBS_MAX_TERMS = 16         # OCN_ENS_OBS_MAX_TERMS
@@ -116,6 +118,7 @@ ENS_OBS_MAX_FIELDS = 4         # OCN_ENS_OBS_MAX_FIELDS
 ENS_OPT_CAPACITY = 1
 ENS_OPT_MAX_GROUP = 2
 ENS_OPT_ASSIM_TIMING = 3
+ENS_OPT_RECORD_IN_LAUNCH = 4
 # OCN_ENS_STAT_* (ocn_ens_stats), in the order of their bits
 ENS_STATS = {"mean": 1, "var": 2, "spread": 4, "min": 8, "max": 16}
 # OCN_ENS_ASSIM_* (ocn_ens_assimilate_result)
@@ -202,6 +205,12 @@ class OcnEnsExtrema(C.Structure):
 
 class OcnEnsAssimInfo(C.Structure):
     _fields_ = [("nobs", C.c_int32), ("n", C.c_int32), ("nonfinite", C.c_int64)]
+
+
+class OcnEnsRecordInfo(C.Structure):
+    _fields_ = [("active", C.c_int32), ("nobs", C.c_int32), ("n", C.c_int32), ("every", C.c_int32),
+                ("max_records", C.c_int32), ("pad", C.c_int32), ("steps", C.c_int64), ("records", C.c_int64),
+                ("in_launch", C.c_int64)]
 
 
 HALO_LOCAL, HALO_SEND, HALO_RECV = 0, 1, 2
@@ -308,6 +317,13 @@ def lib() -> C.CDLL:
     L.ocn_ens_perturb.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_int32,
                                   C.c_int32, C.c_int32, C.c_double]
     L.ocn_ens_perturb_download.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    L.ocn_ens_record_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_int32]
+    L.ocn_ens_step_record.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_int32]
+    L.ocn_ens_record_info.argtypes = [C.c_void_p, C.POINTER(OcnEnsRecordInfo)]
+    L.ocn_ens_record_download.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    L.ocn_ens_record_end.argtypes = [C.c_void_p]
+    L.ocn_ens_record_due.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
     _lib = L
     return L
 

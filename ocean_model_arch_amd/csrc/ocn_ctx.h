@@ -365,9 +365,11 @@ struct ocn_ctx {
     ocn::Batcher batcher;
     // a member of an ensemble (ocn_ens_create): the ensemble owns the context and its compute stream,
     // which the members share.  ens_collect (inside ocn_ens_step): step_impl plans a multi-step launch
-    // as ever but leaves it to the ensemble, which issues it with the other members' (ens_pending, ens_k)
+    // as ever but leaves it to the ensemble, which issues it with the other members' (ens_pending, ens_k).
+    // ens_probe (inside ocn_ens_step_record): step_impl only says whether it would plan one (ens_pending) and
+    // runs none of the call's steps
     ocn_ens *ens = nullptr;
-    bool ens_collect = false, ens_pending = false;
+    bool ens_collect = false, ens_pending = false, ens_probe = false;
     ocn::StepKind ens_k{};
 };
 

@@ -2173,11 +2173,27 @@ extern "C++" int ocn::complete_open(ocn_ctx *c)
     return finish_call(c, run_step(c, c->open_tau, last_step(c, false)));
 }
 
+// step_impl's answer to ocn_ens_step_record's probe (ens_probe): ens_pending = this call would be planned as
+// ONE multi-step launch -- the conditions of the open sequence's branch below in their order, the variant's
+// choice (prepare_kc) included -- with none of its steps run.  (Steps an earlier call deferred stay deferred:
+// the call itself runs them first.)
+static int probe_multi(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every)
+{
+    c->ens_pending = false;
+    if (!c->open || tau != c->open_tau || !c->onepass || !lazy_allowed(c, c->open_x2)) return OCN_OK;
+    RC(prepare_kc(c, c->open_x2));
+    const bool graph_ok = c->use_graph && !has_comm(c) && !c->stage_timing && !(c->sw.use_tracers > 0 && c->tr_step);
+    const bool pairs = c->open_x2 ? x4_now(c) : pair_ok(c);
+    c->ens_pending = !pairs && !c->open_x2 && !graph_ok && nsteps >= 2 && multi_ok(c, check_every);
+    return OCN_OK;
+}
+
 static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every)
 {
     HIPCHK(hipSetDevice(c->dec.device));
     if (nsteps < 0) return set_error(OCN_ERR_ARG, "nsteps < 0");
     if (nsteps == 0) return OCN_OK;
+    if (c->ens_probe) return probe_multi(c, tau, nsteps, check_every);
     // (RCCL / events stay outside graphs; so do the tracer steps' calls: their launches follow pending state)
     const bool graph_ok = c->use_graph && !has_comm(c) && !c->stage_timing && !(c->sw.use_tracers > 0 && c->tr_step);
     c->pair_used = c->nv_used = false;

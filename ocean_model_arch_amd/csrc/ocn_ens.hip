@@ -3,7 +3,8 @@
 // the statistics over the members (ens_stats.hip), their sampling and recombination
 // (ens_transform.hip), their localized observation update (ens_local.hip), the serial filter's
 // observation-space loop in front of it (ens_assim.hip), the inflation of their spread
-// (ens_inflate.hip) and their random perturbation (ens_perturb.hip).  The members' calls are planned by ocn_ctx.hip
+// (ens_inflate.hip), their random perturbation (ens_perturb.hip) and the station recorder in their launches
+// (sw_kernels.hip k_march_multi_rec).  The members' calls are planned by ocn_ctx.hip
 // step_impl; ocn_ens_plan.h holds the grouping policy.
 #include "ocn_ctx.h"
 #include "ocn_ens_plan.h"
@@ -86,7 +87,43 @@ struct ocn_ens {
     // elements apart, based like the members' arrays (raw: the allocations, made at first use); n[k]: the
     // members in use of the last noise launch on block k (0: none yet)
     struct Perturb { std::vector<void *> raw; std::vector<long long *> z; std::vector<long> stride; std::vector<int> n; } perturb;
+    // ocn_ens_record_*: the station recorder.  use: one byte per member; field: the operator's distinct fields
+    // in the order of their first term; d_series: max_records x nobs x n doubles; d_op: the rows' starts, the
+    // terms as ocn_ens_sample_h resolves them (slot: into a gather's pointer table) and, with one local block,
+    // as the recording launch reads them (slot: the field's index in `field`), at start_at / term_at / lterm_at.
+    // The tables a call brings -- the recording launches' EnsRecMember, one for every member, then one pointer
+    // table per gather, tab_b bytes each -- go up through pinned memory as the launches' member table does: a
+    // call fills one of h_stage's two copies, the next call the other; ev[i]: the stream has read copy i
+    // (awaited before it is written again); d_stage: their place on the device (stream order keeps its users
+    // apart).  steps, records: counted since ocn_ens_record_begin; in_launch: records a marching launch wrote
+    struct Recorder {
+        bool active = false;
+        int32_t nobs = 0, n = 0, every = 0, max_records = 0, records = 0;
+        int64_t steps = 0, in_launch = 0;
+        std::vector<uint8_t> use;
+        std::vector<int32_t> field;
+        void *d_series = nullptr, *d_op = nullptr, *d_stage = nullptr, *h_stage[2] = {nullptr, nullptr};
+        size_t start_at = 0, term_at = 0, lterm_at = 0, tab_b = 0, stage_bytes = 0;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        bool ev_set[2] = {false, false};
+        int slot = 0;
+    } rec;
+    bool rec_in_launch = true;     // OCN_ENS_OPT_RECORD_IN_LAUNCH
 };
+
+// the recorder's buffers and events (ocn_ens_record_end, ocn_ens_record_begin over an earlier one, ocn_ens_destroy)
+static void ens_rec_free(ocn_ens *e)
+{
+    ocn_ens::Recorder &r = e->rec;
+    if (r.d_series) (void)hipFree(r.d_series);   // (waits for the launches that use them)
+    if (r.d_op) (void)hipFree(r.d_op);
+    if (r.d_stage) (void)hipFree(r.d_stage);
+    for (int i = 0; i < 2; ++i) {
+        if (r.h_stage[i]) (void)hipHostFree(r.h_stage[i]);
+        if (r.ev[i]) (void)hipEventDestroy(r.ev[i]);
+    }
+    r = ocn_ens::Recorder{};
+}
 
 // ocn_ens_plan's policy: ocn_ens_plan.h (pure host code, also built stand-alone)
 static int ens_plan(const ocn_block *g, const int32_t *variant, int members, int64_t capacity,
@@ -144,6 +181,7 @@ int ocn_ens_destroy(ocn_ens *e)
                 if (r) (void)hipFree(r);
     for (void *r : e->perturb.raw)
         if (r) (void)hipFree(r);
+    ens_rec_free(e);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
     return OCN_OK;
@@ -216,9 +254,48 @@ static int ens_fail(ocn_ctx *c, int rc)
     return fail_fatal(c, finish_call(c, rc));
 }
 
-int ocn_ens_step(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every)
+// the launch groups of a call: ocn_ens_plan's of the members with a variant, within `capacity`
+static int ens_groups(const ocn_ens *e, const std::vector<int32_t> &variant, int64_t capacity, std::vector<ocn_ens_group> &groups)
 {
-    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    const int M = (int)e->m.size();
+    int first = OCN_OK;
+    auto note = [&](int rc) { if (rc && !first) first = rc; };
+    groups.clear();
+    if (capacity >= 1 && e->max_group < 1) {
+        note(ens_plan(&e->m[0]->blocks[0].g, variant.data(), M, capacity, groups));
+    } else if (capacity >= 1) {   // OCN_ENS_OPT_MAX_GROUP: the plan of every max_group planned members
+        std::vector<ocn_ens_group> part;
+        std::vector<int32_t> v((size_t)M, -1);
+        int n = 0;
+        for (int i = 0; i < M; ++i) {
+            if (variant[(size_t)i] >= 0) { v[(size_t)i] = variant[(size_t)i]; ++n; }
+            if (n && (n == e->max_group || i == M - 1)) {
+                note(ens_plan(&e->m[0]->blocks[0].g, v.data(), M, capacity, part));
+                groups.insert(groups.end(), part.begin(), part.end());
+                std::fill(v.begin(), v.end(), -1);
+                n = 0;
+            }
+        }
+    }
+    return first;
+}
+
+// the variant of a member whose call is planned as a multi-step launch (ens_pending), or -1: the launch takes
+// the library's fused path with the sw switches it needs; else the member's own launch
+static int32_t ens_variant(const ocn_ctx *c, double tau, bool check)
+{
+    if (c->ens_pending && c->fused && c->sw.full_free_surface == 1 && c->sw.trans_terms > 0 && c->sw.ksw_lat > 0)
+        return onepass_multi_variant(c->kc_mode, tau, check);
+    return -1;
+}
+
+// A recording call's part in ocn_ens_step's launches (ocn_ens_step_record's in-launch path): the capacity
+// in effect, the members' columns (-1: not in use), the first due step and its slot
+struct EnsRecCall { int64_t capacity; std::vector<int> col; int due0; double *slot0; };
+
+// ocn_ens_step, and with `rec` the same call with the recorder in its launches
+static int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsRecCall *rec)
+{
     const int M = (int)e->m.size();
     e->last = ocn_ens_info_t{};
     e->last.members = M;
@@ -232,30 +309,14 @@ int ocn_ens_step(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every)
         c->ens_collect = true;
         note(guarded(c, "ocn_ens_step", [&] { return step_entry(c, tau, nsteps, check_every); }));
         c->ens_collect = false;
-        // (batched: the library's fused path with the sw switches the launch needs; else its own launch)
-        if (c->ens_pending && c->fused && c->sw.full_free_surface == 1 && c->sw.trans_terms > 0 && c->sw.ksw_lat > 0)
-            variant[(size_t)i] = onepass_multi_variant(c->kc_mode, tau, c->ens_k.check);
+        variant[(size_t)i] = ens_variant(c, tau, c->ens_k.check);
     }
     HIPCHK(hipSetDevice(e->device));
-    e->last.capacity = ens_capacity(e);
+    e->last.capacity = rec ? rec->capacity : ens_capacity(e);
     std::vector<ocn_ens_group> groups;
-    if (e->last.capacity >= 1 && e->max_group < 1) {
-        note(ens_plan(&e->m[0]->blocks[0].g, variant.data(), M, e->last.capacity, groups));
-    } else if (e->last.capacity >= 1) {   // OCN_ENS_OPT_MAX_GROUP: the plan of every max_group planned members
-        std::vector<ocn_ens_group> part;
-        std::vector<int32_t> v((size_t)M, -1);
-        int n = 0;
-        for (int i = 0; i < M; ++i) {
-            if (variant[(size_t)i] >= 0) { v[(size_t)i] = variant[(size_t)i]; ++n; }
-            if (n && (n == e->max_group || i == M - 1)) {
-                note(ens_plan(&e->m[0]->blocks[0].g, v.data(), M, e->last.capacity, part));
-                groups.insert(groups.end(), part.begin(), part.end());
-                std::fill(v.begin(), v.end(), -1);
-                n = 0;
-            }
-        }
-    }
+    note(ens_groups(e, variant, e->last.capacity, groups));
     std::vector<char> done((size_t)M, 0);
+    size_t rec_off = 0;   // (members of the recording launches so far: their EnsRecMember in the call's stage)
     if (!groups.empty()) {
         const int sl = e->slot;
         e->slot ^= 1;
@@ -281,10 +342,25 @@ int ocn_ens_step(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every)
                 if (!c->fused) c->hn_fresh = false;
                 if (!rc) rc = timer_begin(c, OCN_TIMER_ONEPASS_MULTI, recs[(size_t)j]);
             }
-            if (!rc)
+            std::vector<int> col((size_t)q.members, -1);
+            bool recording = false;
+            for (int j = 0; j < q.members && rec && rec->due0 < nsteps; ++j)
+                if ((col[(size_t)j] = rec->col[(size_t)q.member[j]]) >= 0) recording = true;
+            if (!rc && recording) {   // (the call's stage: ens_rec_stage; its other copy's turn at the next call)
+                const ocn_ens::Recorder &r = e->rec;
+                const char *d = (const char *)r.d_op;
+                const EnsRecLaunch rl{col.data(), r.field.data(), (int)r.field.size(), (const int *)(d + r.start_at),
+                                      (const EnsObsTerm *)(d + r.lterm_at), rec->slot0, rec->due0, r.every, r.nobs, r.n,
+                                      (EnsRecMember *)r.h_stage[r.slot] + rec_off, (EnsRecMember *)r.d_stage + rec_off};
+                rec_off += (size_t)q.members;
+                rc = launch_onepass_multi_rec(ms.data(), q.members, q.variant, q.rows, e->m[(size_t)q.member[0]]->sw, tau,
+                                              nsteps, e->d_tab, (char *)e->h_tab[sl] + off, eb * (size_t)q.members,
+                                              (long)e->last.capacity, rl, e->stream);
+            } else if (!rc) {
                 rc = launch_onepass_multi_b(ms.data(), q.members, q.variant, q.rows, e->m[(size_t)q.member[0]]->sw, tau,
                                             nsteps, e->d_tab, (char *)e->h_tab[sl] + off, eb * (size_t)q.members,
                                             (long)e->last.capacity, e->stream);
+            }
             off += eb * (size_t)q.members;
             for (int j = 0; j < q.members; ++j) {
                 ocn_ctx *c = e->m[(size_t)q.member[j]];
@@ -321,6 +397,12 @@ int ocn_ens_step(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every)
         if (const int rc = run_step(c, tau, c->ens_k)) note(ens_fail(c, rc));
     }
     return first;
+}
+
+int ocn_ens_step(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    return ens_step_run(e, tau, nsteps, check_every, nullptr);
 }
 
 int ocn_ens_synchronize(ocn_ens *e, int32_t *status)
@@ -361,6 +443,10 @@ int ocn_ens_set_option(ocn_ens *e, int32_t key, int64_t value)
     case OCN_ENS_OPT_ASSIM_TIMING:
         if (value != 0 && value != 1) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_ASSIM_TIMING: 0 or 1");
         e->as_timing = value != 0;
+        return OCN_OK;
+    case OCN_ENS_OPT_RECORD_IN_LAUNCH:
+        if (value != 0 && value != 1) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_RECORD_IN_LAUNCH: 0 or 1");
+        e->rec_in_launch = value != 0;
         return OCN_OK;
     default: return set_error(OCN_ERR_ARG, "unknown ensemble option");
     }
@@ -1252,6 +1338,240 @@ int ocn_ens_sample_h(ocn_ens *e, const uint8_t *use, int32_t nobs, const int32_t
     HIPCHK(hipStreamSynchronize(e->stream));
     memcpy(host, hp + up_b, res_b);
     return OCN_OK;
+}
+
+// ------------------------------------------------------------------ the station recorder (ocn_sw.h ocn_ens_record_*)
+int ocn_ens_record_due(int64_t counted, int32_t nsteps, int32_t every, int32_t *steps, int32_t cap, int32_t *count)
+{
+    if (counted < 0 || nsteps < 0 || every < 1 || cap < 0 || (cap > 0 && !steps))
+        return set_error(OCN_ERR_ARG, "ens_record_due: counted >= 0, nsteps >= 0, every >= 1, cap >= 0 with an array");
+    std::vector<int32_t> due;
+    ens_record_due(counted, nsteps, every, due);
+    if (count) *count = (int32_t)due.size();
+    for (size_t i = 0; i < due.size() && (int32_t)i < cap; ++i) steps[i] = due[i];
+    return OCN_OK;
+}
+
+int ocn_ens_record_begin(ocn_ens *e, const uint8_t *use, int32_t nobs, const int32_t *start, const int32_t *tfield,
+                         const int32_t *ti, const int32_t *tj, const double *tw, int32_t every, int32_t max_records)
+{
+    if (!e || !start || !tfield || !ti || !tj || !tw) return set_error(OCN_ERR_ARG, "ens_record_begin: null argument");
+    if (nobs < 1 || nobs > 65536) return set_error(OCN_ERR_ARG, "ens_record_begin: 1..65536 observations");
+    if (every < 1 || max_records < 1) return set_error(OCN_ERR_ARG, "ens_record_begin: every >= 1 and max_records >= 1");
+    const ocn_ctx *c0 = e->m[0];
+    const std::vector<ocn_ctx *> in = ens_in_use(e, use);
+    if (in.empty()) return set_error(OCN_ERR_ARG, "ens_record_begin: no member in use");
+    const size_t n = in.size(), nblk = c0->blocks.size(), no = (size_t)nobs, M = e->m.size();
+    EnsObsHost h;
+    RC(ens_obs_resolve(c0, "ens_record_begin", n, nobs, start, tfield, ti, tj, tw, h));
+    for (int32_t f : h.fields)   // (everything else is formed by a call's tail only)
+        if (f != OCN_SSH && f != OCN_SSHP && f != OCN_UBRTR && f != OCN_UBRTRP && f != OCN_VBRTR && f != OCN_VBRTRP)
+            return set_error(OCN_ERR_ARG, "ens_record_begin: a term's field is not one of ssh, sshp, ubrtr, ubrtrp, vbrtr, vbrtrp");
+    const size_t series_b = (size_t)max_records * no * n * sizeof(double);
+    if (series_b > ((size_t)1 << 30)) return set_error(OCN_ERR_ARG, "ens_record_begin: a series above 1 GiB");
+    HIPCHK(hipSetDevice(e->device));
+    // the new recorder whole before the earlier one goes (a failed allocation keeps that one)
+    ocn_ens::Recorder r;
+    const size_t nt = h.term.size(), start_b = ((no + 1) * 4 + 255) / 256 * 256, term_b = (nt * sizeof(EnsObsTerm) + 255) / 256 * 256;
+    r.start_at = 0; r.term_at = start_b; r.lterm_at = start_b + term_b;
+    r.tab_b = (h.fields.size() * nblk * n * sizeof(double *) + 255) / 256 * 256;
+    // (the stage: the launches' tables and 16 gathers' to begin with; a call that needs more grows it)
+    r.stage_bytes = (M * sizeof(EnsRecMember) + 255) / 256 * 256 + 16 * r.tab_b;
+    int rc = check_hip(hipMalloc(&r.d_series, series_b), "hipMalloc");
+    if (!rc) rc = check_hip(hipMalloc(&r.d_op, start_b + 2 * term_b), "hipMalloc");
+    if (!rc) rc = check_hip(hipMalloc(&r.d_stage, r.stage_bytes), "hipMalloc");
+    for (int i = 0; i < 2 && !rc; ++i) {
+        rc = check_hip(hipHostMalloc(&r.h_stage[i], r.stage_bytes, hipHostMallocDefault), "hipHostMalloc");
+        if (!rc) rc = check_hip(hipEventCreateWithFlags(&r.ev[i], hipEventDisableTiming), "hipEventCreate");
+    }
+    // the operator up (synchronous: new memory that nothing in flight reads); the launch's terms name the field
+    // by its index in `field` (one block: slot = index * n)
+    std::vector<EnsObsTerm> lterm(h.term);
+    for (EnsObsTerm &q : lterm) q.slot = nblk == 1 ? q.slot / (long)n : 0;
+    if (!rc) rc = check_hip(hipMemcpy((char *)r.d_op + r.start_at, start, (no + 1) * 4, hipMemcpyHostToDevice), "hipMemcpy");
+    if (!rc) rc = check_hip(hipMemcpy((char *)r.d_op + r.term_at, h.term.data(), nt * sizeof(EnsObsTerm), hipMemcpyHostToDevice), "hipMemcpy");
+    if (!rc) rc = check_hip(hipMemcpy((char *)r.d_op + r.lterm_at, lterm.data(), nt * sizeof(EnsObsTerm), hipMemcpyHostToDevice), "hipMemcpy");
+    if (rc) {
+        ocn_ens::Recorder keep = std::move(e->rec);
+        e->rec = std::move(r);
+        ens_rec_free(e);
+        e->rec = std::move(keep);
+        return rc;
+    }
+    ens_rec_free(e);
+    r.active = true;
+    r.nobs = nobs; r.n = (int32_t)n; r.every = every; r.max_records = max_records;
+    r.use.assign(M, 0);
+    for (size_t i = 0; i < M; ++i) r.use[i] = (!use || use[i]) ? 1 : 0;
+    r.field = h.fields;
+    e->rec = std::move(r);
+    return OCN_OK;
+}
+
+int ocn_ens_record_end(ocn_ens *e)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    if (!e->rec.active) return set_error(OCN_ERR_STATE, "ens_record_end: no recorder (ocn_ens_record_begin)");
+    HIPCHK(hipSetDevice(e->device));
+    ens_rec_free(e);
+    return OCN_OK;
+}
+
+int ocn_ens_record_info(ocn_ens *e, ocn_ens_record_info_t *out)
+{
+    if (!e || !out) return set_error(OCN_ERR_ARG, "ens_record_info: null argument");
+    const ocn_ens::Recorder &r = e->rec;
+    *out = ocn_ens_record_info_t{r.active ? 1 : 0, r.nobs, r.n, r.every, r.max_records, 0, r.steps, (int64_t)r.records, r.in_launch};
+    return OCN_OK;
+}
+
+int ocn_ens_record_download(ocn_ens *e, int32_t first, int32_t count, double *host)
+{
+    if (!e || !host) return set_error(OCN_ERR_ARG, "ens_record_download: null argument");
+    const ocn_ens::Recorder &r = e->rec;
+    if (!r.active) return set_error(OCN_ERR_STATE, "ens_record_download: no recorder (ocn_ens_record_begin)");
+    if (first < 0 || count < 0 || (int64_t)first + count > r.records)
+        return set_error(OCN_ERR_ARG, "ens_record_download: a range outside the records taken");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const size_t rb = (size_t)r.nobs * (size_t)r.n * sizeof(double);
+    if (count) HIPCHK(hipMemcpy(host, (const char *)r.d_series + (size_t)first * rb, (size_t)count * rb, hipMemcpyDeviceToHost));
+    return OCN_OK;
+}
+
+// The stage of one recording call: `need` bytes in the copy whose turn it is, read by the stream no more.
+// Growing it waits for the device (rare: a call with more than 16 gathers after ocn_ens_record_begin).
+static int ens_rec_stage(ocn_ens *e, size_t need)
+{
+    ocn_ens::Recorder &r = e->rec;
+    if (need > r.stage_bytes) {
+        for (int i = 0; i < 2; ++i)
+            if (r.ev_set[i]) HIPCHK(hipEventSynchronize(r.ev[i]));
+        const size_t grown = (need + 65535) / 65536 * 65536;
+        void *d = nullptr, *h[2] = {nullptr, nullptr};
+        int rc = check_hip(hipMalloc(&d, grown), "hipMalloc");
+        for (int i = 0; i < 2 && !rc; ++i) rc = check_hip(hipHostMalloc(&h[i], grown, hipHostMallocDefault), "hipHostMalloc");
+        if (rc) {
+            if (d) (void)hipFree(d);
+            for (void *p : h)
+                if (p) (void)hipHostFree(p);
+            return rc;
+        }
+        (void)hipFree(r.d_stage);   // (waits for the launches that use it)
+        for (int i = 0; i < 2; ++i) { (void)hipHostFree(r.h_stage[i]); r.h_stage[i] = h[i]; r.ev_set[i] = false; }
+        r.d_stage = d;
+        r.stage_bytes = grown;
+    }
+    r.slot ^= 1;
+    if (r.ev_set[r.slot]) HIPCHK(hipEventSynchronize(r.ev[r.slot]));
+    return OCN_OK;
+}
+
+// record `index` gathered from the members in use as their field tables name the arrays now: the pointer table
+// at `at` of the call's stage up, then k_ens_sample_h into the record's slot.  No wait.
+static int ens_rec_gather(ocn_ens *e, const std::vector<ocn_ctx *> &in, int32_t index, size_t at)
+{
+    const ocn_ens::Recorder &r = e->rec;
+    ens_obs_table(in, r.field, (const double **)((char *)r.h_stage[r.slot] + at));
+    HIPCHK(hipMemcpyAsync((char *)r.d_stage + at, (const char *)r.h_stage[r.slot] + at, r.tab_b, hipMemcpyHostToDevice, e->stream));
+    const char *d = (const char *)r.d_op;
+    const EnsObsOp op{(const double *const *)((const char *)r.d_stage + at), (const int *)(d + r.start_at),
+                      (const EnsObsTerm *)(d + r.term_at)};
+    return launch_ens_sample_h(op, r.n, r.nobs, (double *)r.d_series + (size_t)index * (size_t)r.nobs * (size_t)r.n, e->stream);
+}
+
+int ocn_ens_step_record(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    ocn_ens::Recorder &r = e->rec;
+    if (!r.active) return set_error(OCN_ERR_STATE, "ens_step_record: no recorder (ocn_ens_record_begin)");
+    if (nsteps < 0) return set_error(OCN_ERR_ARG, "nsteps < 0");
+    for (const ocn_ctx *c : e->m)
+        if (!c->initialized) return set_error(OCN_ERR_STATE, "ocn_ctx_init_state not called");
+    std::vector<int32_t> due;
+    ens_record_due(r.steps, nsteps, r.every, due);
+    if ((int64_t)r.records + (int64_t)due.size() > r.max_records)
+        return set_error(OCN_ERR_ARG, "ens_step_record: the call's records would pass max_records");
+    if (nsteps == 0) return OCN_OK;
+    HIPCHK(hipSetDevice(e->device));
+    const int M = (int)e->m.size();
+    const std::vector<ocn_ctx *> in = ens_in_use(e, r.use.data());
+    int first = OCN_OK;
+    auto note = [&](int rc) { if (rc && !first) first = rc; };
+    const size_t mem_b = ((size_t)M * sizeof(EnsRecMember) + 255) / 256 * 256;
+
+    // In the launch only if every member in use would go in a recording launch -- known before any step of
+    // the call runs (a member that has stepped without its records cannot be repaired): each member says
+    // whether it would plan a multi-step launch (step_impl's probe), the planner whether it lands in a group
+    // under the recording capacity.  The call itself then plans the same way.
+    EnsRecCall rc_call{std::min<int64_t>(ens_capacity(e), onepass_multi_rec_capacity()), std::vector<int>((size_t)M, -1), 0, nullptr};
+    bool in_launch = e->rec_in_launch && nsteps >= 2 && e->m[0]->blocks.size() == 1;
+    if (in_launch) {
+        std::vector<int32_t> variant((size_t)M, -1);
+        for (int i = 0; i < M; ++i) {
+            ocn_ctx *c = e->m[(size_t)i];
+            c->ens_probe = true;
+            const int rc = guarded(c, "ocn_ens_step_record", [&] { return step_entry(c, tau, nsteps, check_every); });
+            c->ens_probe = false;
+            if (!rc) variant[(size_t)i] = ens_variant(c, tau, check_every == 1);
+            c->ens_pending = false;
+        }
+        std::vector<ocn_ens_group> groups;
+        if (ens_groups(e, variant, rc_call.capacity, groups)) in_launch = false;
+        std::vector<char> grouped((size_t)M, 0);
+        for (const ocn_ens_group &q : groups)
+            for (int j = 0; j < q.members; ++j) grouped[(size_t)q.member[j]] = 1;
+        for (int i = 0, col = 0; i < M; ++i) {
+            if (!r.use[(size_t)i]) continue;
+            rc_call.col[(size_t)i] = col++;
+            if (!grouped[(size_t)i]) in_launch = false;
+        }
+    }
+    if (in_launch) {
+        const bool tail = !due.empty() && due.back() == nsteps;
+        RC(ens_rec_stage(e, mem_b + (tail ? r.tab_b : 0)));
+        rc_call.due0 = due.empty() ? nsteps : due[0];   // (nsteps: nothing due inside the launch)
+        rc_call.slot0 = (double *)r.d_series + (size_t)r.records * (size_t)r.nobs * (size_t)r.n;
+        note(ens_step_run(e, tau, nsteps, check_every, &rc_call));
+        // the last step's record: no barrier behind it in the launch, so a gather behind the launch, from the
+        // tables after the host's role swap (the six state fields are current in an open sequence: no tail)
+        if (tail) note(ens_rec_gather(e, in, r.records + (int32_t)due.size() - 1, mem_b));
+        r.in_launch += (int64_t)due.size() - (tail ? 1 : 0);
+    } else {
+        // chunked: up to each due step a plain call, then a gather, all on the stream.
+        // A stretch is split further where check_every > 1 would lose its phase: the checks stay at the
+        // steps s of THIS call with s % check_every == 0
+        RC(ens_rec_stage(e, mem_b + due.size() * r.tab_b));
+        int32_t pos = 0;
+        for (size_t k = 0; k <= due.size() && pos < nsteps; ++k) {
+            const int32_t upto = k < due.size() ? due[k] : nsteps;
+            while (pos < upto) {
+                int32_t len = upto - pos, ce = check_every;
+                if (check_every > 1 && pos % check_every) {
+                    const int32_t to_check = check_every - pos % check_every;
+                    len = std::min(len, to_check);
+                    ce = len == to_check ? len : 0;
+                }
+                note(ens_step_run(e, tau, len, ce, nullptr));
+                pos += len;
+            }
+            if (k == due.size()) break;
+            // (the six state fields are current after any call, its tail pending or not -- the next call starts
+            // from them -- so the sequences stay open and the next call may be one launch; only steps that pair
+            // launches deferred are still to run: they run now, as the tail does)
+            int rt = OCN_OK;
+            for (ocn_ctx *c : in)
+                if (c->open && c->deferred)
+                    if (const int rq = guarded(c, "ocn_ens_step_record", [&] { return complete_open(c); }); rq && !rt) rt = rq;
+            note(rt);
+            note(ens_rec_gather(e, in, r.records + (int32_t)k, mem_b + k * r.tab_b));
+        }
+    }
+    HIPCHK(hipEventRecord(r.ev[r.slot], e->stream));
+    r.ev_set[r.slot] = true;
+    r.steps += nsteps;
+    r.records += (int32_t)due.size();
+    return first;
 }
 
 // bytes [at, at + bytes) of the last call's results into the pinned copy, with one wait

@@ -57,4 +57,12 @@ inline int ens_plan_groups(const ocn_block *g, const int32_t *variant, int membe
     return OCN_OK;
 }
 
+// The recorder's schedule (ocn_sw.h ocn_ens_record_due): the 1-based steps s of a call of nsteps steps, made
+// after `counted` counted steps, with (counted + s) % every == 0, in rising order
+inline void ens_record_due(int64_t counted, int32_t nsteps, int32_t every, std::vector<int32_t> &out)
+{
+    out.clear();
+    for (int64_t s = (int64_t)every - counted % every; s <= nsteps; s += every) out.push_back((int32_t)s);
+}
+
 }  // namespace ocn

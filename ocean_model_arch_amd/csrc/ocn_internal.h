@@ -218,6 +218,30 @@ size_t onepass_multi_b_entry_bytes();
 long onepass_multi_b_capacity();
 int launch_onepass_multi_b(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
                            int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, hipStream_t s);
+// launch_onepass_multi_b with a station recorder in the launch (sw_kernels.hip k_march_multi_rec; ocn_sw.h
+// ocn_ens_step_record): after each due step but the call's last, every member with a column >= 0 stores
+// H_j of its state into slot[j * n + col], j < nobs.  The operator is one table for all the members of the
+// launch (one block, one geometry): start as EnsObsOp's, term[t].slot the index of the term's field in
+// `field` (nfields of the six prognostic fields), term[t].off its element.  due0: the call's first due step
+// (1-based; beyond nsteps: none), then every `every` steps; slot0: the first due record's slot, the next
+// nobs * n doubles on.  h_mem / d_mem: pinned host and device memory for n EnsRecMember (the host copy is
+// read when the stream reaches the copy).  capacity: at most onepass_multi_rec_capacity().
+struct EnsObsTerm;
+struct EnsRecMember { const double *f[2][OCN_ENS_OBS_MAX_FIELDS]; int col, pad; };   // [parity of the steps done][field]
+struct EnsRecArgs {
+    const EnsRecMember *mem; const int *start; const EnsObsTerm *term;
+    double *slot0; int due0, every, nobs, n;
+};
+struct EnsRecLaunch {
+    const int *col; const int32_t *field; int nfields;
+    const int *d_start; const EnsObsTerm *d_term;
+    double *slot0; int due0, every, nobs, n;
+    EnsRecMember *h_mem, *d_mem;
+};
+long onepass_multi_rec_capacity();
+int launch_onepass_multi_rec(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
+                             int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, const EnsRecLaunch &rec,
+                             hipStream_t s);
 // Statistics over the members of an ensemble (ens_stats.hip; ocn_sw.h ocn_ens_stats): of the n arrays
 // src[0 .. n) (one field of one block geometry in member order, all with the lane of A(bnd_x1, :) in its
 // 256-B line that src[0] has) into out[0 .. 5) = mean, variance, spread, minimum, maximum (based like the

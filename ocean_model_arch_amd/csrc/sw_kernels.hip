@@ -3387,6 +3387,88 @@ __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_b(const E
     }
 }
 
+// k_march_multi_rec: k_march_multi_b's loop with a station recorder in it (ocn_sw.h ocn_ens_step_record).
+// After member_barrier of epoch s the member's state after step s is in memory and visible to this
+// workgroup: every tile stored it write-through, every wave drained its stores (vmcnt(0)) before it arrived,
+// and the barrier ends in an agent-scope acquire and __syncthreads -- what the next step's halo columns rely
+// on.  If step s is due, the member's workgroups share the operator's rows; a row's value is the ordered sum
+// of ens_assim.hip obs_apply (the same operations in the same order, -ffp-contract=off: the same bits),
+// its terms read with ordinary per-lane loads issued after the barrier (never the scalar path or the
+// constant address space: the kernel writes these buffers) and stored into the member's column of the
+// record's slot with a plain store.  After an even number of steps the state is in the buffers of the
+// member's field table (f[0]), after an odd number in those of the odd steps' table (f[1]: the role pairs
+// swapped, the *p levels in the second buffers).
+// No race, in this order: step s + 1 writes only the other buffer of each pair (the SSHN role and the
+// second *p buffers), never the buffers that hold state s; step s + 2 does write them, but no workgroup
+// begins step s + 2 before THIS workgroup has arrived at barrier s + 1, and that barrier's vmcnt(0) retires
+// this workgroup's record loads first.  So the loads sit between barrier s and this workgroup's arrival at
+// barrier s + 1, and state s is intact all that time.
+// The call's last step has no barrier behind it: its record is taken by a gather launch behind this one.
+// The members' tables (EnsRecMember: 2 x 4 base pointers and the column, -1 for a member not in use) are
+// written by a copy ordered before the launch and never by the kernel: scalar loads, as EnsEntry.  No
+// atomics, LDS or inline assembly beyond the barrier's; no scratch (a term's base pointer is picked by a
+// select chain, not by a dynamic index).
+__device__ __forceinline__ double rec_apply(const double *f0, const double *f1, const double *f2, const double *f3,
+                                            const int *start, const EnsObsTerm *term, int j)
+{
+    constexpr int kGroup = 4;   // (ens_assim.hip kObsGroup)
+    const int t0 = start[j], t1 = start[j + 1];
+    double s = 0.0;
+    for (int t = t0; t < t1; t += kGroup) {
+        double x[kGroup], w[kGroup];
+#pragma unroll
+        for (int e = 0; e < kGroup; ++e)
+            if (t + e < t1) {
+                const EnsObsTerm q = term[t + e];
+                const double *p = q.slot == 0 ? f0 : q.slot == 1 ? f1 : q.slot == 2 ? f2 : f3;
+                x[e] = p[q.off];
+                w[e] = q.w;
+            }
+#pragma unroll
+        for (int e = 0; e < kGroup; ++e)
+            if (t + e < t1) {
+                const double p = x[e] * w[e];
+                s = t + e == t0 ? p : s + p;
+            }
+    }
+    return s;
+}
+
+template <class Body>
+__global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_rec(const EnsEntry<Body> *__restrict__ tab, int tiles,
+                                                                           int nsteps, const EnsRecArgs rec)
+{
+    typedef const EnsEntry<Body> __attribute__((address_space(4))) *ConstTab;
+    typedef const EnsRecMember __attribute__((address_space(4))) *ConstRec;
+    const int mem = __builtin_amdgcn_readfirstlane((int)blockIdx.x / tiles);
+    const int tile = (int)blockIdx.x - mem * tiles;
+    ConstTab e = (ConstTab)tab + mem;
+    ConstRec rm = (ConstRec)rec.mem + mem;
+    const MarchRect R = *(const MarchRect *)&e->R;
+    unsigned *const bar = e->bar;
+    int32_t *const err = e->err;
+    const int spin = e->spin;
+    const int col = rm->col;
+    long due = rec.due0;          // the next due step of this call, 1-based
+    double *slot = rec.slot0;     // its record's slot
+    if constexpr (HasPrologue<Body>::v) ((const Body *)&e->b[0])->prologue(R, tile / R.ntx);   // the same rows every step
+    for (int s = 0; s < nsteps; ++s) {
+        march_tile<Body, false>(R, tile, *(const Body *)&e->b[__builtin_amdgcn_readfirstlane(s & 1)]);
+        if (s + 1 == nsteps) break;
+        if (!member_barrier(bar, (unsigned)tiles, (unsigned)tile, (unsigned)(s + 1), err, spin)) return;
+        if (s + 1 != due) continue;
+        if (col >= 0) {   // state s + 1, in the table of its parity
+            const int par = __builtin_amdgcn_readfirstlane((s + 1) & 1);
+            const double *const f0 = rm->f[par][0], *const f1 = rm->f[par][1], *const f2 = rm->f[par][2],
+                         *const f3 = rm->f[par][3];
+            for (int j = tile * 256 + (int)threadIdx.x; j < rec.nobs; j += tiles * 256)
+                slot[(long)j * rec.n + col] = rec_apply(f0, f1, f2, f3, rec.start, rec.term, j);
+        }
+        due += rec.every;
+        slot += (long)rec.nobs * rec.n;
+    }
+}
+
 // the variant of a member's launch as the planner's id: 2 x (0 known-constant, 1 h_r-read, 2 general)
 // + (tau a power of two), + 6 with the per-step check; -1: no variant chosen on the host
 int onepass_multi_variant(int kc_mode, double tau, bool check)
@@ -3441,8 +3523,34 @@ long onepass_multi_b_capacity()
     return cap[dev] = c;
 }
 
-int launch_onepass_multi_b(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
-                           int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, hipStream_t s)
+// the resident capacity of the recording launch: onepass_multi_b_capacity() and the recording kernels' own
+// occupancy x CUs (kept apart: folding it into the other would change the plans of calls that record nothing)
+long onepass_multi_rec_capacity()
+{
+    static std::mutex mu;
+    static std::map<int, long> cap;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    long c = onepass_multi_b_capacity();
+    std::lock_guard<std::mutex> g(mu);
+    const auto it = cap.find(dev);
+    if (it != cap.end()) return it->second;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) c = 0;
+    for (int v = 0; v < 6; ++v)
+        multi_b_dispatch(v, [&](auto b) {
+            int per = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_march_multi_rec<typename decltype(b)::type>, 256, 0) != hipSuccess)
+                per = 0;
+            c = std::min(c, (long)per * cus);
+            return 0;
+        });
+    return cap[dev] = c;
+}
+
+// launch_onepass_multi_b (rec null) and launch_onepass_multi_rec behind their checks: one table of entries, one launch
+static int launch_multi_b_impl(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
+                               int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, const EnsRecLaunch *rec,
+                               hipStream_t s)
 {
     if (!m || n < 1 || variant < 0 || variant >= 12 || rows < 1 || rows > 16 || nsteps < 1 || !d_tab || !h_tab)
         return set_error(OCN_ERR_ARG, "ensemble launch: members, a variant, 1..16 rows, a table");
@@ -3489,14 +3597,60 @@ int launch_onepass_multi_b(const EnsMember *m, int n, int variant, int rows, con
             tiles = tab[i].R.tiles;
         }
         // residency from the grid size alone, as the single-member launch: every workgroup at once
-        if ((long)n * tiles > capacity || capacity > onepass_multi_b_capacity())
+        if ((long)n * tiles > capacity || capacity > (rec ? onepass_multi_rec_capacity() : onepass_multi_b_capacity()))
             return set_error(OCN_ERR_ARG, "ensemble launch: grid larger than the resident capacity");
+        EnsRecArgs ra{};
+        if (rec) {   // the recorder's tables: per member the operator's fields in both parities' buffers, and the column
+            for (int i = 0; i < n; ++i) {
+                const EnsMember &e = m[i];
+                std::vector<void *> odd(e.ptr, e.ptr + e.nptr);   // (as above)
+                for (const auto &pr : {std::make_pair(OCN_SSH, OCN_SSHN), std::make_pair(OCN_UBRTR, OCN_UBRTRN),
+                                       std::make_pair(OCN_VBRTR, OCN_VBRTRN)})
+                    std::swap(odd[ocn_field_slot(pr.first)], odd[ocn_field_slot(pr.second)]);
+                const int ids[3] = {OCN_SSHP, OCN_UBRTRP, OCN_VBRTRP};
+                for (int j = 0; j < 3; ++j) odd[ocn_field_slot(ids[j])] = e.alt[j];
+                EnsRecMember &q = rec->h_mem[i];
+                for (int f = 0; f < OCN_ENS_OBS_MAX_FIELDS; ++f) {   // (unused entries: the first field's, never read)
+                    const int slot = ocn_field_slot(rec->field[f < rec->nfields ? f : 0]);
+                    q.f[0][f] = (const double *)e.ptr[slot];
+                    q.f[1][f] = (const double *)odd[slot];
+                }
+                q.col = rec->col[i];
+                q.pad = 0;
+            }
+            RC_K(check_hip(hipMemcpyAsync(rec->d_mem, rec->h_mem, sizeof(EnsRecMember) * (size_t)n, hipMemcpyHostToDevice, s),
+                           "ensemble launch: recorder table"));
+            ra = EnsRecArgs{rec->d_mem, rec->d_start, rec->d_term, rec->slot0, rec->due0, rec->every, rec->nobs, rec->n};
+        }
         RC_K(check_hip(hipMemcpyAsync(d_tab, h_tab, sizeof(Entry) * (size_t)n, hipMemcpyHostToDevice, s),
                        "ensemble launch: member table"));
         count_launch();
-        k_march_multi_b<Body><<<dim3((unsigned)(n * tiles)), dim3(256), 0, s>>>((const Entry *)d_tab, tiles, nsteps);
+        if (rec)
+            k_march_multi_rec<Body><<<dim3((unsigned)(n * tiles)), dim3(256), 0, s>>>((const Entry *)d_tab, tiles, nsteps, ra);
+        else
+            k_march_multi_b<Body><<<dim3((unsigned)(n * tiles)), dim3(256), 0, s>>>((const Entry *)d_tab, tiles, nsteps);
         return check_hip(hipGetLastError(), "ensemble launch");
     });
+}
+
+int launch_onepass_multi_b(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
+                           int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, hipStream_t s)
+{
+    return launch_multi_b_impl(m, n, variant, rows, sw, tau, nsteps, d_tab, h_tab, tab_bytes, capacity, nullptr, s);
+}
+
+int launch_onepass_multi_rec(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
+                             int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, const EnsRecLaunch &rec,
+                             hipStream_t s)
+{
+    if (!rec.col || !rec.field || rec.nfields < 1 || rec.nfields > OCN_ENS_OBS_MAX_FIELDS || !rec.d_start || !rec.d_term ||
+        !rec.slot0 || rec.due0 < 1 || rec.every < 1 || rec.nobs < 1 || rec.n < 1 || !rec.h_mem || !rec.d_mem)
+        return set_error(OCN_ERR_ARG, "ensemble launch: the recorder's tables, schedule or slot");
+    for (int f = 0; f < rec.nfields; ++f)
+        if (rec.field[f] != OCN_SSH && rec.field[f] != OCN_SSHP && rec.field[f] != OCN_UBRTR && rec.field[f] != OCN_UBRTRP &&
+            rec.field[f] != OCN_VBRTR && rec.field[f] != OCN_VBRTRP)
+            return set_error(OCN_ERR_ARG, "ensemble launch: the recorder reads the six prognostic fields only");
+    return launch_multi_b_impl(m, n, variant, rows, sw, tau, nsteps, d_tab, h_tab, tab_bytes, capacity, &rec, s);
 }
 
 // Rows per workgroup tile of the two-step launch: the fewest iterations in total, counting

@@ -12,7 +12,7 @@ import operator
 
 import numpy as np
 
-from . import _lib, ens_local_rule, ens_obs_rule, ens_perturb_rule
+from . import _lib, ens_local_rule, ens_obs_rule, ens_perturb_rule, ens_record_rule
 from ._lib import check, lib
 from .config import BasinConfig, ParallelConfig, SWConfig
 from .model import BlockInfo, OceanModel
@@ -114,6 +114,8 @@ class OceanEnsemble:
 
     def close(self):
         if getattr(self, "ens", None):
+            if getattr(self, "_recording", False):
+                self.record_end()
             for m in self.members:
                 m.close()
             lib().ocn_ens_destroy(self.ens)
@@ -612,6 +614,78 @@ class OceanEnsemble:
             out["nonfinite"] = int(info.nonfinite)
             return out
         return finish if defer else finish()
+
+    # ------------------------------------------------------------ station time series
+    def record(self, op, every: int = 1, max_records: int = 1024, members=None):
+        """Start recording station time series (ocn_ens_record_begin): after every `every`-th step counted by
+        step_record() the sparse linear operator `op` (ens_obs_rule.ObsOperator, as sample_h() takes it, its
+        terms over ssh, sshp, ubrtr, ubrtrp, vbrtr, vbrtrp only) is applied to the members in use (`members`:
+        indices; None: all) and the (nobs, n) values become the next record, up to `max_records` of them, in
+        a buffer on the device.  An earlier recorder is replaced.  TypeError for an argument of the wrong type,
+        ValueError for one out of range."""
+        arrays = self._op_arrays(op)
+        for what, v in (("every", every), ("max_records", max_records)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"record: {what} = {v!r}, not an integer")
+        ens_record_rule.check(every, max_records)
+        n = self._count(members)
+        if max_records * op.nobs * n * 8 > ens_record_rule.MAX_SERIES_BYTES:
+            raise ValueError(f"record: {max_records} records of {op.nobs} x {n} doubles, a series above 1 GiB")
+        check(lib().ocn_ens_record_begin(self.ens, self._use(members), op.nobs, *[a.ctypes.data_as(C.c_void_p) for a in arrays],
+                                         int(every), int(max_records)), "ocn_ens_record_begin")
+        self._recording = True
+        return self
+
+    def step_record(self, nsteps: int = 1, tau: float = 1.0, check_every: int = 1):
+        """step() with the recorder on (ocn_ens_step_record): the members end up exactly as after
+        step(nsteps, tau, check_every), and every record that falls due in these steps is written on the way --
+        by the marching launch itself where the call is one (record_info()["in_launch"]), else by a gather
+        launch behind each stretch of steps.  No host wait.  Plain step() calls neither count nor record."""
+        if isinstance(nsteps, bool) or not isinstance(nsteps, (int, np.integer)):
+            raise TypeError(f"step_record: nsteps = {nsteps!r}, not an integer")
+        if nsteps < 0:
+            raise ValueError(f"step_record: nsteps = {nsteps} < 0")
+        check(lib().ocn_ens_step_record(self.ens, tau, int(nsteps), check_every), "ocn_ens_step_record")
+        return self
+
+    def record_info(self) -> dict:
+        """The recorder: active, nobs, n, every, max_records, steps counted, records taken, and in_launch, the
+        records a marching launch wrote itself (cumulative)."""
+        i = _lib.OcnEnsRecordInfo()
+        check(lib().ocn_ens_record_info(self.ens, C.byref(i)), "ocn_ens_record_info")
+        return {"active": bool(i.active), "nobs": int(i.nobs), "n": int(i.n), "every": int(i.every),
+                "max_records": int(i.max_records), "steps": int(i.steps), "records": int(i.records),
+                "in_launch": int(i.in_launch)}
+
+    def series(self, first: int = 0, count=None) -> np.ndarray:
+        """Records first .. first + count - 1 (count None: all from `first`) as a float64 array
+        (records, nobs, n), column m the m-th member in use in member order (ocn_ens_record_download: one wait).
+        ValueError for a range outside the records taken."""
+        for what, v in (("first", first), ("count", 0 if count is None else count)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"series: {what} = {v!r}, not an integer")
+        info = self.record_info()
+        if not info["active"]:
+            raise _lib.OcnError(_lib.OCN_ERR_STATE, "series: no recorder (record())")
+        count = info["records"] - first if count is None else count
+        if first < 0 or count < 0 or first + count > info["records"]:
+            raise ValueError(f"series: records {first} .. {first + count - 1} of {info['records']} taken")
+        out = np.zeros((count, info["nobs"], info["n"]), dtype=np.float64)
+        if count:
+            check(lib().ocn_ens_record_download(self.ens, int(first), int(count), out.ctypes.data_as(C.c_void_p)),
+                  "ocn_ens_record_download")
+        return out
+
+    def record_end(self):
+        """Stop recording and free the series (ocn_ens_record_end)."""
+        self._recording = False
+        check(lib().ocn_ens_record_end(self.ens), "ocn_ens_record_end")
+        return self
+
+    def set_record_in_launch(self, on: bool = True):
+        """Tests and measurements: off, step_record() always takes the chunked route."""
+        check(lib().ocn_ens_set_option(self.ens, _lib.ENS_OPT_RECORD_IN_LAUNCH, int(bool(on))), "ocn_ens_set_option")
+        return self
 
     def set_assim_timing(self, on: bool = True):
         """Measurements: assimilate(device=True) records events around its two stages (assimilate_spans)."""
