@@ -976,6 +976,23 @@ const char *ocn_build_id(void);
  * between buffers not included): a host takes differences around a region to count launches. */
 int64_t ocn_launch_count(void);
 
+/* The two-step launch's tile plan (pure, no device, as ocn_ens_plan; the function the launches themselves
+ * call): a range of width x height points is cut into workgroup tiles of 116 columns and *rows rows; a
+ * tile's workgroup passes *rows + 8 iterations, the chip holds 512 workgroups of it at once, and `mult`
+ * ranges of this size share one launch (a batch of blocks).  The plan is the tile height with the fewest
+ * iterations in total, *iterations = *rounds x (*rows + 8), among 8 .. 150 rows (what the workgroup's LDS
+ * table of row constants holds); the smallest such height is taken.  nv != 0 asks for the plan of the
+ * inviscid bodies (OCN_OPT_INVISCID): today the same one, they share the cap.  A fixed height
+ * (ocn_set_pair_rows) replaces the search, clipped to the cap.
+ * OCN_ERR_ARG for a size or mult below 1 or a null output pointer. */
+int ocn_pair_plan(int width, int height, int mult, int nv, int *rows, int *rounds, int *iterations);
+/* A fixed tile height for every two-step launch of the process from now on, clipped to the cap of 150
+ * rows; 0 = automatic (ocn_pair_plan's search).  The environment variable OCN_PAIR_ROWS, read when
+ * the library is loaded, is its initial value (a value below 8 there counts as 0).  A tuning and testing
+ * aid, not a context option: it takes effect for launches issued after the call, and a step captured as a
+ * graph is captured again under a new height.  OCN_ERR_ARG for a negative value or 1 .. 7. */
+int ocn_set_pair_rows(int rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,7 +101,7 @@ CTX_SYMBOLS = ["ocn_decompose", "ocn_halo_schedule", "ocn_ctx_create", "ocn_ctx_
                "ocn_ctx_set_topography", "ocn_ctx_init_state", "ocn_ctx_sync", "ocn_ctx_stage", "ocn_ctx_tracer_stage", "ocn_ctx_step", "ocn_ctx_synchronize",
                "ocn_ctx_download", "ocn_ctx_complete", "ocn_ctx_upload", "ocn_ctx_output_r4", "ocn_ctx_set_option", "ocn_ctx_get_option", "ocn_ctx_stage_times", "ocn_ctx_stage_stats",
                "ocn_ctx_comm_info", "ocn_ctx_overlap_info", "ocn_ctx_clock_info", "ocn_ctx_set_watchdog", "ocn_last_error", "ocn_abi_version",
-               "ocn_build_id", "ocn_launch_count"]
+               "ocn_build_id", "ocn_launch_count", "ocn_pair_plan", "ocn_set_pair_rows"]
 ENS_SYMBOLS = ["ocn_ens_plan", "ocn_ens_create", "ocn_ens_destroy", "ocn_ens_size", "ocn_ens_member",
                "ocn_ens_init_state", "ocn_ens_step", "ocn_ens_complete", "ocn_ens_synchronize", "ocn_ens_info",
                "ocn_ens_set_option", "ocn_ens_stats", "ocn_ens_stats_download", "ocn_ens_stats_output_r4",
@@ -324,6 +324,9 @@ def lib() -> C.CDLL:
     L.ocn_ens_record_download.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     L.ocn_ens_record_end.argtypes = [C.c_void_p]
     L.ocn_ens_record_due.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
+    L.ocn_pair_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                C.POINTER(C.c_int)]
+    L.ocn_set_pair_rows.argtypes = [C.c_int]
     _lib = L
     return L
 
@@ -336,6 +339,21 @@ def build_id() -> str:
 def launch_count() -> int:
     """ocn_launch_count(): kernel launches issued through the library by this process so far."""
     return int(lib().ocn_launch_count())
+
+
+def pair_plan(width: int, height: int, mult: int = 1, nv: bool = True) -> tuple[int, int, int]:
+    """ocn_pair_plan (pure, no device): (rows, rounds, iterations) of the two-step launch over a
+    width x height range; nv = for the inviscid bodies (today the same plan: they share the cap)."""
+    rows, rounds, its = C.c_int(), C.c_int(), C.c_int()
+    check(lib().ocn_pair_plan(int(width), int(height), int(mult), int(bool(nv)), C.byref(rows), C.byref(rounds),
+                              C.byref(its)), "ocn_pair_plan")
+    return rows.value, rounds.value, its.value
+
+
+def set_pair_rows(rows: int = 0) -> None:
+    """ocn_set_pair_rows: a fixed tile height for the process's two-step launches from now on, clipped
+    to the cap of 150 rows; 0 = automatic."""
+    check(lib().ocn_set_pair_rows(int(rows)), "ocn_set_pair_rows")
 
 
 def check(rc: int, what: str = ""):

@@ -219,7 +219,7 @@ struct ocn_ctx {
     bool use_graph = false;
     // the launches a captured step replays depend on everything in its key (march and ring_sea
     // select launch forms and the ring launch; options that change them also drop the cache)
-    struct Graph { hipGraphExec_t exec; double tau; ocn::StepKind kind; bool compact, march, ring_sea; int role, kc_mode; bool kc_nv; };
+    struct Graph { hipGraphExec_t exec; double tau; ocn::StepKind kind; bool compact, march, ring_sea; int role, kc_mode; bool kc_nv; int pair_rows; };
     std::vector<Graph> graphs;         // one captured step per key
     std::vector<void *> allocs;
     // per-stage HIP-event timing (OCN_OPT_STAGE_TIMING): pending (stage, start, stop) records

@@ -1857,7 +1857,7 @@ extern "C++" int ocn::run_step(ocn_ctx *c, double tau, const StepKind &k)
 }
 
 // one step as a replayed hipGraph, captured once per (tau, step kind, compact, role, one-pass
-// variant); a role-flip step swaps the host's pointer roles as the captured launches did.  The
+// variant, fixed two-step tile height); a role-flip step swaps the host's pointer roles as the captured launches did.  The
 // known-constant variant's constants and the device check's verdict are read from device memory
 // by the launches, so a replay sees their current values.
 static int graph_step(ocn_ctx *c, double tau, const StepKind &k)
@@ -1865,7 +1865,7 @@ static int graph_step(ocn_ctx *c, double tau, const StepKind &k)
     c->hn_fresh = false;   // (a replay runs whatever the captured step ran)
     for (const auto &g : c->graphs)
         if (g.tau == tau && g.kind == k && g.compact == c->compact && g.march == c->march && g.ring_sea == c->ring_sea &&
-            g.role == c->role && g.kc_mode == c->kc_mode && g.kc_nv == c->kc_nv) {
+            g.role == c->role && g.kc_mode == c->kc_mode && g.kc_nv == c->kc_nv && g.pair_rows == pair_rows_fixed()) {
             HIPCHK(hipGraphLaunch(g.exec, c->stream));
             if (k.rc) swap_sshp(c);
             if (k.one || k.one_last) swap_alt3(c);
@@ -1886,7 +1886,8 @@ static int graph_step(ocn_ctx *c, double tau, const StepKind &k)
     e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     HIPCHK(e);
-    c->graphs.push_back(ocn_ctx::Graph{exec, tau, k, c->compact, c->march, c->ring_sea, role, c->kc_mode, c->kc_nv});
+    c->graphs.push_back(ocn_ctx::Graph{exec, tau, k, c->compact, c->march, c->ring_sea, role, c->kc_mode, c->kc_nv,
+                                        pair_rows_fixed()});
     HIPCHK(hipGraphLaunch(exec, c->stream));
     return OCN_OK;
 }

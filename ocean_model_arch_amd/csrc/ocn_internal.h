@@ -150,6 +150,8 @@ int launch_onepass(const ocn_block *b, void *const *ptr, int nptr, const Compact
                    double tau, int32_t *nbad, double *sshp_out, double *up_out, double *vp_out, hipStream_t s,
                    const Range *range, bool last, const OnepassKC &kc, unsigned own = 0,
                    const Range *frame_of = nullptr);
+// the two-step launches' fixed tile height in force (ocn_set_pair_rows / OCN_PAIR_ROWS; 0: automatic)
+int pair_rows_fixed();
 // Two one-pass steps in one launch (sw_kernels.hip MarchStep PAIR): single block, no exchange,
 // a variant chosen on the host (kc.mode OCN_KC_KNOWN / OCN_KC_KNOWN_HR / OCN_KC_GENERAL); reads the state where a single step reads it and writes the second step's new state where
 // a single step writes (one role flip); nbad1 / nbad2: the steps' check_ssh_err counts (null: none)

@@ -21,6 +21,8 @@
 // per array.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
@@ -1758,6 +1760,9 @@ __device__ __forceinline__ void exp_check(int &acc, double x)
     acc = min(acc, __builtin_amdgcn_frexp_exp(x));
 }
 constexpr int kUdivMinExp = -899;   // frexp exponent >= -899  <=>  |x| >= 2^-900
+// a marked lane's start value of the range-check accumulator (StepRegs::mark): below every frexp exponent, so the
+// minimum over a row's dividends stays below kUdivMinExp whatever they are
+constexpr int kGuardMark = -0x40000000;
 
 // The row-uniform operands of the one-pass step, per row r, as the doubles the arithmetic uses
 // (each formed exactly as the step forms it from the real(4) row table: promoted metrics, the
@@ -1786,6 +1791,8 @@ __shared__ unsigned g_step_rlo;                       // table row of its first 
 // out; their exact re-run forms those from scalar loads of the row table (StepRegs::cst<0>)
 constexpr int kRowCNV = 17;
 constexpr int nv_col(int k) { return k <= RC_RDYB ? k : k == RC_RLH ? 14 : k == RC_AREA ? 15 : k == RC_RAREA ? 16 : -1; }
+// (Measured and dropped: a row capacity of its own, 300 + 10 rows at 17 columns -- 4096^2 in one round of 504
+// workgroups of 293 rows instead of two rounds of 147: 0.8-0.9 % of the 100-step bench line, nothing in the 20-step one.)
 __shared__ double g_step_rc_nv[kStepLdsRows * kRowCNV];
 // Two steps per launch (MarchStep PAIR): the producer waves' new state (ssh, sshp, ubrtr, ubrtrp,
 // vbrtr, vbrtrp after the first step, by row mod 4) for the consumer waves.
@@ -1890,7 +1897,7 @@ struct StepRegs {
     int32_t *nbp;                      // where this wave's check_ssh_err count goes (null: unchecked)
     bool cnt;                          // the point is counted (PAIR producers: their workgroup's points only)
     int pj;                            // PAIR: the lane's column in the workgroup's LDS ring
-    bool big;                          // NV: a state value this lane took was not below 2^300 (MarchStep::guard)
+    int mark;                          // NV: 0, or kGuardMark once a state value this lane took was not below 2^300 (MarchStep::guard)
     double fyx, fyy, vht, a2t;         // row n-1's n faces (MarchStep::face)
     double hr0, mu0;                   // known-constant variant: the uniform h_r and mu (MarchStep::kc)
     const __attribute__((address_space(3))) double *lds;   // (kLds) the workgroup's row constants
@@ -2023,11 +2030,18 @@ struct StepRegs {
 // rows n-1 .. n+2, h_r and the metrics (finite, their ratios finite: launch_prepare); with the state
 // and h_r below 2^300 in magnitude all of them are finite.  A wave sums the six |x| of every row it
 // takes (take: from memory or from the ring; NaN and inf propagate through the sum) and compares
-// once; a failing lane stays failed for the rest of the tile (StepRegs::big), and its wave then runs
-// each row again in full as the full body runs it (iteration: step<false, PH, true> -- udiv with all
-// its range checks, derive's dropped checks too -- then the IEEE re-run if they ask for it), the
+// once; a failing lane stays failed for the rest of the tile: its StepRegs::mark becomes kGuardMark,
+// an int below every frexp exponent, and the range-check accumulators of derive and step start from
+// the mark instead of 0 (every exp_check is a min), so the hot path has the one ballot per half row
+// it had without the guard -- no flag, no second ballot operand.  Inside the unlikely branch a second
+// ballot (mark != 0) tells the two causes apart.  A marked wave runs each row again in full as the
+// full body runs it (iteration: derive<false> again with its accumulator from 0 and the stresses'
+// three dropped checks added, step<false, PH, true, true> -- udiv with all its range checks -- then
+// the IEEE re-run only if those checks ask for it; RE = true in both, so that check_ssh_err's count
+// of the first pass is corrected, not added to), the
 // stresses formed again from the state ring (viscous): nothing is carried from rows of the short
-// form.  The same full IEEE re-run (step<true>) serves a kept dividend out of udiv's range.  Why udiv
+// form.  An unmarked wave takes the full IEEE re-run (derive<true>, step<true>) directly: a kept
+// dividend of its own was out of udiv's range.  Why udiv
 // first: udiv of an infinite dividend is NaN where the IEEE quotient is infinite, so a marked wave
 // must divide as the full body does for the two to agree byte for byte on non-finite state.
 // Dropping the range checks of the dropped dividends changes no kept value on finite state: udiv
@@ -2117,14 +2131,16 @@ struct MarchStepT {
         if constexpr (NV) guard(x, q.u, q.up, q.ssh, q.shp, q.v, q.vp, q.hr);
     }
     // NV: the row's state (and h_r where it is read) finite and below 2^300, or the lane is marked for
-    // good (see MarchStep) -- the sum of the magnitudes: inf and NaN propagate, one compare
+    // good (see MarchStep) -- the sum of the magnitudes: inf and NaN propagate, one compare, one select.
+    // The mark is the int the rows' range-check accumulators start from (iteration): no flag of its own is
+    // tested on the hot path
     __device__ __forceinline__ static void guard(StepRegs &x, double a, double b, double c, double d, double e, double f,
                                                  double hr)
     {
         double s = __builtin_fabs(a) + __builtin_fabs(b) + __builtin_fabs(c) + __builtin_fabs(d) + __builtin_fabs(e) +
                    __builtin_fabs(f);
         if (HR) s += __builtin_fabs(hr);
-        x.big = x.big || !(s < 0x1p300);
+        x.mark = s < 0x1p300 ? x.mark : kGuardMark;
     }
 
     // hh_init's interpolation weights of row n + dy (slot dy + 1): interp_wt(h) = h * dx * dy * lu
@@ -2685,7 +2701,7 @@ struct MarchStepT {
             x.hr.s<0>(2) = ZF && !HR ? x.hr0 : ld(t.f(OCN_HHQ_REST), c1);
             x.bits.s<0>(2) = ld(t.bits, c1);
             if constexpr (NV) {   // these rows' part in the guard (the uniform h_r once)
-                x.big = !HR && !(__builtin_fabs(x.hr0) < 0x1p300);
+                x.mark = !HR && !(__builtin_fabs(x.hr0) < 0x1p300) ? kGuardMark : 0;
                 guard(x, x.up.s<0>(2), x.ssh.s<0>(2), x.shp.s<0>(2), x.u.s<0>(2), x.vp.s<0>(1), 0.0, x.hr.s<0>(2));
             }
         }
@@ -2763,36 +2779,41 @@ struct MarchStepT {
         if (n < ne) load<RO>(x, q, L.m, n + 1);   // in flight while this row is computed
         Out o;
         {
-            int acc = 0;
+            // NV: the accumulator starts from the lane's mark (guard), so the one ballot below fires for a dividend
+            // out of udiv's range and for a marked wave alike; the two are told apart inside the unlikely branch
+            int acc = NV ? x.mark : 0;
             double qb, qc;
             derive<false, PH>(x, fb, acc, qb, qc);
             bool again = __builtin_amdgcn_ballot_w64(acc < kUdivMinExp) != 0;
-            if constexpr (NV) {   // a marked wave (guard): the range checks of the stresses' dividends too, so that
-                // it re-runs the rows the full body re-runs
-                if (__builtin_expect(!again && __builtin_amdgcn_ballot_w64(x.big) != 0, 0)) {
-                    int a5 = 0;
-                    exp_check(a5, x.up.s<PH>(2)); exp_check(a5, x.vp.s<PH>(2)); exp_check(a5, x.up.s<PH>(3));
-                    again = __builtin_amdgcn_ballot_w64(a5 < kUdivMinExp) != 0;
+            if (__builtin_expect(again, 0)) {
+                if constexpr (NV) {   // a marked wave: its own range checks again from 0, and those of the stresses'
+                    // dividends too, so that it re-runs the rows the full body re-runs
+                    if (__builtin_amdgcn_ballot_w64(x.mark != 0) != 0) {
+                        acc = 0;
+                        derive<false, PH>(x, fb, acc, qb, qc);
+                        exp_check(acc, x.up.s<PH>(2)); exp_check(acc, x.vp.s<PH>(2)); exp_check(acc, x.up.s<PH>(3));
+                        again = __builtin_amdgcn_ballot_w64(acc < kUdivMinExp) != 0;
+                    }
                 }
+                if (again) derive<true, PH>(x, fb, acc, qb, qc);
             }
-            if (__builtin_expect(again, 0))
-                derive<true, PH>(x, fb, acc, qb, qc);
-            acc = 0;
+            acc = NV ? x.mark : 0;
             if (WARM) {
                 if (n == nb - 1) face<PH>(x);
             } else {
                 bool bad = false;
                 step<false, PH, false>(x, L, n, acc, bad, o);
                 bool exact = __builtin_amdgcn_ballot_w64(acc < kUdivMinExp) != 0;
-                if constexpr (NV) {   // a marked wave: the row again in full, as the full body runs it (udiv, its checks)
-                    if (__builtin_expect(!exact && __builtin_amdgcn_ballot_w64(x.big) != 0, 0)) {
-                        acc = 0;
-                        step<false, PH, true, true>(x, L, n, acc, bad, o);
-                        exact = __builtin_amdgcn_ballot_w64(acc < kUdivMinExp) != 0;
+                if (__builtin_expect(exact, 0)) {
+                    if constexpr (NV) {   // a marked wave: the row again in full, as the full body runs it (udiv, its checks)
+                        if (__builtin_amdgcn_ballot_w64(x.mark != 0) != 0) {
+                            acc = 0;
+                            step<false, PH, true, true>(x, L, n, acc, bad, o);
+                            exact = __builtin_amdgcn_ballot_w64(acc < kUdivMinExp) != 0;
+                        }
                     }
+                    if (exact) step<true, PH, true>(x, L, n, acc, bad, o);
                 }
-                if (__builtin_expect(exact, 0))
-                    step<true, PH, true>(x, L, n, acc, bad, o);
                 x.fyx = o.fyx;
                 x.fyy = o.fyy;
                 x.vht = o.vht;
@@ -3658,25 +3679,43 @@ int launch_onepass_multi_rec(const EnsMember *m, int n, int variant, int rows, c
 // size in one launch (a batch: one_step_x4 on several blocks of a device)
 // wave slots of the chip for the two-step launch: 256 CUs x 4 SIMDs x its waves per SIMD
 constexpr long kPairSlots = 256L * 4L * OCN_PAIR_WAVES;
-static int pair_rows(const Range &r, int cols, int mult = 1)
+constexpr int kPairColsHost = MarchStep<true, false, true, false, false, true>::kPairCols;
+// a fixed tile height (0: automatic), process-wide: OCN_PAIR_ROWS as its initial value (read once, at load -- not
+// a libc call per launch), ocn_set_pair_rows after that; a launch clips it to the cap (OCN_PAIR_MAX_ROWS)
+static std::atomic<int> g_pair_rows_fixed{[] {
+    const char *e = getenv("OCN_PAIR_ROWS");
+    const int v = e ? atoi(e) : 0;
+    return v >= 8 ? v : 0;
+}()};
+// The plan for a range of width x height points (pure host code: ocn_pair_plan)
+static int pair_plan(long width, long height, int mult, int *rounds_out = nullptr)
 {
-    const long wx = (r.m1 - r.m0 + cols) / cols, h = r.n1 - r.n0 + 1;
-    // a tuning override (a fixed tile height), read once per process -- not a libc call per launch
-    static const int fixed = [] {
-        const char *e = getenv("OCN_PAIR_ROWS");
-        const int v = e ? atoi(e) : 0;
-        return v >= 8 && v <= OCN_PAIR_MAX_ROWS ? v : 0;
-    }();
-    if (fixed) return fixed;
+    const long wx = (width - 1 + kPairColsHost) / kPairColsHost, h = height;
+    const int cap = OCN_PAIR_MAX_ROWS, fixed = g_pair_rows_fixed.load(std::memory_order_relaxed);
+    auto rounds_of = [&](int rows) {
+        const long tiles = (h + rows - 1) / rows, waves = 4 * tiles * wx * mult;
+        return (waves + kPairSlots - 1) / kPairSlots;
+    };
     int best = 8;
-    long cost = -1;
-    for (int rows = 8; rows <= OCN_PAIR_MAX_ROWS; ++rows) {
-        const long tiles = (h + rows - 1) / rows, waves = 4 * tiles * wx * mult,
-                   rounds = (waves + kPairSlots - 1) / kPairSlots, c = rounds * (rows + 8);
-        if (cost < 0 || c < cost) { cost = c; best = rows; }
+    if (fixed) {
+        best = std::min(fixed, cap);
+    } else {
+        long cost = -1;
+        for (int rows = 8; rows <= cap; ++rows) {
+            const long c = rounds_of(rows) * (rows + 8);
+            if (cost < 0 || c < cost) { cost = c; best = rows; }
+        }
     }
+    if (rounds_out) *rounds_out = (int)rounds_of(best);
     return best;
 }
+static int pair_rows(const Range &r, int mult = 1)
+{
+    return pair_plan((long)r.m1 - r.m0 + 1, (long)r.n1 - r.n0 + 1, mult);
+}
+
+// the fixed tile height in force (0: automatic): part of what a captured step depends on (ocn_ctx.hip graph_step)
+int pair_rows_fixed() { return g_pair_rows_fixed.load(std::memory_order_relaxed); }
 
 int launch_onepass_pair(const ocn_block *b, void *const *ptr, int nptr, const Compact *cp, const ocn_sw_params &sw,
                         double tau, int32_t *nbad1, int32_t *nbad2, double *sshp_out, double *up_out, double *vp_out,
@@ -3692,8 +3731,7 @@ int launch_onepass_pair(const ocn_block *b, void *const *ptr, int nptr, const Co
     const Tab<true> t = make_tab<true>(ptr, nptr, cp->bits, cp->rows, block_rows(b), 0);
     const Range r = range_interior(b);
     if (range_empty(r)) return OCN_OK;
-    using KP = MarchStep<true, false, true, false, false, true>;
-    const int cols = KP::kPairCols, rows = pair_rows(r, cols);
+    const int cols = kPairColsHost, rows = pair_rows(r);
     MarchGrid g{};
     const int ntx = (r.m1 - r.m0 + cols) / cols;
     g.r[0] = MarchRect{r.m0, r.m1, r.n0, r.n1, r.m0, ntx, ntx * ((r.n1 - r.n0 + rows) / rows), max(r.m0 - 4, b->bnd_x1),
@@ -3769,7 +3807,7 @@ int launch_onepass_pair_x4(const ocn_block *bx, void *const *ptr, int nptr, cons
     MarchGrid g{};
     for (int i = 0; i < nr; ++i) {
         const Range &r = rs[i];
-        const int rows = pair_rows(r, cols, mult), ntx = (r.m1 - r.m0 + cols) / cols;
+        const int rows = pair_rows(r, mult), ntx = (r.m1 - r.m0 + cols) / cols;
         g.r[g.nr++] = MarchRect{r.m0, r.m1, r.n0, r.n1, r.m0, ntx, ntx * ((r.n1 - r.n0 + rows) / rows),
                                 max(r.m0 - 4, bx->bnd_x1), min(r.m1 + 4, bx->bnd_x2), rows, 0};
         g.ntiles += g.r[g.nr - 1].tiles;
@@ -4223,6 +4261,24 @@ using namespace ocn;
 // entries one thread per point
 
 extern "C" {
+
+// the two-step launch's tile plan and its process-wide fixed height (pair_plan)
+int ocn_pair_plan(int width, int height, int mult, int nv, int *rows, int *rounds, int *iterations)
+{
+    if (width < 1 || height < 1 || mult < 1 || !rows || !rounds || !iterations)
+        return set_error(OCN_ERR_ARG, "ocn_pair_plan: positive sizes and three output pointers");
+    (void)nv;   // the full and the inviscid bodies share one cap (OCN_PAIR_MAX_ROWS) and so one plan
+    *rows = pair_plan(width, height, mult, rounds);
+    *iterations = *rounds * (*rows + 8);
+    return OCN_OK;
+}
+
+int ocn_set_pair_rows(int rows)
+{
+    if (rows != 0 && rows < 8) return set_error(OCN_ERR_ARG, "ocn_set_pair_rows: 0 (automatic) or at least 8 rows");
+    g_pair_rows_fixed.store(rows, std::memory_order_relaxed);
+    return OCN_OK;
+}
 
 int ocn_sw_update_ssh(const ocn_block *b, double tau, const float *lu, const float *dx, const float *dy,
                       const float *dxh, const float *dyh, const double *hhu, const double *hhv, double *sshn,
