@@ -855,6 +855,54 @@ int ocn_ens_record_download(ocn_ens *ens, int32_t first, int32_t count, double *
 int ocn_ens_record_end(ocn_ens *ens);
 int ocn_ens_record_due(int64_t counted, int32_t nsteps, int32_t every, int32_t *steps, int32_t cap, int32_t *count);
 
+/* Observations at their own times: first guess at appropriate time, the asynchronous ensemble filter (Sakov
+ * et al. 2010).  A tide gauge reports through the analysis window, an altimeter pass crosses the basin once
+ * somewhere in it; the innovation of such an observation is value - H(state at the OBSERVATION's time), and the
+ * recorder's series holds exactly those equivalents.  One gather in time, from the series on the device, in front
+ * of ocn_ens_assimilate_h's loop and update, which then apply the resulting Y and Z to the state at analysis
+ * time.  No counterpart in the reference.
+ *
+ * The rule.  An active recorder has R records taken, nobs_r rows and n_r member columns.  Observation j < nobs of
+ * a call names a row row[j] of the recorder's operator (0 .. nobs_r-1), a record rec[j] (0 .. R-1) and a weight
+ * wt[j], finite, 0.0 <= wt < 1.0; if wt[j] != 0.0 record rec[j] + 1 must exist as well.  With
+ * a = series[rec][row][col] and b = series[rec+1][row][col]:
+ *   hx[j][m] = a                                   if wt == 0.0 (a copy, bit for bit, -0.0 and NaN included; b is
+ *                                                  not read)
+ *            = a + q,  where p = b - a;  q = wt * p   otherwise (IEEE double, every operation rounded, no
+ *                                                  contraction: ens_record_rule.interp restates it in numpy)
+ * Several observations may name the same row: a gauge's readings through the window name one row at different
+ * times.  The members of the call are `use`: NULL means the recorder's members, otherwise a subset of them,
+ * n >= 2 either way; column m is the recorder's column of the m-th member in use, in member order.  Record r was
+ * taken after the counted step (r + 1) * every: an observation at the counted step s (which may lie between
+ * steps) has x = s / every - 1.0, rec = floor(x), wt = x - rec (ens_record_rule.at_steps).
+ *
+ * ocn_ens_record_sample: host[j * n + m] = hx[j][m].  ONE launch, the nobs x n doubles come down through pinned
+ * memory with one wait; synchronous.  At most 65536 observations.  No member is read, no tail formed, no
+ * bookkeeping touched: the series is already on the ensemble's stream.
+ *
+ * ocn_ens_assimilate_rec: ocn_ens_assimilate_h with the prologue hx[j][m] = the rule's in the place of H_j(member
+ * u_m); (io[j], jo[j]) are the anchors as there.  The loop, the epilogue, the field update and all bookkeeping are
+ * ocn_ens_assimilate_h's, at most 8192 observations, asynchronous on the ensemble's stream, one launch for the
+ * prologue, the loop and the epilogue together and then the update's; ocn_ens_assimilate_info and
+ * ocn_ens_assimilate_result serve the last successful call of the three entries.  The recorder stays active and
+ * unchanged: the call neither counts nor records.
+ *
+ * What the caller must see to: the call uses the records AS THEY ARE.  A record taken before an earlier analysis,
+ * perturbation or upload of the same window describes a trajectory the members have left: it is stale, and
+ * nothing here notices.  A member whose status was not OCN_OK has undefined columns (above); the remedy is `use`.
+ *
+ * OCN_ERR_STATE without a recorder.  OCN_ERR_ARG -- nothing launched, no member's tail, state or bookkeeping
+ * touched, the recorder and the earlier results kept, nothing written to host -- for a null argument, everything
+ * ocn_ens_assimilate refuses (its obs_field apart; ocn_ens_record_sample: nobs < 1 or > 65536), no record taken
+ * yet, a row or rec out of range, a wt that is not finite, < 0 or >= 1, a wt != 0 at the last record, a member in
+ * `use` that the recorder does not hold, fewer than 2 members. */
+int ocn_ens_record_sample(ocn_ens *ens, const uint8_t *use, int32_t nobs, const int32_t *row, const int32_t *rec,
+                          const double *wt, double *host);
+int ocn_ens_assimilate_rec(ocn_ens *ens, const int32_t *field_ids, int32_t nfields, const uint8_t *use, int32_t nobs,
+                           const int32_t *io, const int32_t *jo, const int32_t *row, const int32_t *rec,
+                           const double *wt, const double *value, const double *variance, const double *taper,
+                           int32_t ntaper);
+
 /* Covariance inflation on the device: what keeps a square-root filter's spread from collapsing over the
  * cycles.  ocn_ens_transform can apply ONE factor to every point (n^2 work per point, and it inflates the
  * points no observation reached as well); relaxation to prior spread (RTPS, Whitaker & Hamill 2012) needs a

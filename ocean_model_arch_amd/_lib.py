@@ -110,7 +110,7 @@ ENS_SYMBOLS = ["ocn_ens_plan", "ocn_ens_create", "ocn_ens_destroy", "ocn_ens_siz
                "ocn_ens_assimilate_h", "ocn_ens_spread_save",
                "ocn_ens_inflate", "ocn_ens_inflate_download", "ocn_ens_perturb", "ocn_ens_perturb_download",
                "ocn_ens_record_begin", "ocn_ens_step_record", "ocn_ens_record_info", "ocn_ens_record_download",
-               "ocn_ens_record_end", "ocn_ens_record_due"]
+               "ocn_ens_record_end", "ocn_ens_record_due", "ocn_ens_record_sample", "ocn_ens_assimilate_rec"]
 ALL_SYMBOLS = KERNEL_SYMBOLS + CTX_SYMBOLS + ENS_SYMBOLS
 ENS_MAX_MEMBERS = 256          # OCN_ENS_MAX_MEMBERS
 ENS_OBS_MAX_TERMS = 16         # OCN_ENS_OBS_MAX_TERMS
@@ -324,6 +324,9 @@ def lib() -> C.CDLL:
     L.ocn_ens_record_download.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     L.ocn_ens_record_end.argtypes = [C.c_void_p]
     L.ocn_ens_record_due.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
+    L.ocn_ens_record_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ocn_ens_assimilate_rec.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.ocn_pair_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                 C.POINTER(C.c_int)]
     L.ocn_set_pair_rows.argtypes = [C.c_int]

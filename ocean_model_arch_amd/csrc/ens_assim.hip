@@ -39,6 +39,10 @@
 // H_j(member u_m) from a CSR table of terms; k_ens_sample_h brings it down, one thread per (observation,
 // member); k_ens_obs_space_h is k_ens_obs_space with hx[j][m] = H_j(member u_m) in the prologue -- the two
 // are instances of one body, as_stage, and still ONE launch of ONE workgroup each.
+//
+// Observations at their own times (ocn_sw.h ocn_ens_record_sample, ocn_ens_assimilate_rec): rec_interp forms hx
+// from the station recorder's series, one gather in time; k_ens_record_sample brings it down, one thread per
+// (observation, member) with the member fastest; k_ens_obs_space_r is the third instance of as_stage.
 #include "ocn_internal.h"
 
 namespace ocn {
@@ -95,11 +99,32 @@ __device__ __forceinline__ double obs_apply(const EnsObsOp &h, int j, int m)
     return s;
 }
 
+// ------------------------------------------------------------------ the recorder's series as the source
+// hx[j][m] from the station recorder's series (ocn_sw.h ocn_ens_record_sample): a = the row's value in record
+// rec, column col[m]; with wt == 0.0 a itself, bit for bit, and the second load is not issued; else b = the same
+// element of record rec + 1, p = b - a; q = wt * p; a + q, every operation rounded (-ffp-contract=off).  ONE
+// function for the sample and for the filter's prologue: the same bits from both.
+__device__ __forceinline__ double rec_interp(const EnsRecSrc &r, int j, int m)
+{
+    const EnsRecObs o = r.obs[j];
+    const double *at = r.series + (o.off + r.col[m]);
+    const double a = at[0];
+    if (o.wt == 0.0) return a;
+    const double b = at[r.next];
+    const double p = b - a;
+    const double q = o.wt * p;
+    return a + q;
+}
+
 // ------------------------------------------------------------------ the observation-space stage
-// The whole stage, ONE text for k_ens_obs_space (kOp false: hx gathered at points) and k_ens_obs_space_h (kOp
-// true: hx = the operator h applied to the members): only the prologue's right-hand side differs.
-template <bool kOp>
-__device__ __forceinline__ void as_stage(const EnsAsArgs a, const EnsObsOp h, double *xk, double *yk, double *zk)
+// The whole stage, ONE text for k_ens_obs_space (kSrc kAsPoints: hx gathered at points), k_ens_obs_space_h
+// (kAsOperator: hx = the operator h applied to the members) and k_ens_obs_space_r (kAsRecords: hx interpolated in
+// the recorder's series r): only the prologue's right-hand side differs.
+constexpr int kAsPoints = 0, kAsOperator = 1, kAsRecords = 2;
+
+template <int kSrc>
+__device__ __forceinline__ void as_stage(const EnsAsArgs a, const EnsObsOp h, const EnsRecSrc r, double *xk, double *yk,
+                                         double *zk)
 {
     const int tid = (int)threadIdx.x, n = a.n, nobs = a.nobs;
     const long row = a.row;
@@ -109,7 +134,8 @@ __device__ __forceinline__ void as_stage(const EnsAsArgs a, const EnsObsOp h, do
     for (long q = tid; q < (long)nobs * row; q += kAsThreads) {
         const int j = (int)(q / row), m = (int)(q % row);
         if (m < n) {
-            if constexpr (kOp) a.hx[q] = obs_apply(h, j, m);
+            if constexpr (kSrc == kAsOperator) a.hx[q] = obs_apply(h, j, m);
+            else if constexpr (kSrc == kAsRecords) a.hx[q] = rec_interp(r, j, m);
             else a.hx[q] = a.tab[(long)a.blk[j] * n + m][a.off[j]];
         } else {
             a.hx[q] = 0.0; a.y[q] = 0.0; a.z[q] = 0.0;
@@ -221,7 +247,7 @@ __device__ __forceinline__ void as_stage(const EnsAsArgs a, const EnsObsOp h, do
 __global__ __launch_bounds__(kAsThreads) void k_ens_obs_space(const EnsAsArgs a)
 {
     __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
-    as_stage<false>(a, EnsObsOp{}, xk, yk, zk);
+    as_stage<kAsPoints>(a, EnsObsOp{}, EnsRecSrc{}, xk, yk, zk);
 }
 
 // grid: (observations / 256, members)
@@ -236,7 +262,23 @@ __global__ __launch_bounds__(256) void k_ens_sample_h(const EnsObsOp h, int n, i
 __global__ __launch_bounds__(kAsThreads) void k_ens_obs_space_h(const EnsAsArgs a, const EnsObsOp h)
 {
     __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
-    as_stage<true>(a, h, xk, yk, zk);
+    as_stage<kAsOperator>(a, h, EnsRecSrc{}, xk, yk, zk);
+}
+
+// one thread per (observation, member), the member fastest: a wave's series loads and its stores are contiguous
+// runs (k_ens_sample_h's mapping, j fastest, would stride the series by the recorder's member count)
+__global__ __launch_bounds__(256) void k_ens_record_sample(const EnsRecSrc r, int n, long total, double *__restrict__ out)
+{
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= total) return;
+    out[q] = rec_interp(r, (int)(q / n), (int)(q % n));
+}
+
+// k_ens_obs_space with the recorder's series in its prologue
+__global__ __launch_bounds__(kAsThreads) void k_ens_obs_space_r(const EnsAsArgs a, const EnsRecSrc r)
+{
+    __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
+    as_stage<kAsRecords>(a, EnsObsOp{}, r, xk, yk, zk);
 }
 
 int launch_ens_obs_space(const EnsAsArgs &a, hipStream_t s)
@@ -264,6 +306,25 @@ int launch_ens_obs_space_h(const EnsAsArgs &a, const EnsObsOp &h, hipStream_t s)
         !a.taper || !a.hx || !a.y || !a.z || !a.innovation || !a.prior || !a.posterior || !a.nonfinite)
         return set_error(OCN_ERR_ARG, "ens_obs_space_h: member count, tables or reach");
     hipLaunchKernelGGL(k_ens_obs_space_h, dim3(1), dim3(kAsThreads), 0, s, a, h);
+    return check_launch();
+}
+
+int launch_ens_record_sample(const EnsRecSrc &r, int n, int nobs, double *d_out, hipStream_t s)
+{
+    if (n < 1 || n > OCN_ENS_MAX_MEMBERS || nobs < 1 || nobs > 65536 || !r.series || !r.obs || !r.col || r.next < 1 || !d_out)
+        return set_error(OCN_ERR_ARG, "ens_record_sample: nothing to gather");
+    const long total = (long)nobs * n;   // (at most 2^24: the grid's x dimension holds it)
+    hipLaunchKernelGGL(k_ens_record_sample, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, r, n, total, d_out);
+    return check_launch();
+}
+
+int launch_ens_obs_space_r(const EnsAsArgs &a, const EnsRecSrc &r, hipStream_t s)
+{
+    if (a.n < 2 || a.n > OCN_ENS_MAX_MEMBERS || a.nobs < 1 || a.ntaper < 1 || a.reach < 0 || a.reach > 255 ||
+        a.row != (long)ens_lu_row(a.n) || !r.series || !r.obs || !r.col || r.next < 1 || !a.io || !a.jo || !a.value ||
+        !a.variance || !a.taper || !a.hx || !a.y || !a.z || !a.innovation || !a.prior || !a.posterior || !a.nonfinite)
+        return set_error(OCN_ERR_ARG, "ens_obs_space_r: member count, tables or reach");
+    hipLaunchKernelGGL(k_ens_obs_space_r, dim3(1), dim3(kAsThreads), 0, s, a, r);
     return check_launch();
 }
 

@@ -59,7 +59,7 @@ struct ocn_ens {
     hipEvent_t ev_lu = nullptr;
     bool ev_lu_set = false;
     // ocn_ens_assimilate: the call's tables (taper, lists, values, variances, offsets, indices, blocks, the
-    // members' arrays per block), then the device-formed rows hx, y, z and the innovation, prior and
+    // operator's or the recorder's observations, the members' arrays per block), then the device-formed rows hx, y, z and the innovation, prior and
     // posterior vectors and the count, on the device and in pinned host memory (as_bytes each, grown when a
     // call needs more; the results come down into h_as at the offsets they have in d_as); ev_as: the stream
     // has read h_as's tables.  as_last: the last successful call's results (nobs 0: none yet)
@@ -1096,9 +1096,9 @@ int ocn_ens_local_update(ocn_ens *e, const int32_t *field_ids, int32_t nfields, 
 }
 
 // ------------------------------------------------------------------ the serial filter on the device (ens_assim.hip)
-// Launches per call: kAsLaunches for the observation-space stage (k_ens_obs_space, or k_ens_obs_space_h behind a
-// sparse linear observation operator; whatever n and nobs), then ocn_ens_local_update's: one per listed field
-// and block that an observation reaches.
+// Launches per call: kAsLaunches for the observation-space stage (k_ens_obs_space, k_ens_obs_space_h behind a
+// sparse linear observation operator, or k_ens_obs_space_r behind the recorder's series; whatever n and nobs),
+// then ocn_ens_local_update's: one per listed field and block that an observation reaches.
 constexpr int kAsLaunches = 1;
 static_assert(kAsLaunches == 1, "ocn_sw.h and DESIGN.md state this count");
 
@@ -1172,12 +1172,14 @@ static void ens_obs_table(const std::vector<ocn_ctx *> &in, const std::vector<in
                 tab[(f * nblk + b) * n + m] = (const double *)in[m]->blocks[b].ptr[field_slot(fields[f])];
 }
 
-// ocn_ens_assimilate and ocn_ens_assimilate_h behind their checks.  The prologue reads `src`, the fields of
-// the pointer table: one field at the points (off, blk), or with `start` the operator's terms.
+// ocn_ens_assimilate, ocn_ens_assimilate_h and ocn_ens_assimilate_rec behind their checks.  The prologue reads
+// `src`, the fields of the pointer table: one field at the points (off, blk), or with `start` the operator's
+// terms; or, with `robs`, no field at all but the recorder's series at robs[j] in the columns `col`.
 static int ens_as_run(ocn_ens *e, const char *entry, const std::vector<ocn_ctx *> &in, const int32_t *field_ids, int32_t nfields,
                       int32_t nobs, const int32_t *io, const int32_t *jo, const double *value, const double *variance,
                       const double *taper, int32_t ntaper, const std::vector<int32_t> &src, const std::vector<long> &off,
-                      const std::vector<int> &blk, const int32_t *start, const std::vector<EnsObsTerm> &term)
+                      const std::vector<int> &blk, const int32_t *start, const std::vector<EnsObsTerm> &term,
+                      const std::vector<EnsRecObs> &robs = {}, const std::vector<int> &col = {})
 {
     const ocn_ctx *c0 = e->m[0];
     const size_t n = in.size(), nblk = c0->blocks.size(), no = (size_t)nobs;
@@ -1191,7 +1193,8 @@ static int ens_as_run(ocn_ens *e, const char *entry, const std::vector<ocn_ctx *
     const size_t tap_at = 0, list_at0 = part(tap_at, (size_t)ntaper * sizeof(double)), val_at = part(list_at0, list_n * sizeof(EnsLuObs)),
                  var_at = part(val_at, no * 8), off_at = part(var_at, no * 8), io_at = part(off_at, off.size() * sizeof(long)),
                  jo_at = part(io_at, no * 4), blk_at = part(jo_at, no * 4), start_at = part(blk_at, blk.size() * 4),
-                 term_at = part(start_at, start ? (no + 1) * 4 : 0), tab_at = part(term_at, term.size() * sizeof(EnsObsTerm)),
+                 term_at = part(start_at, start ? (no + 1) * 4 : 0), robs_at = part(term_at, term.size() * sizeof(EnsObsTerm)),
+                 col_at = part(robs_at, robs.size() * sizeof(EnsRecObs)), tab_at = part(col_at, col.size() * sizeof(int)),
                  up_b = part(tab_at, src.size() * nblk * n * sizeof(double *)), hx_at = up_b, y_at = part(hx_at, rows_b),
                  z_at = part(y_at, rows_b), vec_at = part(z_at, rows_b), count_at = part(vec_at, 3 * no * 8),
                  need = part(count_at, sizeof(long));
@@ -1224,7 +1227,10 @@ static int ens_as_run(ocn_ens *e, const char *entry, const std::vector<ocn_ctx *
     memcpy(h + var_at, variance, no * 8);
     memcpy(h + io_at, io, no * 4);
     memcpy(h + jo_at, jo, no * 4);
-    if (start) {
+    if (!robs.empty()) {
+        memcpy(h + robs_at, robs.data(), robs.size() * sizeof(EnsRecObs));
+        memcpy(h + col_at, col.data(), col.size() * sizeof(int));
+    } else if (start) {
         memcpy(h + start_at, start, (no + 1) * 4);
         memcpy(h + term_at, term.data(), term.size() * sizeof(EnsObsTerm));
     } else {
@@ -1245,7 +1251,12 @@ static int ens_as_run(ocn_ens *e, const char *entry, const std::vector<ocn_ctx *
     a.nonfinite = (long *)(d + count_at);
     a.row = (long)row; a.n = (int)n; a.nobs = nobs; a.ntaper = ntaper; a.reach = reach;
     if (timed) HIPCHK(hipEventRecord(e->ev_t[0], e->stream));
-    if (start) {
+    if (!robs.empty()) {
+        const ocn_ens::Recorder &r = e->rec;
+        const EnsRecSrc rs{(const double *)r.d_series, (const EnsRecObs *)(d + robs_at), (const int *)(d + col_at),
+                           (long)r.nobs * (long)r.n};
+        RC(launch_ens_obs_space_r(a, rs, e->stream));
+    } else if (start) {
         const EnsObsOp op{a.tab, (const int *)(d + start_at), (const EnsObsTerm *)(d + term_at)};
         RC(launch_ens_obs_space_h(a, op, e->stream));
     } else {
@@ -1572,6 +1583,98 @@ int ocn_ens_step_record(ocn_ens *e, double tau, int32_t nsteps, int32_t check_ev
     r.steps += nsteps;
     r.records += (int32_t)due.size();
     return first;
+}
+
+// ------------------------------------------------------------------ observations at their own times (ocn_sw.h)
+// What ocn_ens_record_sample and ocn_ens_assimilate_rec check alike.  ens_rec_members: the members of the call
+// (`use`, or the recorder's) among the recorder's, each one's column of the series in `col`.  ens_rec_obs: each
+// observation's row, record and weight against the records taken, resolved into its series offset; nothing is
+// read beyond a bad entry.  `who` opens the message.
+static int ens_rec_members(const ocn_ens *e, const std::string &who, const uint8_t *use, std::vector<ocn_ctx *> &in,
+                           std::vector<int> &col)
+{
+    const ocn_ens::Recorder &r = e->rec;
+    int held = 0;
+    for (size_t i = 0; i < e->m.size(); ++i) {
+        if (use && use[i] && !r.use[i]) return set_error(OCN_ERR_ARG, who + ": a member in use that the recorder does not hold");
+        if (r.use[i] && (!use || use[i])) { in.push_back(e->m[i]); col.push_back(held); }
+        held += r.use[i] ? 1 : 0;
+    }
+    return OCN_OK;
+}
+
+static int ens_rec_obs(const ocn_ens *e, const std::string &who, int32_t nobs, const int32_t *row, const int32_t *rec,
+                       const double *wt, std::vector<EnsRecObs> &robs)
+{
+    const ocn_ens::Recorder &r = e->rec;
+    if (r.records < 1) return set_error(OCN_ERR_ARG, who + ": no record taken yet");
+    robs.resize((size_t)nobs);
+    for (int32_t j = 0; j < nobs; ++j) {
+        if (row[j] < 0 || row[j] >= r.nobs) return set_error(OCN_ERR_ARG, who + ": a row outside the recorder's operator");
+        if (rec[j] < 0 || rec[j] >= r.records) return set_error(OCN_ERR_ARG, who + ": a record outside the records taken");
+        if (!std::isfinite(wt[j]) || !(wt[j] >= 0.0) || !(wt[j] < 1.0))
+            return set_error(OCN_ERR_ARG, who + ": a weight that is not finite and in [0, 1)");
+        if (wt[j] != 0.0 && rec[j] + 1 >= r.records) return set_error(OCN_ERR_ARG, who + ": a nonzero weight at the last record");
+        robs[(size_t)j] = EnsRecObs{((long)rec[j] * (long)r.nobs + (long)row[j]) * (long)r.n, wt[j]};
+    }
+    return OCN_OK;
+}
+
+// ocn_ens_sample_h with the series in the members' place, in ocn_ens_sample's buffers: no member is read
+int ocn_ens_record_sample(ocn_ens *e, const uint8_t *use, int32_t nobs, const int32_t *row, const int32_t *rec,
+                          const double *wt, double *host)
+{
+    if (!e || !row || !rec || !wt || !host) return set_error(OCN_ERR_ARG, "ens_record_sample: null argument");
+    const ocn_ens::Recorder &r = e->rec;
+    if (!r.active) return set_error(OCN_ERR_STATE, "ens_record_sample: no recorder (ocn_ens_record_begin)");
+    if (nobs < 1 || nobs > 65536) return set_error(OCN_ERR_ARG, "ens_record_sample: 1..65536 observations");
+    std::vector<ocn_ctx *> in;
+    std::vector<int> col;
+    RC(ens_rec_members(e, "ens_record_sample", use, in, col));
+    if (in.size() < 2) return set_error(OCN_ERR_ARG, "ens_record_sample: fewer than two members in use");
+    std::vector<EnsRecObs> robs;
+    RC(ens_rec_obs(e, "ens_record_sample", nobs, row, rec, wt, robs));
+    HIPCHK(hipSetDevice(e->device));
+    // one layout on both sides: the observations' table, the columns (up), the results (down)
+    const size_t n = in.size(), no = (size_t)nobs, obs_b = no * sizeof(EnsRecObs), col_b = (n * sizeof(int) + 7) / 8 * 8,
+                 up_b = obs_b + col_b, res_b = no * n * sizeof(double);
+    if (e->samp_bytes < up_b + res_b) {   // (a synchronous entry: nothing in flight reads the old ones)
+        if (e->d_samp) (void)hipFree(e->d_samp);
+        if (e->h_samp) (void)hipHostFree(e->h_samp);
+        e->d_samp = e->h_samp = nullptr;
+        e->samp_bytes = 0;
+        HIPCHK(hipMalloc(&e->d_samp, up_b + res_b));
+        HIPCHK(hipHostMalloc(&e->h_samp, up_b + res_b, hipHostMallocDefault));
+        e->samp_bytes = up_b + res_b;
+    }
+    char *d = (char *)e->d_samp, *hp = (char *)e->h_samp;
+    memcpy(hp, robs.data(), obs_b);
+    memcpy(hp + obs_b, col.data(), n * sizeof(int));
+    HIPCHK(hipMemcpyAsync(d, hp, up_b, hipMemcpyHostToDevice, e->stream));
+    const EnsRecSrc rs{(const double *)r.d_series, (const EnsRecObs *)d, (const int *)(d + obs_b), (long)r.nobs * (long)r.n};
+    RC(launch_ens_record_sample(rs, (int)n, nobs, (double *)(d + up_b), e->stream));
+    HIPCHK(hipMemcpyAsync(hp + up_b, d + up_b, res_b, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    memcpy(host, hp + up_b, res_b);
+    return OCN_OK;
+}
+
+int ocn_ens_assimilate_rec(ocn_ens *e, const int32_t *field_ids, int32_t nfields, const uint8_t *use, int32_t nobs,
+                           const int32_t *io, const int32_t *jo, const int32_t *row, const int32_t *rec, const double *wt,
+                           const double *value, const double *variance, const double *taper, int32_t ntaper)
+{
+    if (!e || !field_ids || !io || !jo || !row || !rec || !wt || !value || !variance || !taper)
+        return set_error(OCN_ERR_ARG, "ens_assimilate_rec: null argument");
+    if (!e->rec.active) return set_error(OCN_ERR_STATE, "ens_assimilate_rec: no recorder (ocn_ens_record_begin)");
+    std::vector<ocn_ctx *> in;
+    std::vector<int> col;
+    RC(ens_rec_members(e, "ens_assimilate_rec", use, in, col));
+    RC(ens_lu_check(e, "ens_assimilate_rec", field_ids, nfields, in, nobs, io, jo, taper, ntaper));
+    RC(ens_as_check("ens_assimilate_rec", nobs, value, variance));
+    std::vector<EnsRecObs> robs;
+    RC(ens_rec_obs(e, "ens_assimilate_rec", nobs, row, rec, wt, robs));
+    return ens_as_run(e, "ocn_ens_assimilate_rec", in, field_ids, nfields, nobs, io, jo, value, variance, taper, ntaper, {}, {}, {},
+                      nullptr, {}, robs, col);
 }
 
 // bytes [at, at + bytes) of the last call's results into the pinned copy, with one wait

@@ -323,6 +323,18 @@ int launch_ens_sample_h(const EnsObsOp &h, int n, int nobs, double *d_out, hipSt
 // launch_ens_obs_space with the prologue hx[j][m] = H_j(member u_m): a.tab, a.off and a.blk are not read.  ONE
 // launch of ONE workgroup of kAsThreads threads.
 int launch_ens_obs_space_h(const EnsAsArgs &a, const EnsObsOp &h, hipStream_t s);
+// The station recorder's series as the source of hx (ens_assim.hip; ocn_sw.h ocn_ens_record_sample,
+// ocn_ens_assimilate_rec): observation j reads the series at the elements obs[j].off + col[m] and, with
+// obs[j].wt != 0.0, `next` further on (the same row and column of the next record) -- off = (rec * nobs_r + row) *
+// n_r, next = nobs_r * n_r, col[m] the recorder's column of the m-th member in use -- and interpolates between
+// them with the weight wt.  The host has validated every offset.
+struct EnsRecObs { long off; double wt; };
+struct EnsRecSrc { const double *series; const EnsRecObs *obs; const int *col; long next; };
+// out[j * n + m] = the rule's hx[j][m], j < nobs.  ONE launch.
+int launch_ens_record_sample(const EnsRecSrc &r, int n, int nobs, double *d_out, hipStream_t s);
+// launch_ens_obs_space with the prologue hx[j][m] = the rule's: a.tab, a.off and a.blk are not read.  ONE launch
+// of ONE workgroup of kAsThreads threads.
+int launch_ens_obs_space_r(const EnsAsArgs &a, const EnsRecSrc &r, hipStream_t s);
 // Covariance inflation (ens_inflate.hip; ocn_sw.h ocn_ens_inflate) of the n arrays mem[0 .. n) (one field of
 // one block geometry, the members in use in member order, n >= 2), in place, at every point of
 // A(bnd_x1:bnd_x2, bnd_y1:bnd_y2).  mode: OCN_ENS_INFLATE_*; d_spread: the saved spread (RTPS; else unused);

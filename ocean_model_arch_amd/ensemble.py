@@ -106,6 +106,7 @@ class OceanEnsemble:
         self.ens = None
         check(L.ocn_ens_create(C.byref(cb), C.byref(cs), C.byref(cd), mptr, int(members), C.byref(h)), "ocn_ens_create")
         self.ens = h
+        self._rec_op, self._rec_members = None, None   # (record() sets them)
         self.members: list[OceanModel] = []
         for i in range(L.ocn_ens_size(self.ens)):
             c = C.c_void_p()
@@ -634,6 +635,9 @@ class OceanEnsemble:
         check(lib().ocn_ens_record_begin(self.ens, self._use(members), op.nobs, *[a.ctypes.data_as(C.c_void_p) for a in arrays],
                                          int(every), int(max_records)), "ocn_ens_record_begin")
         self._recording = True
+        # what sample_recorded() / assimilate_recorded() need of it: the operator (its anchors) and the members
+        self._rec_op = op
+        self._rec_members = None if members is None else sorted({int(i) for i in members})
         return self
 
     def step_record(self, nsteps: int = 1, tau: float = 1.0, check_every: int = 1):
@@ -681,6 +685,120 @@ class OceanEnsemble:
         self._recording = False
         check(lib().ocn_ens_record_end(self.ens), "ocn_ens_record_end")
         return self
+
+    # ------------------------------------------------------------ observations at their own times
+    def _recorded_obs(self, who, rows, at, members, max_obs):
+        """What sample_recorded() and assimilate_recorded() check and resolve alike: (rows, rec, wt) as the entries
+        take them, the members in effect (None: all), their columns of the series (None: all) and their number."""
+        info = self.record_info()
+        if not info["active"]:
+            raise _lib.OcnError(_lib.OCN_ERR_STATE, f"{who}: no recorder (record())")
+        ra, ta = np.asarray(rows), np.asarray(at)
+        if ra.dtype.kind not in "iu":
+            raise TypeError(f"{who}: rows of dtype {ra.dtype}, not integers")
+        if ta.dtype.kind not in "iuf":
+            raise TypeError(f"{who}: times of dtype {ta.dtype}, not numbers")
+        if ra.ndim != 1 or ta.shape != ra.shape:
+            raise ValueError(f"{who}: rows and times of shapes {ra.shape} and {ta.shape}, not one (nobs,)")
+        rec, wt = ens_record_rule.at_steps(ta.astype(np.float64), info["every"], info["records"])
+        ra, rec, wt = ens_record_rule.check_obs(ra, rec, wt, info["nobs"], info["records"], max_obs)
+        held = list(range(len(self.members))) if self._rec_members is None else self._rec_members
+        if members is None:
+            eff, cols = self._rec_members, None
+        else:
+            self._use(members)   # (IndexError for an index outside the ensemble)
+            eff = sorted({int(i) for i in members})
+            if set(eff) - set(held):
+                raise ValueError(f"{who}: members {sorted(set(eff) - set(held))}, which the recorder does not hold")
+            cols = [held.index(i) for i in eff]
+        n = len(held) if eff is None else len(eff)
+        if n < 2:
+            raise ValueError(f"{who}: {n} members in use, fewer than two")
+        return ra, rec, wt, eff, cols, n
+
+    def sample_recorded(self, rows, at, members=None) -> np.ndarray:
+        """The members' equivalents of observations at their own times, from the recorder's series on the device
+        (ocn_ens_record_sample; the rule is in include/ocn_sw.h, its numpy restatement is
+        ens_record_rule.interp): observation j is row rows[j] of the operator record() took, at the time at[j]
+        in counted steps since record() (a float: it may lie between steps and between records; a row may be named
+        many times).  A float64 array (nobs, n), column m the m-th of `members` in member order (None: the
+        recorder's; otherwise a subset of them, at least two).  One launch and one wait; no member is read.
+        TypeError for rows or times of the wrong type, ValueError for a time outside the records taken, a row
+        outside the operator, more than 65536 observations or a member the recorder does not hold."""
+        ra, rec, wt, _, _, n = self._recorded_obs("sample_recorded", rows, at, members, ens_record_rule.MAX_SAMPLE_OBS)
+        out = np.zeros((len(ra), n), dtype=np.float64)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        check(lib().ocn_ens_record_sample(self.ens, self._use(members), len(ra), ptr(ra), ptr(rec), ptr(wt), ptr(out)),
+              "ocn_ens_record_sample")
+        return out
+
+    def assimilate_recorded(self, rows, at, values, variances, taper, anchors=None, names=STATE, members=None,
+                            device: bool = False, rtps=None) -> dict:
+        """assimilate_h() for observations taken during the window (first guess at appropriate time, the
+        asynchronous ensemble filter of Sakov et al. 2010): observation j is `values[j]`, with error variance
+        `variances[j]`, of row rows[j] of the recorded operator at the time at[j] (as in sample_recorded()); the
+        members' equivalents come from the recorder's series at that time, and the resulting Y and Z are applied
+        to the fields `names` as they are NOW, at `anchors` ((nobs, 2) points of the basin; None: the recorded
+        operator's anchors[rows]).  The keys returned are assimilate_h()'s.
+
+        device=False: series(), ens_record_rule.interp, the observation-space loop on the host
+        (ens_local_rule.ensrf_obs_space at the anchors), one local_update().  device=True: ocn_ens_assimilate_rec
+        -- the gather in time, the loop and the field update on the ensemble's stream with no wait in between --
+        plus "nonfinite".  `members`: None for the recorder's, otherwise a subset of them.  The recorder stays
+        active and unchanged.  The records are used as they are: one taken before an earlier analysis,
+        perturbation or upload of the same window is stale, and a member that blew up has undefined columns --
+        leave it out with `members`.
+
+        rtps=alpha: as in assimilate_h().  TypeError for an argument of the wrong type, ValueError otherwise,
+        more than 8192 observations included."""
+        who = "assimilate_recorded"
+        if rtps is not None:
+            alpha = float(rtps)
+            if not np.isfinite(alpha) or alpha < 0.0:
+                raise ValueError(f"{who}: rtps = {rtps!r}, not a finite float >= 0")
+        ra, rec, wt, eff, cols, n = self._recorded_obs(who, rows, at, members, ens_local_rule.MAX_OBS)
+        nobs = len(ra)
+        ij = np.asarray(self._rec_op.anchors)[ra] if anchors is None else np.asarray(anchors)
+        if ij.dtype.kind not in "iu":
+            raise TypeError(f"{who}: anchors of dtype {ij.dtype}, not integers")
+        if ij.shape != (nobs, 2):
+            raise ValueError(f"{who}: anchors of shape {ij.shape}, not {(nobs, 2)}")
+        va = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
+        ra_ = np.ascontiguousarray(np.asarray(variances, dtype=np.float64).ravel())
+        ta = np.ascontiguousarray(np.asarray(taper, dtype=np.float64))
+        if len(va) != nobs or len(ra_) != nobs:
+            raise ValueError(f"{who}: {len(va)} values and {len(ra_)} variances for {nobs} observations")
+        if ta.ndim != 1 or not 1 <= len(ta) <= ens_local_rule.MAX_TAPER:
+            raise ValueError(f"{who}: a taper of shape {ta.shape}, not 1..{ens_local_rule.MAX_TAPER} entries")
+        names = (names,) if isinstance(names, str) else tuple(names)
+        if rtps is not None:
+            self.spread_save(names, members=eff)
+        if not device:
+            hx = ens_record_rule.interp(self.series(), ra, rec, wt, cols)
+            Y, Z, out = ens_local_rule.ensrf_obs_space(hx, ij, va, ra_, ta)
+            self.local_update(Y, Z, ij, ta, names=names, members=eff)
+            finish = lambda: out   # noqa: E731
+        else:
+            ids = (C.c_int32 * len(names))(*[_lib.FIELD_ID[nm] for nm in names])
+            io, jo = (np.ascontiguousarray(ij[:, c], dtype=np.int32) for c in range(2))
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+            L = lib()
+            check(L.ocn_ens_assimilate_rec(self.ens, ids, len(names), self._use(members), nobs, ptr(io), ptr(jo), ptr(ra),
+                                           ptr(rec), ptr(wt), ptr(va), ptr(ra_), ptr(ta), len(ta)), "ocn_ens_assimilate_rec")
+
+            def finish():   # the call's results (one wait each)
+                out = {}
+                for key in ("hx", "innovations", "prior_spread", "posterior_spread"):
+                    a = np.zeros((nobs, n) if key == "hx" else nobs, dtype=np.float64)
+                    check(L.ocn_ens_assimilate_result(self.ens, _lib.ENS_ASSIM[key], ptr(a)), "ocn_ens_assimilate_result")
+                    out[key] = a
+                info = _lib.OcnEnsAssimInfo()
+                check(L.ocn_ens_assimilate_info(self.ens, C.byref(info)), "ocn_ens_assimilate_info")
+                out["nonfinite"] = int(info.nonfinite)
+                return out
+        if rtps is not None:   # (behind the analysis, before the device path's first wait)
+            self.inflate(alpha, "rtps", names, members=eff)
+        return finish()
 
     def set_record_in_launch(self, on: bool = True):
         """Tests and measurements: off, step_record() always takes the chunked route."""
