@@ -750,8 +750,42 @@ int ocn_ens_assimilate(ocn_ens *ens, int32_t obs_field, const int32_t *field_ids
 typedef struct ocn_ens_assim_info_t { int32_t nobs, n; int64_t nonfinite; } ocn_ens_assim_info_t;
 int ocn_ens_assimilate_info(ocn_ens *ens, ocn_ens_assim_info_t *out);
 enum { OCN_ENS_ASSIM_HX = 0, OCN_ENS_ASSIM_Y = 1, OCN_ENS_ASSIM_Z = 2, OCN_ENS_ASSIM_INNOVATION = 3,
-       OCN_ENS_ASSIM_PRIOR_SPREAD = 4, OCN_ENS_ASSIM_POSTERIOR_SPREAD = 5, OCN_ENS_ASSIM_SPANS = 6 };
+       OCN_ENS_ASSIM_PRIOR_SPREAD = 4, OCN_ENS_ASSIM_POSTERIOR_SPREAD = 5, OCN_ENS_ASSIM_SPANS = 6,
+       OCN_ENS_ASSIM_ACCEPTED = 8 /* (7 stays an unknown `what`: OCN_ERR_ARG) */ };
 int ocn_ens_assimilate_result(ocn_ens *ens, int32_t what, double *host);
+
+/* Quality control of the observations against the background, inside the loop of ocn_ens_assimilate,
+ * ocn_ens_assimilate_h and ocn_ens_assimilate_rec (below): a tide gauge that spikes has an innovation of tens of
+ * background standard deviations and would drag every field within reach; a member that is NaN at an observed
+ * point would write NaN there.  No counterpart in the reference.
+ *
+ * ocn_ens_set_gate: gate2 is the squared threshold in units of the innovation variance (9.0: 3 sigma).  0.0, of
+ * either sign, turns the gate off -- the default; the three entries then launch exactly what they launch without
+ * this entry.  Otherwise gate2 > 0 and not NaN; +inf is allowed and rejects only on a D or d that is not finite.
+ * Anything else: OCN_ERR_ARG, the setting unchanged.  The setting holds for the three entries until it is changed.
+ *   The loop with the gate on: after D and d of observation k are formed (unchanged operations, on the CURRENT
+ *   row), lim = gate2 * D (one rounded product) and ok = isfinite(D) && isfinite(d) && d * d <= lim.
+ *     ok: everything as without a gate.
+ *     not ok, the observation is REJECTED: Y[k][m] = y'_m as formed, Z[k][m] = +0.0, innovation[k] = d, `nonfinite`
+ *     counts as ever; no row takes observation k and no field point takes it.  A rejected observation forms
+ *     nothing: a -0.0 stays -0.0, and a point that only rejected observations reach is not stored.
+ *   prior_spread and posterior_spread keep their definitions (a rejected row's posterior is still that row's final
+ *   spread).  The test is against the CURRENT row -- as observations 0 .. k-1 left it -- not against the
+ *   prologue's prior: like the rest of the serial loop it depends on the ORDER of the observations (an outlier
+ *   ahead of a good observation at the same point is judged against the wider, earlier background).
+ * Launches: those of the ungated call, the observation-space stage still ONE launch of one workgroup; the
+ * update's launches go out as before -- the host does not know what was rejected; the stage rewrites the entries of
+ * rejected observations in the update's lists on the device, and the update skips them.  Asynchronous as before,
+ * no new wait.  The three entries refuse what they refused: a value that is not finite is still OCN_ERR_ARG on the
+ * host; the gate is for outliers and for members that are not finite.
+ * (ens_local_rule.ensrf_obs_space_ordered(..., gate2=) restates it in numpy.)
+ *
+ * ocn_ens_assimilate_result(..., OCN_ENS_ASSIM_ACCEPTED, host): nobs doubles, 1.0 (accepted) or 0.0 (rejected);
+ * all 1.0 after a call made with the gate off.  ocn_ens_gate_info: the setting, and the rejected observations of
+ * the last successful call of the three entries (0 with the gate off or before any call; waits for the stream). */
+int ocn_ens_set_gate(ocn_ens *ens, double gate2);
+typedef struct ocn_ens_gate_info_t { double gate2; int64_t rejected; } ocn_ens_gate_info_t;
+int ocn_ens_gate_info(ocn_ens *ens, ocn_ens_gate_info_t *out);
 
 /* Observations that are not one field's value at one grid point -- an altimeter track between h points, a
  * radial velocity cos(theta) u + sin(theta) v of interpolated values, a footprint average: a SPARSE LINEAR

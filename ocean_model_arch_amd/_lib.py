@@ -110,7 +110,8 @@ ENS_SYMBOLS = ["ocn_ens_plan", "ocn_ens_create", "ocn_ens_destroy", "ocn_ens_siz
                "ocn_ens_assimilate_h", "ocn_ens_spread_save",
                "ocn_ens_inflate", "ocn_ens_inflate_download", "ocn_ens_perturb", "ocn_ens_perturb_download",
                "ocn_ens_record_begin", "ocn_ens_step_record", "ocn_ens_record_info", "ocn_ens_record_download",
-               "ocn_ens_record_end", "ocn_ens_record_due", "ocn_ens_record_sample", "ocn_ens_assimilate_rec"]
+               "ocn_ens_record_end", "ocn_ens_record_due", "ocn_ens_record_sample", "ocn_ens_assimilate_rec",
+               "ocn_ens_set_gate", "ocn_ens_gate_info"]
 ALL_SYMBOLS = KERNEL_SYMBOLS + CTX_SYMBOLS + ENS_SYMBOLS
 ENS_MAX_MEMBERS = 256          # OCN_ENS_MAX_MEMBERS
 ENS_OBS_MAX_TERMS = 16         # OCN_ENS_OBS_MAX_TERMS
@@ -123,6 +124,7 @@ ENS_OPT_RECORD_IN_LAUNCH = 4
 ENS_STATS = {"mean": 1, "var": 2, "spread": 4, "min": 8, "max": 16}
 # OCN_ENS_ASSIM_* (ocn_ens_assimilate_result)
 ENS_ASSIM_SPANS = 6            # (measurements: OCN_ENS_OPT_ASSIM_TIMING)
+ENS_ASSIM_ACCEPTED = 8         # (ocn_ens_set_gate: 1.0 / 0.0 per observation; 7 stays an unknown `what`)
 ENS_ASSIM = {"hx": 0, "y": 1, "z": 2, "innovations": 3, "prior_spread": 4, "posterior_spread": 5}
 # OCN_ENS_INFLATE_* (ocn_ens_inflate's mode; ocn_ens_inflate_download's what)
 ENS_INFLATE_MODE = {"const": 0, "rtps": 1}
@@ -205,6 +207,10 @@ class OcnEnsExtrema(C.Structure):
 
 class OcnEnsAssimInfo(C.Structure):
     _fields_ = [("nobs", C.c_int32), ("n", C.c_int32), ("nonfinite", C.c_int64)]
+
+
+class OcnEnsGateInfo(C.Structure):
+    _fields_ = [("gate2", C.c_double), ("rejected", C.c_int64)]
 
 
 class OcnEnsRecordInfo(C.Structure):
@@ -311,6 +317,8 @@ def lib() -> C.CDLL:
                                        C.c_void_p, C.c_int32]
     L.ocn_ens_assimilate_info.argtypes = [C.c_void_p, C.POINTER(OcnEnsAssimInfo)]
     L.ocn_ens_assimilate_result.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.ocn_ens_set_gate.argtypes = [C.c_void_p, C.c_double]
+    L.ocn_ens_gate_info.argtypes = [C.c_void_p, C.POINTER(OcnEnsGateInfo)]
     L.ocn_ens_spread_save.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.ocn_ens_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double]
     L.ocn_ens_inflate_download.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]

@@ -43,6 +43,10 @@
 // Observations at their own times (ocn_sw.h ocn_ens_record_sample, ocn_ens_assimilate_rec): rec_interp forms hx
 // from the station recorder's series, one gather in time; k_ens_record_sample brings it down, one thread per
 // (observation, member) with the member fastest; k_ens_obs_space_r is the third instance of as_stage.
+//
+// Quality control against the background (ocn_sw.h ocn_ens_set_gate): k_ens_obs_space_g, _hg and _rg are the three
+// instances with as_stage's kGate -- an observation whose squared innovation exceeds gate2 D, or whose D or d is
+// not finite, forms nothing; still ONE launch of ONE workgroup each (see as_stage).
 #include "ocn_internal.h"
 
 namespace ocn {
@@ -122,9 +126,19 @@ __device__ __forceinline__ double rec_interp(const EnsRecSrc &r, int j, int m)
 // the recorder's series r): only the prologue's right-hand side differs.
 constexpr int kAsPoints = 0, kAsOperator = 1, kAsRecords = 2;
 
-template <int kSrc>
-__device__ __forceinline__ void as_stage(const EnsAsArgs a, const EnsObsOp h, const EnsRecSrc r, double *xk, double *yk,
-                                         double *zk)
+// kGate (ocn_sw.h ocn_ens_set_gate; k_ens_obs_space_g, _hg, _rg): after D and d of observation k, every lane forms
+// lim = gate2 * D (one rounded product) and ok = isfinite(D) && isfinite(d) && d * d <= lim from the same LDS copy of
+// row k with the same operations -- the same bits in every lane, so what hangs on ok is workgroup-uniform.  Not ok:
+// Y[k] as formed, Z[k] = +0.0, innovation[k] = d, accept[k] = 0.0, and no row takes observation k; the two barriers
+// behind the stores stand outside the test, so all kAsThreads threads reach them either way and xk is free when it
+// is refilled.  The epilogue walks the update's lists (g.list, every block's, nlist entries) and writes
+// ens_lu_filler() over each entry of a rejected observation: k_ens_local, unchanged and behind this launch on the
+// same stream, rejects a filler on its scalar compares, so no field point takes the observation and a point that
+// only rejected observations reach is not stored.  A filler's own k is 0: accept[0] decides whether a filler is
+// written over it.  Without kGate g is not read and the text is what it was: the ungated kernels keep their bytes.
+template <int kSrc, bool kGate>
+__device__ __forceinline__ void as_stage(const EnsAsArgs a, const EnsObsOp h, const EnsRecSrc r, const EnsAsGate g,
+                                         double *xk, double *yk, double *zk)
 {
     const int tid = (int)threadIdx.x, n = a.n, nobs = a.nobs;
     const long row = a.row;
@@ -179,9 +193,14 @@ __device__ __forceinline__ void as_stage(const EnsAsArgs a, const EnsObsOp h, co
         const double t = r / D;
         const double alpha = 1.0 / (1.0 + sqrt(t));
         const double c = dn1 * D;
+        bool ok = true;
+        if constexpr (kGate) {
+            const double lim = g.gate2 * D;
+            ok = isfinite(D) && isfinite(d) && d * d <= lim;
+        }
         for (int m = tid; m < n; m += kAsThreads) {
             const double ym = x[m] - ybar;
-            const double zm = (d - alpha * ym) / c;
+            const double zm = ok ? (d - alpha * ym) / c : 0.0;
             yk[m] = ym; zk[m] = zm;
             a.y[(long)k * row + m] = ym;
             a.z[(long)k * row + m] = zm;
@@ -189,10 +208,11 @@ __device__ __forceinline__ void as_stage(const EnsAsArgs a, const EnsObsOp h, co
         if (tid == 0) {
             a.innovation[k] = d;
             if (!(isfinite(D) && isfinite(d))) ++bad;
+            if constexpr (kGate) g.accept[k] = ok ? 1.0 : 0.0;
         }
         __syncthreads();   // Y[k], Z[k] in LDS; every lane has read row k
         const int iok = a.io[k], jok = a.jo[k];
-        for (int j = tid; j < nobs; j += kAsThreads) {
+        for (int j = tid; ok && j < nobs; j += kAsThreads) {
             const int di = a.io[j] - iok, dj = a.jo[j] - jok;   // (both within the basin: no overflow)
             if (di > a.reach || -di > a.reach || dj > a.reach || -dj > a.reach) continue;
             const int d2 = di * di + dj * dj;                   // (reach <= 255)
@@ -242,12 +262,23 @@ __device__ __forceinline__ void as_stage(const EnsAsArgs a, const EnsObsOp h, co
 
     for (int j = tid; j < nobs; j += kAsThreads) a.posterior[j] = as_spread(a.hx + (long)j * row, n);
     if (tid == 0) *a.nonfinite = bad;
+    if constexpr (kGate) {
+        // (accept[] is thread 0's, published by the loop's last barrier as the rows are; an entry's k < nobs)
+        for (int q = tid; q < g.nlist; q += kAsThreads)
+            if (g.accept[g.list[q].k] == 0.0) g.list[q] = ens_lu_filler();
+    }
 }
 
 __global__ __launch_bounds__(kAsThreads) void k_ens_obs_space(const EnsAsArgs a)
 {
     __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
-    as_stage<kAsPoints>(a, EnsObsOp{}, EnsRecSrc{}, xk, yk, zk);
+    as_stage<kAsPoints, false>(a, EnsObsOp{}, EnsRecSrc{}, EnsAsGate{}, xk, yk, zk);
+}
+
+__global__ __launch_bounds__(kAsThreads) void k_ens_obs_space_g(const EnsAsArgs a, const EnsAsGate g)
+{
+    __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
+    as_stage<kAsPoints, true>(a, EnsObsOp{}, EnsRecSrc{}, g, xk, yk, zk);
 }
 
 // grid: (observations / 256, members)
@@ -262,7 +293,13 @@ __global__ __launch_bounds__(256) void k_ens_sample_h(const EnsObsOp h, int n, i
 __global__ __launch_bounds__(kAsThreads) void k_ens_obs_space_h(const EnsAsArgs a, const EnsObsOp h)
 {
     __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
-    as_stage<kAsOperator>(a, h, EnsRecSrc{}, xk, yk, zk);
+    as_stage<kAsOperator, false>(a, h, EnsRecSrc{}, EnsAsGate{}, xk, yk, zk);
+}
+
+__global__ __launch_bounds__(kAsThreads) void k_ens_obs_space_hg(const EnsAsArgs a, const EnsObsOp h, const EnsAsGate g)
+{
+    __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
+    as_stage<kAsOperator, true>(a, h, EnsRecSrc{}, g, xk, yk, zk);
 }
 
 // one thread per (observation, member), the member fastest: a wave's series loads and its stores are contiguous
@@ -278,7 +315,13 @@ __global__ __launch_bounds__(256) void k_ens_record_sample(const EnsRecSrc r, in
 __global__ __launch_bounds__(kAsThreads) void k_ens_obs_space_r(const EnsAsArgs a, const EnsRecSrc r)
 {
     __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
-    as_stage<kAsRecords>(a, EnsObsOp{}, r, xk, yk, zk);
+    as_stage<kAsRecords, false>(a, EnsObsOp{}, r, EnsAsGate{}, xk, yk, zk);
+}
+
+__global__ __launch_bounds__(kAsThreads) void k_ens_obs_space_rg(const EnsAsArgs a, const EnsRecSrc r, const EnsAsGate g)
+{
+    __shared__ double xk[OCN_ENS_MAX_MEMBERS], yk[OCN_ENS_MAX_MEMBERS], zk[OCN_ENS_MAX_MEMBERS];
+    as_stage<kAsRecords, true>(a, EnsObsOp{}, r, g, xk, yk, zk);
 }
 
 int launch_ens_obs_space(const EnsAsArgs &a, hipStream_t s)
@@ -325,6 +368,40 @@ int launch_ens_obs_space_r(const EnsAsArgs &a, const EnsRecSrc &r, hipStream_t s
         !a.variance || !a.taper || !a.hx || !a.y || !a.z || !a.innovation || !a.prior || !a.posterior || !a.nonfinite)
         return set_error(OCN_ERR_ARG, "ens_obs_space_r: member count, tables or reach");
     hipLaunchKernelGGL(k_ens_obs_space_r, dim3(1), dim3(kAsThreads), 0, s, a, r);
+    return check_launch();
+}
+
+// what the gated launches check beyond their siblings: a threshold > 0 (not NaN; +inf allowed), the arrays
+static bool as_gate_bad(const EnsAsGate &g) { return !(g.gate2 > 0.0) || !g.accept || !g.list || g.nlist < 0; }
+
+int launch_ens_obs_space_g(const EnsAsArgs &a, const EnsAsGate &g, hipStream_t s)
+{
+    if (a.n < 2 || a.n > OCN_ENS_MAX_MEMBERS || a.nobs < 1 || a.ntaper < 1 || a.reach < 0 || a.reach > 255 ||
+        a.row != (long)ens_lu_row(a.n) || !a.tab || !a.off || !a.blk || !a.io || !a.jo || !a.value || !a.variance ||
+        !a.taper || !a.hx || !a.y || !a.z || !a.innovation || !a.prior || !a.posterior || !a.nonfinite || as_gate_bad(g))
+        return set_error(OCN_ERR_ARG, "ens_obs_space_g: member count, tables, reach or gate");
+    hipLaunchKernelGGL(k_ens_obs_space_g, dim3(1), dim3(kAsThreads), 0, s, a, g);
+    return check_launch();
+}
+
+int launch_ens_obs_space_hg(const EnsAsArgs &a, const EnsObsOp &h, const EnsAsGate &g, hipStream_t s)
+{
+    if (a.n < 2 || a.n > OCN_ENS_MAX_MEMBERS || a.nobs < 1 || a.ntaper < 1 || a.reach < 0 || a.reach > 255 ||
+        a.row != (long)ens_lu_row(a.n) || !h.tab || !h.start || !h.term || !a.io || !a.jo || !a.value || !a.variance ||
+        !a.taper || !a.hx || !a.y || !a.z || !a.innovation || !a.prior || !a.posterior || !a.nonfinite || as_gate_bad(g))
+        return set_error(OCN_ERR_ARG, "ens_obs_space_hg: member count, tables, reach or gate");
+    hipLaunchKernelGGL(k_ens_obs_space_hg, dim3(1), dim3(kAsThreads), 0, s, a, h, g);
+    return check_launch();
+}
+
+int launch_ens_obs_space_rg(const EnsAsArgs &a, const EnsRecSrc &r, const EnsAsGate &g, hipStream_t s)
+{
+    if (a.n < 2 || a.n > OCN_ENS_MAX_MEMBERS || a.nobs < 1 || a.ntaper < 1 || a.reach < 0 || a.reach > 255 ||
+        a.row != (long)ens_lu_row(a.n) || !r.series || !r.obs || !r.col || r.next < 1 || !a.io || !a.jo || !a.value ||
+        !a.variance || !a.taper || !a.hx || !a.y || !a.z || !a.innovation || !a.prior || !a.posterior || !a.nonfinite ||
+        as_gate_bad(g))
+        return set_error(OCN_ERR_ARG, "ens_obs_space_rg: member count, tables, reach or gate");
+    hipLaunchKernelGGL(k_ens_obs_space_rg, dim3(1), dim3(kAsThreads), 0, s, a, r, g);
     return check_launch();
 }
 

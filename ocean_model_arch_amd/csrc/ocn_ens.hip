@@ -60,14 +60,17 @@ struct ocn_ens {
     bool ev_lu_set = false;
     // ocn_ens_assimilate: the call's tables (taper, lists, values, variances, offsets, indices, blocks, the
     // operator's or the recorder's observations, the members' arrays per block), then the device-formed rows hx, y, z and the innovation, prior and
-    // posterior vectors and the count, on the device and in pinned host memory (as_bytes each, grown when a
+    // posterior vectors, the count and the gate's accept flags, on the device and in pinned host memory (as_bytes each, grown when a
     // call needs more; the results come down into h_as at the offsets they have in d_as); ev_as: the stream
     // has read h_as's tables.  as_last: the last successful call's results (nobs 0: none yet)
     void *d_as = nullptr, *h_as = nullptr;
     size_t as_bytes = 0;
     hipEvent_t ev_as = nullptr;
     bool ev_as_set = false;
-    struct AsLast { int nobs = 0, n = 0; size_t row = 0, hx_at = 0, vec_at = 0, count_at = 0; bool timed = false; } as_last;
+    struct AsLast { int nobs = 0, n = 0; size_t row = 0, hx_at = 0, vec_at = 0, count_at = 0; bool timed = false;
+                    size_t accept_at = 0; bool gated = false; } as_last;
+    // ocn_ens_set_gate: the squared threshold of the three entries' quality control (0.0: off, the ungated kernels)
+    double gate2 = 0.0;
     // OCN_ENS_OPT_ASSIM_TIMING: events around the observation-space launch and the update's launches
     bool as_timing = false;
     hipEvent_t ev_t[3] = {nullptr, nullptr, nullptr};
@@ -1097,8 +1100,10 @@ int ocn_ens_local_update(ocn_ens *e, const int32_t *field_ids, int32_t nfields, 
 
 // ------------------------------------------------------------------ the serial filter on the device (ens_assim.hip)
 // Launches per call: kAsLaunches for the observation-space stage (k_ens_obs_space, k_ens_obs_space_h behind a
-// sparse linear observation operator, or k_ens_obs_space_r behind the recorder's series; whatever n and nobs),
-// then ocn_ens_local_update's: one per listed field and block that an observation reaches.
+// sparse linear observation operator, or k_ens_obs_space_r behind the recorder's series; whatever n and nobs; with
+// ocn_ens_set_gate their _g, _hg, _rg instances, which also rewrite the update's lists on the device),
+// then ocn_ens_local_update's: one per listed field and block that an observation reaches -- also with a gate: the
+// host does not know what was rejected.
 constexpr int kAsLaunches = 1;
 static_assert(kAsLaunches == 1, "ocn_sw.h and DESIGN.md state this count");
 
@@ -1197,7 +1202,8 @@ static int ens_as_run(ocn_ens *e, const char *entry, const std::vector<ocn_ctx *
                  col_at = part(robs_at, robs.size() * sizeof(EnsRecObs)), tab_at = part(col_at, col.size() * sizeof(int)),
                  up_b = part(tab_at, src.size() * nblk * n * sizeof(double *)), hx_at = up_b, y_at = part(hx_at, rows_b),
                  z_at = part(y_at, rows_b), vec_at = part(z_at, rows_b), count_at = part(vec_at, 3 * no * 8),
-                 need = part(count_at, sizeof(long));
+                 accept_at = part(count_at, sizeof(long)), need = part(accept_at, no * 8);
+    const bool gated = e->gate2 != 0.0;
     // the buffers first (a failed allocation leaves the members as they were, and no earlier result)
     if (!e->ev_as) HIPCHK(hipEventCreateWithFlags(&e->ev_as, hipEventDisableTiming));
     const bool timed = e->as_timing;
@@ -1250,22 +1256,24 @@ static int ens_as_run(ocn_ens *e, const char *entry, const std::vector<ocn_ctx *
     a.innovation = (double *)(d + vec_at); a.prior = a.innovation + no; a.posterior = a.prior + no;
     a.nonfinite = (long *)(d + count_at);
     a.row = (long)row; a.n = (int)n; a.nobs = nobs; a.ntaper = ntaper; a.reach = reach;
+    // the gate: the lists' device copy, every block's one after another, for the stage's epilogue to rewrite
+    const EnsAsGate g{e->gate2, (double *)(d + accept_at), (EnsLuObs *)(d + list_at0), (int)list_n};
     if (timed) HIPCHK(hipEventRecord(e->ev_t[0], e->stream));
     if (!robs.empty()) {
         const ocn_ens::Recorder &r = e->rec;
         const EnsRecSrc rs{(const double *)r.d_series, (const EnsRecObs *)(d + robs_at), (const int *)(d + col_at),
                            (long)r.nobs * (long)r.n};
-        RC(launch_ens_obs_space_r(a, rs, e->stream));
+        RC(gated ? launch_ens_obs_space_rg(a, rs, g, e->stream) : launch_ens_obs_space_r(a, rs, e->stream));
     } else if (start) {
         const EnsObsOp op{a.tab, (const int *)(d + start_at), (const EnsObsTerm *)(d + term_at)};
-        RC(launch_ens_obs_space_h(a, op, e->stream));
+        RC(gated ? launch_ens_obs_space_hg(a, op, g, e->stream) : launch_ens_obs_space_h(a, op, e->stream));
     } else {
-        RC(launch_ens_obs_space(a, e->stream));
+        RC(gated ? launch_ens_obs_space_g(a, g, e->stream) : launch_ens_obs_space(a, e->stream));
     }
     if (timed) HIPCHK(hipEventRecord(e->ev_t[1], e->stream));
     const int rc = ens_lu_launches(in, field_ids, nfields, lists, d, list_at, a.y, a.z, a.taper, ntaper, reach, e->stream);
     if (timed) HIPCHK(hipEventRecord(e->ev_t[2], e->stream));
-    if (!rc) e->as_last = ocn_ens::AsLast{nobs, (int)n, row, hx_at, vec_at, count_at, timed};
+    if (!rc) e->as_last = ocn_ens::AsLast{nobs, (int)n, row, hx_at, vec_at, count_at, timed, accept_at, gated};
     return rc;
 }
 
@@ -1717,6 +1725,12 @@ int ocn_ens_assimilate_result(ocn_ens *e, int32_t what, double *host)
         memcpy(host, (const char *)e->h_as + at, no * 8);
         return OCN_OK;
     }
+    if (what == OCN_ENS_ASSIM_ACCEPTED) {   // (a call made with the gate off accepted everything: nothing to bring down)
+        if (!l.gated) { std::fill(host, host + no, 1.0); return OCN_OK; }
+        RC(ens_as_down(e, l.accept_at, no * 8));
+        memcpy(host, (const char *)e->h_as + l.accept_at, no * 8);
+        return OCN_OK;
+    }
     if (what == OCN_ENS_ASSIM_SPANS && l.timed) {   // (measurements: the two spans between the call's events, ms)
         HIPCHK(hipSetDevice(e->device));
         HIPCHK(hipEventSynchronize(e->ev_t[2]));
@@ -1728,6 +1742,30 @@ int ocn_ens_assimilate_result(ocn_ens *e, int32_t what, double *host)
         return OCN_OK;
     }
     return set_error(OCN_ERR_ARG, "ens_assimilate_result: what = OCN_ENS_ASSIM_*");
+}
+
+int ocn_ens_set_gate(ocn_ens *e, double gate2)
+{
+    if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    if (gate2 == 0.0) { e->gate2 = 0.0; return OCN_OK; }   // (either sign: off)
+    if (!(gate2 > 0.0)) return set_error(OCN_ERR_ARG, "ens_set_gate: a squared threshold > 0 (+inf allowed), or 0.0 for off");
+    e->gate2 = gate2;
+    return OCN_OK;
+}
+
+int ocn_ens_gate_info(ocn_ens *e, ocn_ens_gate_info_t *out)
+{
+    if (!e || !out) return set_error(OCN_ERR_ARG, "ens_gate_info: null argument");
+    const ocn_ens::AsLast &l = e->as_last;
+    int64_t rejected = 0;
+    if (l.nobs >= 1 && l.gated) {
+        RC(ens_as_down(e, l.accept_at, (size_t)l.nobs * 8));
+        const double *acc = (const double *)((const char *)e->h_as + l.accept_at);
+        for (int k = 0; k < l.nobs; ++k) rejected += acc[k] == 0.0;
+    }
+    out->gate2 = e->gate2;
+    out->rejected = rejected;
+    return OCN_OK;
 }
 
 }  // extern "C"

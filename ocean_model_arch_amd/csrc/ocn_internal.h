@@ -294,7 +294,7 @@ int launch_ens_sample(const double *const *mem, const double *const *d_tab, int 
 constexpr int kLuGroup = 4;   // list entries a wave reads and tests at a time
 constexpr int kLuRow = 8;     // the y and z rows are padded to a multiple of this many doubles
 struct EnsLuObs { int32_t io, jo, k, pad; };
-inline EnsLuObs ens_lu_filler() { return EnsLuObs{-(1 << 30), -(1 << 30), 0, 0}; }   // (its box meets no wave)
+constexpr EnsLuObs ens_lu_filler() { return EnsLuObs{-(1 << 30), -(1 << 30), 0, 0}; }   // (its box meets no wave; host and device)
 inline size_t ens_lu_row(int n) { return (size_t)(n + kLuRow - 1) / kLuRow * kLuRow; }
 int launch_ens_local(const ocn_block *b, double *const *mem, int n, const EnsLuObs *d_list, int ngroups, const double *d_y,
                      const double *d_z, const double *d_taper, int ntaper, int reach, hipStream_t s);
@@ -335,6 +335,18 @@ int launch_ens_record_sample(const EnsRecSrc &r, int n, int nobs, double *d_out,
 // launch_ens_obs_space with the prologue hx[j][m] = the rule's: a.tab, a.off and a.blk are not read.  ONE launch
 // of ONE workgroup of kAsThreads threads.
 int launch_ens_obs_space_r(const EnsAsArgs &a, const EnsRecSrc &r, hipStream_t s);
+// The gate (ocn_sw.h ocn_ens_set_gate) of the three stages above, as an argument of its own behind theirs:
+// EnsAsArgs keeps its layout, so k_ens_obs_space_h's and _r's second argument stays where it is and the ungated
+// kernels keep their bytes.  gate2 > 0 (+inf allowed); accept: nobs doubles, written 1.0 or 0.0; list: the
+// nlist entries of all blocks' lists, the contiguous region ens_lu_put_lists uploads -- the stage's epilogue
+// overwrites each entry of a rejected observation with ens_lu_filler(), and the update's launches, behind it on
+// the same stream, read the rewritten lists (k_ens_local itself is unchanged).
+struct EnsAsGate { double gate2; double *accept; EnsLuObs *list; int nlist; };
+// launch_ens_obs_space, _h and _r with the gate in the loop: their checks, plus gate2, accept and list.  ONE
+// launch of ONE workgroup of kAsThreads threads each.
+int launch_ens_obs_space_g(const EnsAsArgs &a, const EnsAsGate &g, hipStream_t s);
+int launch_ens_obs_space_hg(const EnsAsArgs &a, const EnsObsOp &h, const EnsAsGate &g, hipStream_t s);
+int launch_ens_obs_space_rg(const EnsAsArgs &a, const EnsRecSrc &r, const EnsAsGate &g, hipStream_t s);
 // Covariance inflation (ens_inflate.hip; ocn_sw.h ocn_ens_inflate) of the n arrays mem[0 .. n) (one field of
 // one block geometry, the members in use in member order, n >= 2), in place, at every point of
 // A(bnd_x1:bnd_x2, bnd_y1:bnd_y2).  mode: OCN_ENS_INFLATE_*; d_spread: the saved spread (RTPS; else unused);

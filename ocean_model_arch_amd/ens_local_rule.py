@@ -88,7 +88,38 @@ def local_rule(x, gi, gj, io, jo, y, z, taper):
     return x
 
 
-def ensrf_obs_space(hx, obs_ij, values, variances, taper):
+def gate2_of(gate, who: str = "assimilate"):
+    """The squared threshold ocn_ens_set_gate takes, from a gate in sigma: gate * gate as one float64 product.
+    None stays None (no gate).  TypeError for what is not a number, ValueError unless gate > 0 (inf allowed) and
+    its square is too (0.0 would turn the gate off)."""
+    if gate is None:
+        return None
+    if isinstance(gate, (bool, np.bool_)) or not isinstance(gate, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{who}: gate = {gate!r}, not a number")
+    g = np.float64(gate)
+    with np.errstate(all="ignore"):
+        g2 = g * g
+    if not (g > 0.0 and g2 > 0.0):
+        raise ValueError(f"{who}: gate = {gate!r}, not a float > 0 (inf allowed) whose square is > 0")
+    return float(g2)
+
+
+def _check_gate2(gate2, who):
+    """gate2 as ocn_ens_set_gate takes it with the gate on: > 0 and not NaN, +inf allowed."""
+    if isinstance(gate2, (bool, np.bool_)) or not isinstance(gate2, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{who}: gate2 = {gate2!r}, not a number")
+    if not np.float64(gate2) > 0.0:
+        raise ValueError(f"{who}: gate2 = {gate2!r}, not > 0 (inf allowed)")
+    return np.float64(gate2)
+
+
+def _gate_ok(gate2, D, d):
+    """ocn_ens_set_gate's test: lim = gate2 * D (one rounded product); finite D and d, and d * d <= lim."""
+    lim = gate2 * np.float64(D)
+    return bool(np.isfinite(D) and np.isfinite(d) and np.float64(d) * np.float64(d) <= lim)
+
+
+def ensrf_obs_space(hx, obs_ij, values, variances, taper, gate2=None):
     """The observation-space loop of a serial ensemble square-root filter (Whitaker & Hamill 2002) with a
     taper: from hx, the (nobs, n) members' values at the observed points (i, j) = obs_ij[k], the observed
     values and the observation error variances, the rows Y[k], Z[k] that ocn_ens_local_update needs, and
@@ -99,7 +130,16 @@ def ensrf_obs_space(hx, obs_ij, values, variances, taper):
     Z[k][m] = (d - alpha y'_m) / ((n - 1) D);  then every row -- the observed points are state points like
     any other -- takes observation k by `local_rule`, so the rows stay bit for bit what the device's
     fields hold there.  Returns (Y, Z, info): info["hx"] the final rows, "innovations" the d of each step,
-    "prior_spread" / "posterior_spread" the rows' standard deviations (n - 1) before and after."""
+    "prior_spread" / "posterior_spread" the rows' standard deviations (n - 1) before and after.
+
+    gate2 (None: no gate, nothing changes in any bit or key): ocn_ens_set_gate's squared threshold.  After D and d
+    of observation k, ok = isfinite(D) and isfinite(d) and d * d <= gate2 * D; not ok, the observation is
+    rejected: Y[k] as formed, Z[k] = +0.0, innovations[k] = d, and no row takes it.  The test is against the
+    CURRENT row, so it depends on the order of the observations.  info gains "accepted" (a bool array) and
+    "rejected" (their number)."""
+    if gate2 is not None:
+        gate2 = _check_gate2(gate2, "ensrf_obs_space")
+        accepted = np.ones(len(hx), dtype=bool)
     hx = np.array(hx, dtype=np.float64, copy=True)
     nobs, n = hx.shape
     ij = np.asarray(obs_ij, dtype=np.int64).reshape(nobs, 2)
@@ -119,6 +159,13 @@ def ensrf_obs_space(hx, obs_ij, values, variances, taper):
         r = float(variances[k])
         D = s + r
         d = float(values[k]) - ybar
+        if gate2 is not None:
+            with np.errstate(all="ignore"):
+                accepted[k] = _gate_ok(gate2, D, d)
+            if not accepted[k]:
+                Y[k] = yp
+                innov[k] = d
+                continue
         alpha = 1.0 / (1.0 + np.sqrt(r / D))
         Y[k] = yp
         Z[k] = (d - alpha * yp) / ((n - 1) * D)
@@ -126,7 +173,10 @@ def ensrf_obs_space(hx, obs_ij, values, variances, taper):
         cols = local_rule([hx[:, m] for m in range(n)], ij[:, 0], ij[:, 1], ij[k:k + 1, 0], ij[k:k + 1, 1],
                           Y[k:k + 1], Z[k:k + 1], taper)
         hx = np.stack(cols, axis=1)
-    return Y, Z, {"hx": hx, "innovations": innov, "prior_spread": prior, "posterior_spread": hx.std(axis=1, ddof=1)}
+    info = {"hx": hx, "innovations": innov, "prior_spread": prior, "posterior_spread": hx.std(axis=1, ddof=1)}
+    if gate2 is not None:
+        info["accepted"], info["rejected"] = accepted, int((~accepted).sum())
+    return Y, Z, info
 
 
 def _spread(row):
@@ -145,7 +195,7 @@ def _spread(row):
     return np.sqrt(q / np.float64(n - 1))
 
 
-def ensrf_obs_space_ordered(hx, obs_ij, values, variances, taper):
+def ensrf_obs_space_ordered(hx, obs_ij, values, variances, taper, gate2=None):
     """ocn_ens_assimilate's observation-space loop (include/ocn_sw.h) in numpy, with explicit member loops:
     `ensrf_obs_space` with its two np.sum calls -- whose reduction order is numpy's own -- replaced by sums in
     member order, and the spreads by ocn_ens_stats' ordered definitions.  Every operation is one IEEE double
@@ -155,7 +205,17 @@ def ensrf_obs_space_ordered(hx, obs_ij, values, variances, taper):
     q = y'_0 y'_0, p = y'_m y'_m, q = q + p;  s = q / (n - 1);  D = s + r_k;  d = value_k - ybar;  t = r_k / D;
     alpha = 1 / (1 + sqrt(t));  c = (n - 1) D;  Y[k][m] = y'_m, Z[k][m] = (d - alpha y'_m) / c;  then every row
     takes observation k by `local_rule`.  Returns (Y, Z, info) as `ensrf_obs_space` does; a non-finite row
-    value, D or d propagates, and info["nonfinite"] counts the observations whose D or d was not finite."""
+    value, D or d propagates, and info["nonfinite"] counts the observations whose D or d was not finite.
+
+    gate2 (None: no gate, nothing changes in any bit or key): ocn_ens_set_gate's squared threshold, > 0, inf
+    allowed.  After D and d of observation k:  lim = gate2 * D (one rounded product);  ok = isfinite(D) and
+    isfinite(d) and d * d <= lim.  Not ok, the observation is rejected: Y[k][m] = y'_m as formed, Z[k][m] = +0.0,
+    innovations[k] = d, "nonfinite" counts as ever, and no row takes observation k (a rejected observation forms
+    nothing: no bit of any row changes).  The test is against the CURRENT row, so it depends on the order of the
+    observations.  info gains "accepted" (a bool array) and "rejected" (their number)."""
+    if gate2 is not None:
+        gate2 = _check_gate2(gate2, "ensrf_obs_space_ordered")
+        accepted = np.ones(len(hx), dtype=bool)
     hx = np.array(hx, dtype=np.float64, copy=True)
     nobs, n = hx.shape
     ij = np.asarray(obs_ij, dtype=np.int64).reshape(nobs, 2)
@@ -188,17 +248,25 @@ def ensrf_obs_space_ordered(hx, obs_ij, values, variances, taper):
             t = r / D
             alpha = one / (one + np.sqrt(t))
             c = dn1 * D
+            ok = True
+            if gate2 is not None:
+                ok = accepted[k] = _gate_ok(gate2, D, d)
             for m in range(n):
                 Y[k, m] = yp[m]
-                Z[k, m] = (d - alpha * yp[m]) / c
+                Z[k, m] = (d - alpha * yp[m]) / c if ok else 0.0
             innov[k] = d
             if not (np.isfinite(D) and np.isfinite(d)):
                 nonfinite += 1
+            if not ok:
+                continue
             cols = local_rule([hx[:, m] for m in range(n)], ij[:, 0], ij[:, 1], ij[k:k + 1, 0], ij[k:k + 1, 1],
                               Y[k:k + 1], Z[k:k + 1], taper)
             hx = np.stack(cols, axis=1)
         post = np.array([_spread(hx[j]) for j in range(nobs)])
-    return Y, Z, {"hx": hx, "innovations": innov, "prior_spread": prior, "posterior_spread": post, "nonfinite": nonfinite}
+    info = {"hx": hx, "innovations": innov, "prior_spread": prior, "posterior_spread": post, "nonfinite": nonfinite}
+    if gate2 is not None:
+        info["accepted"], info["rejected"] = accepted, int((~accepted).sum())
+    return Y, Z, info
 
 
 def taper_table(radius: float, kind: str = "gaspari_cohn") -> np.ndarray:

@@ -420,7 +420,7 @@ class OceanEnsemble:
         raise ValueError(f"point ({i}, {j}) lies in no local block's array")
 
     def assimilate(self, name: str, obs_ij, values, variances, taper, names=STATE, members=None, device: bool = False,
-                   rtps=None) -> dict:
+                   rtps=None, gate=None) -> dict:
         """A serial ensemble square-root filter (Whitaker & Hamill 2002) with localization: observations
         `values` of real(8) field `name` at the 1-based global points `obs_ij`, with error variances
         `variances`, assimilated one after another into the fields `names` of the members in use.
@@ -442,27 +442,61 @@ class OceanEnsemble:
         rtps=alpha (a float; None: off): relaxation to prior spread around the analysis -- spread_save(names)
         before it and inflate(alpha, "rtps", names) after it, on either path; with device=True the three calls
         go out back to back with no wait in between.  The returned "hx" and "posterior_spread" describe the
-        analysis BEFORE the relaxation (sample() afterwards gives the relaxed values)."""
+        analysis BEFORE the relaxation (sample() afterwards gives the relaxed values).
+
+        gate=sigma (a float > 0, inf allowed; None: off): quality control against the background inside the loop
+        (ocn_ens_set_gate with gate2 = gate * gate; ens_local_rule.ensrf_obs_space_ordered(gate2=) restates it).  An
+        observation whose squared innovation exceeds gate2 times the innovation variance of the CURRENT row, or
+        whose innovation or innovation variance is not finite, is rejected: it changes no row and no field.  The
+        test depends on the order of the observations, like the loop.  The returned dict gains "accepted" (a
+        bool array) and "rejected" (their number).  device=True sets the ensemble's gate before every call (off
+        without `gate`: a gate never leaks into a later call); device=False runs the gated loop on the host and
+        passes only the accepted observations to local_update().  TypeError for a gate that is not a number,
+        ValueError for one that is not > 0."""
+        gate2 = ens_local_rule.gate2_of(gate, "assimilate")
         if rtps is not None:
             alpha = float(rtps)
             if not np.isfinite(alpha) or alpha < 0.0:
                 raise ValueError(f"assimilate: rtps = {rtps!r}, not a finite float >= 0")
             self.spread_save(names, members=members)
-            info = (self._assimilate_device(name, obs_ij, values, variances, taper, names, members, defer=True) if device else
-                    self.assimilate(name, obs_ij, values, variances, taper, names=names, members=members))
+            info = (self._assimilate_device(name, obs_ij, values, variances, taper, names, members, defer=True, gate2=gate2)
+                    if device else
+                    self.assimilate(name, obs_ij, values, variances, taper, names=names, members=members, gate=gate))
             self.inflate(alpha, "rtps", names, members=members)
             return info() if device else info
         if device:
-            return self._assimilate_device(name, obs_ij, values, variances, taper, names, members)
+            return self._assimilate_device(name, obs_ij, values, variances, taper, names, members, gate2=gate2)
         ij = np.asarray(obs_ij, dtype=np.int64).reshape(-1, 2)
         hx = self.sample(name, [(self.block_of(int(i), int(j)), int(i), int(j)) for i, j in ij], members=members)
-        Y, Z, info = ens_local_rule.ensrf_obs_space(hx, ij, values, variances, taper)
+        Y, Z, info = ens_local_rule.ensrf_obs_space(hx, ij, values, variances, taper, gate2=gate2)
+        if gate2 is not None:   # (a rejected observation forms nothing: the update never sees it)
+            Y, Z, ij = Y[info["accepted"]], Z[info["accepted"]], ij[info["accepted"]]
         for k0 in range(0, len(ij), ens_local_rule.MAX_OBS):
             k1 = k0 + ens_local_rule.MAX_OBS
             self.local_update(Y[k0:k1], Z[k0:k1], ij[k0:k1], np.asarray(taper, dtype=np.float64), names=names, members=members)
         return info
 
-    def _assimilate_device(self, name, obs_ij, values, variances, taper, names, members, defer: bool = False):
+    def _set_gate(self, gate2):
+        """ocn_ens_set_gate ahead of a device call: the call's own gate, or off."""
+        check(lib().ocn_ens_set_gate(self.ens, 0.0 if gate2 is None else gate2), "ocn_ens_set_gate")
+
+    def _gate_results(self, nobs: int):
+        """The last device call's ("accepted", "rejected") (ocn_ens_assimilate_result, ocn_ens_gate_info)."""
+        a = np.zeros(nobs, dtype=np.float64)
+        check(lib().ocn_ens_assimilate_result(self.ens, _lib.ENS_ASSIM_ACCEPTED, a.ctypes.data_as(C.c_void_p)),
+              "ocn_ens_assimilate_result")
+        info = _lib.OcnEnsGateInfo()
+        check(lib().ocn_ens_gate_info(self.ens, C.byref(info)), "ocn_ens_gate_info")
+        return a != 0.0, int(info.rejected)
+
+    def gate_info(self) -> dict:
+        """ocn_ens_gate_info: the ensemble's gate2 as set (0.0: off) and the observations the last successful
+        device call rejected."""
+        info = _lib.OcnEnsGateInfo()
+        check(lib().ocn_ens_gate_info(self.ens, C.byref(info)), "ocn_ens_gate_info")
+        return {"gate2": float(info.gate2), "rejected": int(info.rejected)}
+
+    def _assimilate_device(self, name, obs_ij, values, variances, taper, names, members, defer: bool = False, gate2=None):
         """assimilate(device=True).  defer: return a function that reads the results back, so that the caller
         may issue more work behind the analysis before the first wait (one call's results stay in the
         ensemble's buffers until the next ocn_ens_assimilate; a split list is read back call by call as ever)."""
@@ -489,10 +523,15 @@ class OceanEnsemble:
         ptr = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
         L = lib()
         parts = {k: [] for k in ("hx", "innovations", "prior_spread", "posterior_spread")}
-        nonfinite = 0
+        nonfinite = rejected = 0
+        accepted = []
 
         def read_back(count):   # the last call's results (one wait each)
-            nonlocal nonfinite
+            nonlocal nonfinite, rejected
+            if gate2 is not None:
+                acc, rej = self._gate_results(count)
+                accepted.append(acc)
+                rejected += rej
             for key in parts:
                 a = np.zeros((count, n) if key == "hx" else count, dtype=np.float64)
                 check(L.ocn_ens_assimilate_result(self.ens, _lib.ENS_ASSIM[key], ptr(a)), "ocn_ens_assimilate_result")
@@ -505,6 +544,7 @@ class OceanEnsemble:
         for k0 in range(0, nobs, ens_local_rule.MAX_OBS):
             k1 = min(k0 + ens_local_rule.MAX_OBS, nobs)
             i_, j_, v_, r_ = (np.ascontiguousarray(a[k0:k1]) for a in (io, jo, va, ra))
+            self._set_gate(gate2)
             check(L.ocn_ens_assimilate(self.ens, _lib.FIELD_ID[name], ids, len(names), self._use(members), k1 - k0, ptr(i_),
                                        ptr(j_), ptr(v_), ptr(r_), ptr(ta), len(ta)), "ocn_ens_assimilate")
             if not later:
@@ -523,6 +563,8 @@ class OceanEnsemble:
                 with np.errstate(all="ignore"):
                     out["posterior_spread"] = np.array([ens_local_rule._spread(r) for r in out["hx"]])
             out["nonfinite"] = nonfinite
+            if gate2 is not None:
+                out["accepted"], out["rejected"] = np.concatenate(accepted), rejected
             return out
         return finish if defer else finish()
 
@@ -548,7 +590,8 @@ class OceanEnsemble:
                                      out.ctypes.data_as(C.c_void_p)), "ocn_ens_sample_h")
         return out
 
-    def assimilate_h(self, op, values, variances, taper, names=STATE, members=None, device: bool = False, rtps=None) -> dict:
+    def assimilate_h(self, op, values, variances, taper, names=STATE, members=None, device: bool = False, rtps=None,
+                     gate=None) -> dict:
         """assimilate() for observations that are not one field at one grid point: observation j is `values[j]`,
         with error variance `variances[j]`, of row j of the sparse linear operator `op`
         (ens_obs_rule.ObsOperator) applied to the members; op.anchors[j], an integer point of the basin, is its
@@ -565,18 +608,19 @@ class OceanEnsemble:
         8192 observations raise ValueError on either path and are not split.
 
         rtps=alpha: as in assimilate() -- spread_save(names) before, inflate(alpha, "rtps", names) after, with
-        device=True no wait in between."""
+        device=True no wait in between.  gate=sigma: as in assimilate() -- "accepted" and "rejected" are added."""
+        gate2 = ens_local_rule.gate2_of(gate, "assimilate_h")
         if rtps is not None:
             alpha = float(rtps)
             if not np.isfinite(alpha) or alpha < 0.0:
                 raise ValueError(f"assimilate_h: rtps = {rtps!r}, not a finite float >= 0")
             self.spread_save(names, members=members)
-            info = self._assimilate_h(op, values, variances, taper, names, members, device, defer=True)
+            info = self._assimilate_h(op, values, variances, taper, names, members, device, defer=True, gate2=gate2)
             self.inflate(alpha, "rtps", names, members=members)
             return info()
-        return self._assimilate_h(op, values, variances, taper, names, members, device)
+        return self._assimilate_h(op, values, variances, taper, names, members, device, gate2=gate2)
 
-    def _assimilate_h(self, op, values, variances, taper, names, members, device, defer: bool = False):
+    def _assimilate_h(self, op, values, variances, taper, names, members, device, defer: bool = False, gate2=None):
         """assimilate_h() without the relaxation.  defer: return a function that gives the results, so that the
         caller may issue more work behind the analysis before the device path's first wait."""
         arrays = self._op_arrays(op)
@@ -594,13 +638,16 @@ class OceanEnsemble:
         names = (names,) if isinstance(names, str) else tuple(names)
         if not device:
             hx = self.sample_h(op, members=members)
-            Y, Z, info = ens_local_rule.ensrf_obs_space(hx, op.anchors, va, ra, ta)
-            self.local_update(Y, Z, op.anchors, ta, names=names, members=members)
+            Y, Z, info = ens_local_rule.ensrf_obs_space(hx, op.anchors, va, ra, ta, gate2=gate2)
+            acc = slice(None) if gate2 is None else info["accepted"]
+            if gate2 is None or info["accepted"].any():   # (only the accepted observations reach the update)
+                self.local_update(Y[acc], Z[acc], np.asarray(op.anchors)[acc], ta, names=names, members=members)
             return (lambda: info) if defer else info
         ids = (C.c_int32 * len(names))(*[_lib.FIELD_ID[nm] for nm in names])
         io, jo = (np.ascontiguousarray(op.anchors[:, c], dtype=np.int32) for c in range(2))
         ptr = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
         L = lib()
+        self._set_gate(gate2)
         check(L.ocn_ens_assimilate_h(self.ens, ids, len(names), self._use(members), nobs, ptr(io), ptr(jo),
                                      *[ptr(a) for a in arrays], ptr(va), ptr(ra), ptr(ta), len(ta)), "ocn_ens_assimilate_h")
 
@@ -613,6 +660,8 @@ class OceanEnsemble:
             info = _lib.OcnEnsAssimInfo()
             check(L.ocn_ens_assimilate_info(self.ens, C.byref(info)), "ocn_ens_assimilate_info")
             out["nonfinite"] = int(info.nonfinite)
+            if gate2 is not None:
+                out["accepted"], out["rejected"] = self._gate_results(nobs)
             return out
         return finish if defer else finish()
 
@@ -733,7 +782,7 @@ class OceanEnsemble:
         return out
 
     def assimilate_recorded(self, rows, at, values, variances, taper, anchors=None, names=STATE, members=None,
-                            device: bool = False, rtps=None) -> dict:
+                            device: bool = False, rtps=None, gate=None) -> dict:
         """assimilate_h() for observations taken during the window (first guess at appropriate time, the
         asynchronous ensemble filter of Sakov et al. 2010): observation j is `values[j]`, with error variance
         `variances[j]`, of row rows[j] of the recorded operator at the time at[j] (as in sample_recorded()); the
@@ -749,9 +798,10 @@ class OceanEnsemble:
         perturbation or upload of the same window is stale, and a member that blew up has undefined columns --
         leave it out with `members`.
 
-        rtps=alpha: as in assimilate_h().  TypeError for an argument of the wrong type, ValueError otherwise,
-        more than 8192 observations included."""
+        rtps=alpha, gate=sigma: as in assimilate_h().  TypeError for an argument of the wrong type, ValueError
+        otherwise, more than 8192 observations included."""
         who = "assimilate_recorded"
+        gate2 = ens_local_rule.gate2_of(gate, who)
         if rtps is not None:
             alpha = float(rtps)
             if not np.isfinite(alpha) or alpha < 0.0:
@@ -775,14 +825,17 @@ class OceanEnsemble:
             self.spread_save(names, members=eff)
         if not device:
             hx = ens_record_rule.interp(self.series(), ra, rec, wt, cols)
-            Y, Z, out = ens_local_rule.ensrf_obs_space(hx, ij, va, ra_, ta)
-            self.local_update(Y, Z, ij, ta, names=names, members=eff)
+            Y, Z, out = ens_local_rule.ensrf_obs_space(hx, ij, va, ra_, ta, gate2=gate2)
+            acc = slice(None) if gate2 is None else out["accepted"]
+            if gate2 is None or out["accepted"].any():   # (only the accepted observations reach the update)
+                self.local_update(Y[acc], Z[acc], ij[acc], ta, names=names, members=eff)
             finish = lambda: out   # noqa: E731
         else:
             ids = (C.c_int32 * len(names))(*[_lib.FIELD_ID[nm] for nm in names])
             io, jo = (np.ascontiguousarray(ij[:, c], dtype=np.int32) for c in range(2))
             ptr = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
             L = lib()
+            self._set_gate(gate2)
             check(L.ocn_ens_assimilate_rec(self.ens, ids, len(names), self._use(members), nobs, ptr(io), ptr(jo), ptr(ra),
                                            ptr(rec), ptr(wt), ptr(va), ptr(ra_), ptr(ta), len(ta)), "ocn_ens_assimilate_rec")
 
@@ -795,6 +848,8 @@ class OceanEnsemble:
                 info = _lib.OcnEnsAssimInfo()
                 check(L.ocn_ens_assimilate_info(self.ens, C.byref(info)), "ocn_ens_assimilate_info")
                 out["nonfinite"] = int(info.nonfinite)
+                if gate2 is not None:
+                    out["accepted"], out["rejected"] = self._gate_results(nobs)
                 return out
         if rtps is not None:   # (behind the analysis, before the device path's first wait)
             self.inflate(alpha, "rtps", names, members=eff)

@@ -3,6 +3,7 @@
 one JSON line.
 
     python scripts/ens_assim_bench.py [--members 8,32,64] [--obs 64,1024] [--radius 10] [--steps 20] [--repeats 5]
+                                      [--gate off|inf|SIGMA] [--outliers FRACTION]
 
 The case is scripts/ens_local_bench.py's: the Black Sea fixture's basin (tests/golden, one block), per member
 count M in ONE process an OceanEnsemble of M members perturbed by per-member ssh patterns, after a 2-step and
@@ -18,6 +19,11 @@ every field.  Then, alternating per repeat after one untimed repeat of each:
 
 and, from timed calls (OCN_ENS_OPT_ASSIM_TIMING), the spans of k_ens_obs_space and of the update's launches
 between HIP events on the ensemble's stream.  Reported: median (min - max) in ms over the repeats.
+
+--gate (default off: the ungated kernels, every leg as before): the gate in sigma of every leg (ocn_ens_set_gate;
+assimilate(gate=)), `inf` for the gated kernel that rejects nothing.  --outliers F (with a gate only): every
+round(1 / F)-th observation's value is the members' mean + 1e3, which a finite gate rejects; the result then counts
+the rejected observations of the checked call.
 """
 import argparse
 import json
@@ -38,7 +44,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--case", default="bs_b1x1_s60")
+    ap.add_argument("--gate", default="off")
+    ap.add_argument("--outliers", type=float, default=0.0)
     a = ap.parse_args()
+    gate = None if a.gate == "off" else float(a.gate)
+    if a.outliers and (gate is None or not 0.0 < a.outliers <= 1.0):
+        ap.error("--outliers: a fraction in (0, 1], with a --gate")
+    every = int(round(1.0 / a.outliers)) if a.outliers else 0
 
     import ctypes as C
 
@@ -61,8 +73,11 @@ def main():
 
     taper = taper_table(a.radius)
     out = {"bench": "ens_assim", "case": a.case, "steps": a.steps, "repeats": a.repeats, "fields": list(STATE),
-           "radius": a.radius, "ntaper": len(taper), "ocn_build_id": amd.build_id(), "results": []}
+           "radius": a.radius, "ntaper": len(taper), "ocn_build_id": amd.build_id(), "gate": a.gate, "outliers": a.outliers,
+           "results": []}
     L = amd.lib()
+    kw = {} if gate is None else {"gate": gate}
+    gate2 = None if gate is None else gate * gate
     ids = (C.c_int32 * len(STATE))(*[_lib.FIELD_ID[nm] for nm in STATE])
     for M in [int(x) for x in a.members.split(",")]:
         e = amd.OceanEnsemble(basin, sw, par, members=M).init()
@@ -94,36 +109,43 @@ def main():
 
             def truth():
                 hx = e.sample("ssh", pts)
-                return hx, hx.mean(axis=1) + rng.normal(0.0, 0.01, nobs)
+                values = hx.mean(axis=1) + rng.normal(0.0, 0.01, nobs)
+                if every:
+                    values[::every] = hx.mean(axis=1)[::every] + 1e3
+                return hx, values
 
             # the device against the restatement, bitwise, before anything is timed
             hx, values = truth()
             before = downloads()
-            got = e.assimilate("ssh", ij, values, variances, taper, device=True)
+            got = e.assimilate("ssh", ij, values, variances, taper, device=True, **kw)
             yz = e.assimilate_results(("y", "z"))
             after = downloads()
-            Y, Z, ref = A.ensrf_obs_space_ordered(hx, ij, values, variances, taper)
+            Y, Z, ref = A.ensrf_obs_space_ordered(hx, ij, values, variances, taper, gate2=gate2)
+            acc = ref["accepted"] if gate is not None else np.ones(nobs, dtype=bool)   # (the update takes the accepted alone)
             same = (not A.info_mismatches(got, ref) and A.bits_equal(yz["y"], Y) and A.bits_equal(yz["z"], Z)
+                    and (gate is None or list(got["accepted"]) == list(acc))
                     and all(A.bits_equal(g, v) for nm in STATE
-                            for g, v in zip(after[nm], A.block_update(before[nm], blk, ij[:, 0], ij[:, 1], Y, Z, taper))))
+                            for g, v in zip(after[nm], A.block_update(before[nm], blk, ij[acc, 0], ij[acc, 1], Y[acc], Z[acc], taper))))
 
             def host():
                 _, v = truth()
                 t0 = time.perf_counter()
-                e.assimilate("ssh", ij, v, variances, taper)
+                e.assimilate("ssh", ij, v, variances, taper, **kw)
                 e.synchronize()
                 return 1e3 * (time.perf_counter() - t0)
 
             def device():
                 _, v = truth()
                 t0 = time.perf_counter()
-                e.assimilate("ssh", ij, v, variances, taper, device=True)
+                e.assimilate("ssh", ij, v, variances, taper, device=True, **kw)
                 e.synchronize()
                 return 1e3 * (time.perf_counter() - t0)
 
             def call():
                 _, v = truth()
                 v = np.ascontiguousarray(v)
+                if gate is not None:   # (the Python driver's legs leave it set; an ungated run never names the entry)
+                    amd._lib.check(L.ocn_ens_set_gate(e.ens, gate2), "ocn_ens_set_gate")
                 t0 = time.perf_counter()
                 rc = L.ocn_ens_assimilate(e.ens, _lib.FIELD_ID["ssh"], ids, len(STATE), None, nobs, ptr(io), ptr(jo), ptr(v),
                                           ptr(variances), ptr(taper), len(taper))
@@ -143,7 +165,7 @@ def main():
             spans = {"obs_space_ms": [], "update_ms": []}
             for r in range(a.repeats + 1):
                 _, v = truth()
-                e.assimilate("ssh", ij, v, variances, taper, device=True)
+                e.assimilate("ssh", ij, v, variances, taper, device=True, **kw)
                 sp = e.assimilate_spans()
                 if r:
                     for k in spans:
@@ -152,6 +174,8 @@ def main():
             res = {"members": M, "observations": nobs, "array": list(shape), "update_path": "register" if M <= 32 else "lds",
                    "bitwise_equal_to_restatement": bool(same), "nonfinite": int(got["nonfinite"]),
                    "statuses_ok": not any(e.synchronize())}
+            if gate is not None:
+                res["rejected"] = int(got["rejected"])
             for k, ts in times.items():
                 res[k] = summary(ts)
             res["k_ens_obs_space"] = summary(spans["obs_space_ms"], 5)
