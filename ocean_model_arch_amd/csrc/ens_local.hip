@@ -22,6 +22,11 @@
 //   REG  (n <= kEnsStatsReg): the n values in registers, 256 threads per workgroup.
 //   !REG (beyond): the values in LDS as [member][lane] (lane-consecutive doubles: no bank conflict), one
 //        wave per workgroup, n x 512 B of dynamic LDS.  The same operations in the same order: the same bits.
+//        Up to 128 members that is at most 64 KiB and launches as it stands; 129 .. 256 members need 66 048 B ..
+//        128 KiB of gfx950's 160 KiB, which a kernel gets only after hipFuncSetAttribute(...,
+//        hipFuncAttributeMaxDynamicSharedMemorySize, bytes) -- the launcher sets it per call beyond 64 KiB, and a
+//        refusal is OCN_ERR_HIP, nothing launched.  Observed on the MI355X: the attribute is granted and the kernel
+//        launches at 129, 255 and 256 members (tests/test_gpu_ens_large.py, bitwise; one such workgroup fits a CU).
 // No atomics, no inline assembly.
 #include "ocn_internal.h"
 

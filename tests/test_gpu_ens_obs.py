@@ -91,13 +91,13 @@ def _assim_h_vs_restatement(e, op, taper, names, members=None, seed=0, values=No
 
 
 # ---------------------------------------------------------------- 1. the operator alone
-@pytest.mark.parametrize("n", [2, 9, 33])
-def test_sample_h(amd, ens33, n):
-    """Rows of 1, 4 and 16 terms over three fields, terms in the outer rings (halo and land) and repeated:
-    sample_h() is the restatement on the members' downloads; points() rows are sample()."""
-    e = ens33
-    members = None if n == 33 else range(n)
-    idx = list(range(n))
+def _sample_h_vs_downloads(e, n, members=None):
+    """sample_h() over n members of an ensemble of Shape(61, 9) -- the first n (all of them: `use` NULL), or the n
+    `members` -- against the restatement on their downloads, and points() rows against sample()."""
+    if members is None:
+        members = None if n == len(e) else range(n)
+    idx = list(range(len(e))) if members is None else sorted(set(members))
+    assert len(idx) == n
     rng = np.random.default_rng(n)
     names = ("ssh", "ubrtr", "vbrtr")
     rows = [[("ssh", 30, 6, 1.0)], [("ssh", 1, 1, -0.5)],
@@ -112,6 +112,13 @@ def test_sample_h(amd, ens33, n):
     assert got.shape == (len(rows), n) and O.bits_equal(got, want)
     unit = e.sample_h(O.points("ubrtr", OBS_61x9), members=members)
     assert O.bits_equal(unit, e.sample("ubrtr", _points(e, OBS_61x9), members=members))
+
+
+@pytest.mark.parametrize("n", [2, 9, 33])
+def test_sample_h(amd, ens33, n):
+    """Rows of 1, 4 and 16 terms over three fields, terms in the outer rings (halo and land) and repeated:
+    sample_h() is the restatement on the members' downloads; points() rows are sample()."""
+    _sample_h_vs_downloads(ens33, n)
 
 
 # ---------------------------------------------------------------- 2. unit rows are the grid-point entry
