@@ -89,7 +89,7 @@ module ocn_sw_c
 
     ! the x2 / x4 steps' measured overlap choice (ocn_ctx_overlap_info)
     type, bind(C) :: ocn_overlap_info
-        integer(c_int32_t) :: level, state, kind, pad
+        integer(c_int32_t) :: level, state, kind, probes
         real(c_double) :: seq_ms, overlapped_ms
     end type
 
@@ -293,6 +293,18 @@ module ocn_sw_c
             type(ocn_decomp), intent(in) :: dec
             type(c_ptr), value :: mask, field_ids
             integer(c_int32_t), value :: nfields
+            type(c_ptr), value :: out
+            integer(c_int32_t), value :: cap
+            integer(c_int32_t), intent(out) :: count
+        end function
+        ! the same for the x2 steps' (depth 2) and the x4 pairs' (depth 4) exchanges
+        integer(c_int) function ocn_halo_schedule_deep(basin, dec, mask, field_ids, nfields, depth, out, cap, count) &
+                                                       bind(C, name='ocn_halo_schedule_deep')
+            import :: c_int, c_int32_t, c_ptr, ocn_basin, ocn_decomp
+            type(ocn_basin), intent(in) :: basin
+            type(ocn_decomp), intent(in) :: dec
+            type(c_ptr), value :: mask, field_ids
+            integer(c_int32_t), value :: nfields, depth
             type(c_ptr), value :: out
             integer(c_int32_t), value :: cap
             integer(c_int32_t), intent(out) :: count

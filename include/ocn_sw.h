@@ -238,6 +238,15 @@ typedef struct ocn_halo_msg {
 int ocn_halo_schedule(const ocn_basin *basin, const ocn_decomp *dec, const int32_t *mask,
                       const int32_t *field_ids, int32_t nfields, ocn_halo_msg *out, int32_t cap,
                       int32_t *count);
+/* The same for the exchanges of the x2 steps (depth 2) and the x4 pairs (depth 4), as the device path
+ * plans them: every side strip `depth` columns / rows deep, layer by layer, and depth x depth corner
+ * patches as rows; tracer fields (ids from OCN_TRACER_BASE) go 1 deep, 2 deep in a 4-deep exchange.
+ * depth 1 is ocn_halo_schedule; any other depth than 1, 2 or 4 is OCN_ERR_ARG.  The strips of a
+ * neighbour narrower than the depth reach into that neighbour's own halo (the step machine runs such
+ * exchanges only for h_r's copy). */
+int ocn_halo_schedule_deep(const ocn_basin *basin, const ocn_decomp *dec, const int32_t *mask,
+                           const int32_t *field_ids, int32_t nfields, int32_t depth, ocn_halo_msg *out,
+                           int32_t cap, int32_t *count);
 
 /* Create a context: decomposes the basin (mask = int32 global (nx,ny) column-major, 0 = sea,
  * 1 = land, or NULL for the closed box of tools/io.f90:49-59), allocates every field of every
@@ -278,13 +287,22 @@ int ocn_ctx_comm_info(ocn_ctx *ctx, ocn_comm_info *out);
 /* The x2 / x4 steps' overlap with OCN_OPT_OVERLAP auto (-1) and peers on other ranks: the first step
  * of a sequence's kind (not the one that opens it) runs exchange-then-march, the next the inner part
  * beside the exchange, each timed with events; the next vote max-reduces both times over the ranks
- * and every rank keeps the faster form.  level = the OCN_OPT_OVERLAP level in effect; state 0 =
- * nothing measured, 1 = the sequential step measured, 2 = both (not yet voted), 3 = decided; kind =
- * the form measured (2: x2 steps, 4: x4 pairs); seq_ms / overlapped_ms = the times (after the
- * decision: the maxima over the ranks it used).  The reference's hybrid overlap mode
- * (core/kernel_interface.f90:105-117) has no such choice. */
+ * and every rank keeps the faster form.  Each kind keeps its own pair of measurements (a call that
+ * mixes x4 pairs with a single x2 step loses neither); the first kind every rank has measured in both
+ * forms decides the level of both.  An x4 pair is measured only where every block of the grid, on any
+ * rank, keeps an inner part (the same answer on every rank).  After OCN_OVERLAP_MAX_VOTES (6) votes
+ * without a decision -- calls too short to hold a step that may be timed, ranks that keep disagreeing --
+ * the choice gives up: level 2, the default before there was a measurement, and no further probe.
+ * level = the OCN_OPT_OVERLAP level in effect; state 0 = nothing measured, 1 = the sequential step
+ * measured, 2 = both (not yet voted) -- of the kind measured last --, 3 = decided, 4 = gave up
+ * (level 2); 3 and 4 are final until OCN_OPT_OVERLAP is set again; kind = the form measured last or
+ * decided from (2: x2 steps, 4: x4 pairs); probes = the steps run as timed probes so far (none once
+ * the state is final); seq_ms / overlapped_ms = the times (after the decision: the maxima over the
+ * ranks it used).  The reference's hybrid overlap mode (core/kernel_interface.f90:105-117) has no
+ * such choice. */
+#define OCN_OVERLAP_MAX_VOTES 6
 typedef struct ocn_overlap_info {
-    int32_t level, state, kind, pad;
+    int32_t level, state, kind, probes;
     double seq_ms, overlapped_ms;
 } ocn_overlap_info;
 int ocn_ctx_overlap_info(ocn_ctx *ctx, ocn_overlap_info *out);
@@ -439,7 +457,7 @@ int ocn_ctx_output_r4(ocn_ctx *ctx, int k, int field_id, float undef, float *hos
  *  reference's arrays hold the exchanged state.  Tracer runs (tracer steps): the tracers exchanged two
  *  deep, two tracer steps per exchange -- with 1 only where exchanges go to other ranks, with 3 always.
  *  0 = off.  Same results bit for bit.  ocn_ctx_get_option: 2 if the last ocn_ctx_step used such
- *  launches.
+ *  launches, else the value set (0, 1 or 3).
  *  OCN_OPT_CO_LAUNCH (default 1): tracer runs with x2 steps (one tracer, block batching on): each
  *  step's march -- with OCN_OPT_OVERLAP 2 the part after the exchange -- and the previous state's
  *  tracer step go as ONE launch (their workgroups in one grid) instead of two.  Same results bit for

@@ -96,7 +96,7 @@ KERNEL_SYMBOLS = ["ocn_sw_update_ssh", "ocn_hh_update", "ocn_uv_trans_vort", "oc
                   "ocn_stress_components", "ocn_uv_diff2", "ocn_sw_update_uv", "ocn_sw_next_step",
                   "ocn_hh_shift", "ocn_hh_init", "ocn_check_ssh_err", "ocn_tran_diff_fluxes",
                   "ocn_tran_diff_tracer", "ocn_tracer_next_step"]
-CTX_SYMBOLS = ["ocn_decompose", "ocn_halo_schedule", "ocn_ctx_create", "ocn_ctx_destroy", "ocn_ctx_block_count", "ocn_ctx_block_info",
+CTX_SYMBOLS = ["ocn_decompose", "ocn_halo_schedule", "ocn_halo_schedule_deep", "ocn_ctx_create", "ocn_ctx_destroy", "ocn_ctx_block_count", "ocn_ctx_block_info",
                "ocn_ctx_field", "ocn_ctx_stream", "ocn_comm_unique_id", "ocn_ctx_attach_comm", "ocn_ctx_attach_loopback",
                "ocn_ctx_set_topography", "ocn_ctx_init_state", "ocn_ctx_sync", "ocn_ctx_stage", "ocn_ctx_tracer_stage", "ocn_ctx_step", "ocn_ctx_synchronize",
                "ocn_ctx_download", "ocn_ctx_complete", "ocn_ctx_upload", "ocn_ctx_output_r4", "ocn_ctx_set_option", "ocn_ctx_get_option", "ocn_ctx_stage_times", "ocn_ctx_stage_stats",
@@ -183,7 +183,7 @@ class OcnCommInfo(C.Structure):
 
 
 class OcnOverlapInfo(C.Structure):
-    _fields_ = [("level", C.c_int32), ("state", C.c_int32), ("kind", C.c_int32), ("pad", C.c_int32),
+    _fields_ = [("level", C.c_int32), ("state", C.c_int32), ("kind", C.c_int32), ("probes", C.c_int32),
                 ("seq_ms", C.c_double), ("overlapped_ms", C.c_double)]
 
 
@@ -220,6 +220,7 @@ class OcnEnsRecordInfo(C.Structure):
 
 
 HALO_LOCAL, HALO_SEND, HALO_RECV = 0, 1, 2
+OVERLAP_MAX_VOTES = 6          # OCN_OVERLAP_MAX_VOTES
 
 _lib = None
 
@@ -288,6 +289,8 @@ def lib() -> C.CDLL:
                                 C.c_int32, C.POINTER(C.c_int32)]
     L.ocn_halo_schedule.argtypes = [C.POINTER(OcnBasin), C.POINTER(OcnDecomp), C.c_void_p, C.POINTER(C.c_int32),
                                     C.c_int32, C.POINTER(OcnHaloMsg), C.c_int32, C.POINTER(C.c_int32)]
+    L.ocn_halo_schedule_deep.argtypes = [C.POINTER(OcnBasin), C.POINTER(OcnDecomp), C.c_void_p, C.POINTER(C.c_int32),
+                                         C.c_int32, C.c_int32, C.POINTER(OcnHaloMsg), C.c_int32, C.POINTER(C.c_int32)]
     L.ocn_ens_plan.argtypes = [C.POINTER(OcnBlock), C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.POINTER(OcnEnsGroup),
                                C.c_int32, C.POINTER(C.c_int32)]
     L.ocn_ens_create.argtypes = [C.POINTER(OcnBasin), C.POINTER(OcnSwParams), C.POINTER(OcnDecomp), C.c_void_p,

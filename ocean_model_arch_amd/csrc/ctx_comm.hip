@@ -549,7 +549,7 @@ int allreduce_max(ocn_ctx *c, int32_t *word, hipStream_t s, int words)
         }
     }
     for (hipEvent_t e : evs) HIPCHK(hipStreamWaitEvent(s, e, 0));
-    int32_t *red = c->d_nbad + 48;
+    int32_t *red = c->d_red;
     hipLaunchKernelGGL(k_vote_max, dim3(1), dim3(64), 0, s, v, red);
     RC(check_launch());
     HIPCHK(hipEventRecord(c->lb_ev_b, s));
@@ -654,10 +654,11 @@ int run_sync(ocn_ctx *c, const std::vector<int> &fields, hipStream_t stream, int
 
 extern "C" {
 
-int ocn_halo_schedule(const ocn_basin *basin, const ocn_decomp *dec, const int32_t *mask, const int32_t *field_ids,
-                      int32_t nfields, ocn_halo_msg *out, int32_t cap, int32_t *count)
+int ocn_halo_schedule_deep(const ocn_basin *basin, const ocn_decomp *dec, const int32_t *mask, const int32_t *field_ids,
+                           int32_t nfields, int32_t depth, ocn_halo_msg *out, int32_t cap, int32_t *count)
 {
     if (!field_ids || nfields < 1) return set_error(OCN_ERR_ARG, "no fields");
+    if (depth != 1 && depth != 2 && depth != 4) return set_error(OCN_ERR_ARG, "halo exchanges are 1, 2 or 4 points deep");
     std::vector<int> fields(field_ids, field_ids + nfields);
     for (int id : fields)
         if (id < OCN_SSH || id >= OCN_TRACER_BASE + 3 * kMaxTracers)
@@ -665,7 +666,7 @@ int ocn_halo_schedule(const ocn_basin *basin, const ocn_decomp *dec, const int32
     ocn_ctx *c = nullptr;
     RC(host_ctx(basin, dec, mask, c));
     std::vector<PlanEntry> es;
-    const int rc = plan_entries(c, fields, es);
+    const int rc = plan_entries(c, fields, es, depth);
     delete c;
     RC(rc);
     if (count) *count = (int32_t)es.size();
@@ -678,6 +679,12 @@ int ocn_halo_schedule(const ocn_basin *basin, const ocn_decomp *dec, const int32
         o.offset = e.buf_off; o.count = e.count;
     }
     return OCN_OK;
+}
+
+int ocn_halo_schedule(const ocn_basin *basin, const ocn_decomp *dec, const int32_t *mask, const int32_t *field_ids,
+                      int32_t nfields, ocn_halo_msg *out, int32_t cap, int32_t *count)
+{
+    return ocn_halo_schedule_deep(basin, dec, mask, field_ids, nfields, 1, out, cap, count);
 }
 
 }  // extern "C"

@@ -278,14 +278,16 @@ int allocate(ocn_ctx *c)
         RC(allocate_x2(c, b));
     }
     // d_nbad words: 0 check_ssh_err's count, 16 the fallback check's verdict (d_fbz) and 17 its mu word, 32..47 flags and
-    // the vote (d_flags), 48..55 the loopback vote's reduction, 56 the count's maximum over the ranks
-    // (sync_impl), 61 the multi-step launch's barrier timeout flag; then per block h_r, mu (LBlock::kc)
+    // the vote (d_flags), 56 the count's maximum over the ranks (sync_impl), 61 the multi-step launch's
+    // barrier timeout flag; then per block h_r, mu (LBlock::kc); then the loopback vote's reduction
+    // (d_red: 64 words)
     const size_t kcb = 16 * c->blocks.size();
-    HIPCHK(hipMalloc(&c->d_nbad, 256 + kcb));
+    HIPCHK(hipMalloc(&c->d_nbad, 256 + kcb + 256));
     c->allocs.push_back(c->d_nbad);
     HIPCHK(hipMalloc(&c->d_bar, kMultiBarBytes));
     c->allocs.push_back(c->d_bar);
-    HIPCHK(hipMemsetAsync(c->d_nbad, 0, 256 + kcb, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_nbad, 0, 256 + kcb + 256, c->stream));
+    c->d_red = (int32_t *)((char *)c->d_nbad + 256 + kcb);
     c->d_fbz = c->d_nbad + kFbzWord;   // (and kFbzWord + 1: its mu word)
     c->d_flags = c->d_nbad + 32;
     for (size_t i = 0; i < c->blocks.size(); ++i) c->blocks[i].kc = (double *)((char *)c->d_nbad + 256) + 2 * i;

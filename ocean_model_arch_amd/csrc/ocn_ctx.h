@@ -200,15 +200,23 @@ struct ocn_ctx {
     bool fb_copy = false;
     int overlap = -1;            // OCN_OPT_OVERLAP: 0 none, 1 standard steps, 2 + role-flip steps, -1 auto
     // OCN_OPT_OVERLAP auto with peers on other ranks: the x2 / x4 steps' form (inner part beside the
-    // exchange, or exchange then march) chosen from a measurement (ov_begin): ov_state 0 = nothing
-    // measured, 1 = a sequential step's events recorded, 2 = an overlapped one's too (the next vote
-    // reduces them), 3 = decided (ov_level); ov_kind = the step form measured (2: x2 steps, 4: x4 pairs);
-    // ov_ms = the two step times (this rank's, then the maxima over the ranks the decision used)
-    int ov_state = 0, ov_kind = 0, ov_level = 2;
-    hipEvent_t ov_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // exchange, or exchange then march) chosen from a measurement (ov_begin).  One slot per step form
+    // (ov_slot[0]: x2 steps, [1]: x4 pairs; a call that runs both loses neither's measurement): state 0 =
+    // nothing measured, 1 = a sequential step's events recorded, 2 = an overlapped one's too (the next
+    // vote reduces them).  ov_final 0 = undecided, 3 = decided (ov_level), 4 = gave up after kOvMaxVotes
+    // votes without a decision (level 2, no further probes); ov_kind = the step form measured last or
+    // decided from (2: x2 steps, 4: x4 pairs); ov_votes = the votes taken while undecided; ov_probes =
+    // the steps run as probes; ov_ms = the two step times the decision used (maxima over the ranks)
+    struct OvSlot {
+        int state = 0;
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    };
+    OvSlot ov_slot[2];
+    int ov_final = 0, ov_kind = 0, ov_level = 2, ov_votes = 0, ov_probes = 0;
     double ov_ms[2] = {0.0, 0.0};
     int xdelay_us = 0;           // OCN_OPT_XCHG_DELAY (tests): a device wait before each exchange with remote peers
     int32_t *d_nbad = nullptr;
+    int32_t *d_red = nullptr;    // the loopback vote's reduction (allreduce_max): 64 words behind d_nbad's
     unsigned *d_bar = nullptr;   // the multi-step launch's grid-barrier words (kMultiBarBytes)
     ncclComm_t comm = nullptr;
     bool comm_aborted = false;         // fail_fatal aborted the communicator: calls with exchanges fail
@@ -399,7 +407,10 @@ int run_sync(ocn_ctx *c, const std::vector<int> &fields, hipStream_t stream = nu
 // d_nbad's words of the known-constant check (ctx_setup.hip allocate): the verdict the launches' gates read,
 // and right after it the word FallbackCheck ORs into when mu's one value is not +0.0 (flag[1]; the host's alone)
 constexpr int kFbzWord = 16, kFbzWords = 2;
-constexpr int kVoteWords = 8;   // the role-flip vote (check_coherence): one 0/1 word per condition
+constexpr int kVoteWords = 12;   // the role-flip vote (check_coherence): one word per condition (d_flags has 16)
+// the measured overlap choice gives up after this many votes without a decision (include/ocn_sw.h
+// ocn_overlap_info states the number)
+constexpr int kOvMaxVotes = OCN_OVERLAP_MAX_VOTES;
 int allreduce_max(ocn_ctx *c, int32_t *word, hipStream_t s, int words = 1);
 int nccl_rc(ncclResult_t r, const char *what);
 int fail_fatal(ocn_ctx *c, int rc);

@@ -53,7 +53,7 @@ static int overlap_level(const ocn_ctx *c)
 {
     if (c->overlap >= 0) return c->overlap;
     if (!(has_comm(c) && c->dec.nranks > 1)) return 1;
-    return c->ov_state == 3 ? c->ov_level : 2;   // (measured: ov_begin, check_coherence)
+    return c->ov_final == 3 ? c->ov_level : 2;   // (measured: ov_begin, check_coherence; 4 = gave up: 2)
 }
 
 // The form of an x2 step (kind 2) or an x4 pair (kind 4) under OCN_OPT_OVERLAP auto with peers on
@@ -63,30 +63,44 @@ static int overlap_level(const ocn_ctx *c)
 // check_coherence max-reduces both times over the ranks and keeps the faster form (ov_level) --
 // every rank the same.  Either form runs the same exchange (one group per step or pair), so ranks
 // may differ in form meanwhile; the results are the same bit for bit.
+// Each kind has its own slot (ocn_ctx::ov_slot): a call of pairs that ends in a single x2 step
+// advances both measurements instead of starting each over.  `allow` must be the same on every rank
+// (every rank runs the same step kinds -- the vote sees to that -- so the slots then advance
+// together): not the opening step of a sequence, and for the pairs x4_inner_everywhere, which reads
+// the global block table.  Once the choice is final (decided, or given up after kOvMaxVotes votes) no
+// step is a probe.
 static int ov_begin(ocn_ctx *c, int kind, bool allow, int &probe)
 {
     probe = 0;
     const int lv = overlap_level(c);
-    if (c->overlap >= 0 || !(has_comm(c) && c->dec.nranks > 1) || c->capturing || !allow || c->ov_state >= 2)
+    ocn_ctx::OvSlot &slot = c->ov_slot[kind == 4];
+    // (a kind with both forms measured waits for the next vote: no probe of the other kind meanwhile)
+    if (c->overlap >= 0 || !(has_comm(c) && c->dec.nranks > 1) || c->capturing || !allow || c->ov_final ||
+        c->ov_slot[0].state >= 2 || c->ov_slot[1].state >= 2)
         return lv;
-    for (hipEvent_t &e : c->ov_ev)
+    for (hipEvent_t &e : slot.ev)
         if (!e && hipEventCreate(&e) != hipSuccess) return lv;
-    if (c->ov_state == 0 || c->ov_kind != kind) {
-        c->ov_state = 0;
-        c->ov_kind = kind;
-        probe = 1;
-        return 1;
-    }
-    probe = 2;
-    return 2;
+    probe = slot.state + 1;
+    return probe;   // (probe 1: level 1, in sequence; probe 2: level 2, overlapped)
 }
-// probe's start (end = false) or end event on the context stream; the end advances ov_state
-static int ov_mark(ocn_ctx *c, int probe, bool end)
+// probe's start (end = false) or end event on the context stream; the end advances the kind's slot
+static int ov_mark(ocn_ctx *c, int kind, int probe, bool end)
 {
     if (!probe) return OCN_OK;
-    HIPCHK(hipEventRecord(c->ov_ev[2 * (probe - 1) + (end ? 1 : 0)], c->stream));
-    if (end) c->ov_state = probe;
+    ocn_ctx::OvSlot &slot = c->ov_slot[kind == 4];
+    HIPCHK(hipEventRecord(slot.ev[2 * (probe - 1) + (end ? 1 : 0)], c->stream));
+    if (end) {
+        slot.state = probe;
+        c->ov_kind = kind;
+        ++c->ov_probes;
+    }
     return OCN_OK;
+}
+static void ov_reset(ocn_ctx *c)   // (OCN_OPT_OVERLAP set: measured again)
+{
+    c->ov_slot[0].state = c->ov_slot[1].state = 0;
+    c->ov_final = c->ov_kind = c->ov_votes = 0;
+    c->ov_level = 2;
 }
 
 // ------------------------------------------------------------------ stages (envoke)
@@ -436,10 +450,12 @@ static bool is_flip_field(int id)
 // one-pass / hybrid decisions, so the exchange sequences of all ranks match.
 // kVoteX4: this rank cannot run one_step_x4's pairs (its tables, or the known-constant verdict its host
 // has read for the x2 range) -- every rank then runs the same steps and exchanges
-// kVoteOvSeq / kVoteOvOv: the measured sequential / overlapped step times in us (ov_begin; INT32_MAX
-// from a rank that has not measured both: no decision)
+// kVoteOvSeq / kVoteOvOv (+ 2 for the x4 pairs' slot): the measured sequential / overlapped step times
+// of the x2 steps in us (ov_begin; INT32_MAX from a rank that has not measured both: no decision from
+// that kind)
 enum { kVoteIncoherent = 0, kVoteIneligible, kVoteUdiv, kVoteHhStale, kVoteX2, kVoteX4, kVoteOvSeq, kVoteOvOv,
-       kVoteUsed };
+       kVoteOvSeq4, kVoteOvOv4, kVoteUsed };
+static_assert(kVoteOvSeq4 == kVoteOvSeq + 2 && kVoteOvOv4 == kVoteOvOv + 2, "the overlap slots' vote words");
 static_assert(kVoteUsed <= kVoteWords, "vote words");
 struct VoteIn { bool eligible, udiv_ok, hh_consistent, x2_ok, x4_ok, nv_ok; };
 struct VoteOut { bool udiv_ok, hh_consistent, x2_ok, x4_ok; };
@@ -508,16 +524,18 @@ static int check_coherence(ocn_ctx *c, const VoteIn &in, VoteOut &out)
     host[kVoteX2] = !in.x2_ok;
     // (one word, reduced by maximum: 2 = no pairs here, 1 = pairs but not their inviscid bodies, 0 = both)
     host[kVoteX4] = !in.x4_ok ? 2 : !in.nv_ok ? 1 : 0;
-    host[kVoteOvSeq] = host[kVoteOvOv] = INT32_MAX;
-    if (c->ov_state == 2) {   // both probe steps recorded (ov_begin): their times, in us
-        float ms[2] = {0.f, 0.f};
-        HIPCHK(hipEventSynchronize(c->ov_ev[3]));
-        HIPCHK(hipEventElapsedTime(&ms[0], c->ov_ev[0], c->ov_ev[1]));
-        HIPCHK(hipEventElapsedTime(&ms[1], c->ov_ev[2], c->ov_ev[3]));
-        for (int i = 0; i < 2; ++i) {
-            c->ov_ms[i] = ms[i];
-            host[kVoteOvSeq + i] = (int32_t)std::min(1.0e9, std::max(1.0, std::round(1000.0 * ms[i])));
-        }
+    // the measured overlap choice, while it is open (OCN_OPT_OVERLAP auto, peers on other ranks)
+    const bool ov_open = c->overlap < 0 && has_comm(c) && c->dec.nranks > 1 && !c->ov_final;
+    for (int sl = 0; sl < 2; ++sl) {
+        host[kVoteOvSeq + 2 * sl] = host[kVoteOvOv + 2 * sl] = INT32_MAX;
+        const ocn_ctx::OvSlot &slot = c->ov_slot[sl];
+        if (!ov_open || slot.state != 2) continue;
+        float ms[2] = {0.f, 0.f};   // both probe steps recorded (ov_begin): their times, in us
+        HIPCHK(hipEventSynchronize(slot.ev[3]));
+        HIPCHK(hipEventElapsedTime(&ms[0], slot.ev[0], slot.ev[1]));
+        HIPCHK(hipEventElapsedTime(&ms[1], slot.ev[2], slot.ev[3]));
+        for (int i = 0; i < 2; ++i)
+            host[kVoteOvSeq + 2 * sl + i] = (int32_t)std::min(1.0e9, std::max(1.0, std::round(1000.0 * ms[i])));
     }
     HIPCHK(hipMemcpyAsync(c->d_flags, host, sizeof(host), hipMemcpyHostToDevice, c->stream));
     if (in.eligible)
@@ -547,13 +565,24 @@ static int check_coherence(ocn_ctx *c, const VoteIn &in, VoteOut &out)
     out.x2_ok = w[kVoteX2] == 0 && exch && c->x2;
     c->x2_dev_ok = out.x2_ok;
     out.x4_ok = out.x2_ok && w[kVoteX4] < 2;
-    if (w[kVoteOvSeq] != INT32_MAX && w[kVoteOvOv] != INT32_MAX) {   // every rank measured: the faster form
-        c->ov_ms[0] = 1.0e-3 * w[kVoteOvSeq];
-        c->ov_ms[1] = 1.0e-3 * w[kVoteOvOv];
-        c->ov_level = w[kVoteOvOv] < w[kVoteOvSeq] ? 2 : 1;
-        c->ov_state = 3;
-    } else if (c->ov_state == 2) {   // another rank has not: measure again, together
-        c->ov_state = 0;
+    // every rank takes the same decision from the reduced words: the first kind (x2 steps, then x4
+    // pairs) every rank has measured in both forms decides, the faster form wins; a kind some rank has
+    // not measured is measured again, together; kOvMaxVotes votes without a decision end the choice
+    for (int sl = 0; sl < 2 && ov_open && !c->ov_final; ++sl) {
+        const int32_t seq = w[kVoteOvSeq + 2 * sl], ovl = w[kVoteOvOv + 2 * sl];
+        if (seq != INT32_MAX && ovl != INT32_MAX) {
+            c->ov_ms[0] = 1.0e-3 * seq;
+            c->ov_ms[1] = 1.0e-3 * ovl;
+            c->ov_level = ovl < seq ? 2 : 1;
+            c->ov_kind = sl ? 4 : 2;
+            c->ov_final = 3;
+        } else if (c->ov_slot[sl].state == 2) {
+            c->ov_slot[sl].state = 0;
+        }
+    }
+    if (ov_open && !c->ov_final && ++c->ov_votes >= kOvMaxVotes) {
+        c->ov_final = 4;
+        c->ov_level = 2;
     }
     c->x4_dev_ok = out.x4_ok;
     c->nv_dev_ok = w[kVoteX4] == 0;   // every rank's pairs run the inviscid bodies, or none's
@@ -966,7 +995,7 @@ static int one_step_x2(ocn_ctx *c, double tau, const StepKind &k)
     };
     int probe = 0;
     const int lv = ov_begin(c, 2, !k.x2_save, probe);
-    RC(ov_mark(c, probe, false));
+    RC(ov_mark(c, 2, probe, false));
     if (lv >= 2 && !c->capturing) {
         RC(overlapped_exchange(c, OCN_TIMER_ONEPASS, 2, with_tracers(c, kStateX2), k.x2_save,   // the state two points deep
             [&](const LBlock &b) -> int {
@@ -1005,7 +1034,7 @@ static int one_step_x2(ocn_ctx *c, double tau, const StepKind &k)
         }
         RC(timer_end(c, rec));
     }
-    RC(ov_mark(c, probe, true));
+    RC(ov_mark(c, 2, probe, true));
     // the previous state's tracer step: it reads that state (untouched by the march) and the tracers
     // with their first halo ring, both just exchanged
     RC(run_tracer_step(c, tau));
@@ -1056,6 +1085,29 @@ static int one_step_pair(ocn_ctx *c, double tau, const StepKind &k)
 // 4096^2 overlapped: see DESIGN.md 4.4
 constexpr int kX4BandCols = 116;   // sw_kernels.hip MarchStep::kPairCols
 static Range x4_inner(const LBlock &b) { return inner_range(b, band_cols(b, kX4BandCols, 4), 4); }
+// Whether every kept block of the GRID, on whatever rank, keeps an inner part under an x4 pair: x4_inner's
+// rule from the global block table, so every rank has the same answer (ov_begin's `allow`: a rank whose
+// own blocks all keep one would otherwise measure pairs its peers cannot, and the vote never conclude)
+static bool x4_inner_everywhere(const ocn_ctx *c)
+{
+    auto kept = [&](int bm, int bn) {
+        return bm >= 1 && bm <= c->bnx && bn >= 1 && bn <= c->bny &&
+               c->gblocks[(size_t)(bm - 1) + (size_t)(bn - 1) * c->bnx].rank >= 0;
+    };
+    for (const GBlock &g : c->gblocks) {
+        if (g.rank < 0) continue;
+        auto fed = [&](int dm, int dn) {   // side_fed: the side's neighbour or one of its two diagonal ones
+            for (int t = -1; t <= 1; ++t)
+                if (kept(g.bm + (dm ? dm : t), g.bn + (dn ? dn : t))) return true;
+            return false;
+        };
+        const int w = g.g.nx_end - g.g.nx_start + 1, h = g.g.ny_end - g.g.ny_start + 1;
+        const int ew = w >= 3 * kX4BandCols ? kX4BandCols : 4;   // band_cols
+        if (w - (fed(-1, 0) ? ew : 0) - (fed(1, 0) ? ew : 0) < 1 || h - (fed(0, -1) ? 4 : 0) - (fed(0, 1) ? 4 : 0) < 1)
+            return false;
+    }
+    return true;
+}
 
 // With OCN_OPT_OVERLAP 2 (the default with remote peers; not while capturing): the inner part
 // (x4_inner) on the compute stream beside the exchange on the comm stream (the device's highest
@@ -1117,8 +1169,9 @@ static int one_step_x4(ocn_ctx *c, double tau, const StepKind &k)
         inner_ok = inner_ok && in.m0 <= in.m1 && in.n0 <= in.n1;
     }
     int probe = 0;
-    const int lv = ov_begin(c, 4, !k.x2_save && inner_ok, probe);
-    RC(ov_mark(c, probe, false));
+    // (measured only where every block of the grid keeps one: the same on every rank)
+    const int lv = ov_begin(c, 4, !k.x2_save && x4_inner_everywhere(c), probe);
+    RC(ov_mark(c, 4, probe, false));
     if (lv >= 2 && !c->capturing && inner_ok) {
         RC(overlapped_exchange(c, OCN_TIMER_ONEPASS2, 4, tr ? with_tracers(c, kStateX2) : kStateX2, k.x2_save,   // the state 4 deep
             [&](const LBlock &b) -> int {
@@ -1140,7 +1193,7 @@ static int one_step_x4(ocn_ctx *c, double tau, const StepKind &k)
         }, co));
         RC(timer_end(c, rec));
     }
-    RC(ov_mark(c, probe, true));
+    RC(ov_mark(c, 4, probe, true));
     if (trA) {   // tracer step A (here when not co-launched: after the join, it reads the exchanged halos)
         c->tr_pending = false;
         for (int t = co ? 2 : 1; t <= c->sw.tracer_num; ++t)
@@ -1611,8 +1664,9 @@ extern "C++" int ocn::ctx_destroy(ocn_ctx *c)
     for (void *p : c->allocs) (void)hipFree(p);
     if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    for (hipEvent_t e : c->ov_ev)
-        if (e) (void)hipEventDestroy(e);
+    for (const ocn_ctx::OvSlot &slot : c->ov_slot)
+        for (hipEvent_t e : slot.ev)
+            if (e) (void)hipEventDestroy(e);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_fb) (void)hipEventDestroy(c->ev_fb);
     if (c->h_fbz) (void)hipHostFree(c->h_fbz);
@@ -1710,8 +1764,9 @@ int ocn_ctx_overlap_info(ocn_ctx *c, ocn_overlap_info *out)
     if (!c || !out) return set_error(OCN_ERR_ARG, "null argument");
     *out = ocn_overlap_info{};
     out->level = overlap_level(c);
-    out->state = c->ov_state;
+    out->state = c->ov_final ? c->ov_final : c->ov_kind ? c->ov_slot[c->ov_kind == 4].state : 0;
     out->kind = c->ov_kind;
+    out->probes = c->ov_probes;
     out->seq_ms = c->ov_ms[0];
     out->overlapped_ms = c->ov_ms[1];
     return OCN_OK;
@@ -2567,7 +2622,7 @@ int ocn_ctx_set_option(ocn_ctx *c, int32_t key, int64_t value)
     case OCN_OPT_OVERLAP:
         if (c->overlap != value) drop_graphs(c);
         c->overlap = value < 0 ? -1 : value > 2 ? 2 : (int)value;
-        if (c->overlap < 0) c->ov_state = 0;   // (auto again: measured again)
+        if (c->overlap < 0) ov_reset(c);   // (auto again: measured again)
         return OCN_OK;
     case OCN_OPT_XCHG_DELAY: c->xdelay_us = value < 0 ? 0 : value > 1000000 ? 1000000 : (int)value; return OCN_OK;
     case OCN_OPT_MARCH:
@@ -2639,7 +2694,7 @@ int ocn_ctx_get_option(const ocn_ctx *c, int32_t key, int64_t *value)
     case OCN_OPT_MULTI: *value = c->multi_used ? 2 : c->multi; return OCN_OK;
     case OCN_OPT_TRACER_STEP: *value = c->tr_call ? 2 : c->tr_step; return OCN_OK;
     case OCN_OPT_MULTI_SPIN: *value = c->multi_spin; return OCN_OK;
-    case OCN_OPT_X4: *value = c->x4_used ? 2 : c->x4 ? 1 : 0; return OCN_OK;
+    case OCN_OPT_X4: *value = c->x4_used ? 2 : c->x4; return OCN_OK;   // (0, 1 or 3 as set)
     case OCN_OPT_CO_LAUNCH: *value = c->co_used ? 2 : c->co_launch; return OCN_OK;
     case OCN_OPT_XCHG_DELAY: *value = c->xdelay_us; return OCN_OK;
     case OCN_OPT_INVISCID: *value = c->nv_used ? 2 : c->inviscid; return OCN_OK;

@@ -42,17 +42,17 @@ def decompose(basin: BasinConfig, par: ParallelConfig, rank: int = 0, nranks: in
 
 
 def halo_schedule(basin: BasinConfig, par: ParallelConfig, fields: list[str], rank: int = 0,
-                  nranks: int = 1) -> list[dict]:
+                  nranks: int = 1, depth: int = 1) -> list[dict]:
+    """depth 1: the reference's exchange; 2 / 4: the x2 steps' / x4 pairs' (ocn_halo_schedule_deep)."""
     cb, cd, mask = _c_args(basin, par, rank, nranks)
     mp = None if mask is None else mask.ctypes.data_as(C.c_void_p)
     ids = (C.c_int32 * len(fields))(*[FIELD_ID[f] for f in fields])
     n = C.c_int32()
-    check(lib().ocn_halo_schedule(C.byref(cb), C.byref(cd), mp, ids, len(fields), None, 0, C.byref(n)),
-          "ocn_halo_schedule")
+    check(lib().ocn_halo_schedule_deep(C.byref(cb), C.byref(cd), mp, ids, len(fields), depth, None, 0, C.byref(n)),
+          "ocn_halo_schedule_deep")
     out = (_lib.OcnHaloMsg * max(1, n.value))()
-    check(lib().ocn_halo_schedule(C.byref(cb), C.byref(cd), mp, ids, len(fields), out, n.value, C.byref(n)),
-          "ocn_halo_schedule")
-    inv = {v: k for k, v in FIELD_ID.items()}
-    return [dict(kind=m.kind, peer=m.peer, k=m.k, k_src=m.k_src, field=inv[m.field],
+    check(lib().ocn_halo_schedule_deep(C.byref(cb), C.byref(cd), mp, ids, len(fields), depth, out, n.value,
+                                       C.byref(n)), "ocn_halo_schedule_deep")
+    return [dict(kind=m.kind, peer=m.peer, k=m.k, k_src=m.k_src, field=FIELD_ID.name(m.field),
                  dst=(m.dst_x0, m.dst_x1, m.dst_y0, m.dst_y1), src=(m.src_x0, m.src_x1, m.src_y0, m.src_y1),
                  count=m.count, offset=m.offset) for m in out[:n.value]]

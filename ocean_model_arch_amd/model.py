@@ -175,11 +175,12 @@ class OceanModel:
 
     def overlap_info(self) -> dict:
         """ocn_ctx_overlap_info: the overlap level in effect and, with OCN_OPT_OVERLAP auto and peers on
-        other ranks, the measured choice (state 3 = decided; seq_ms / overlapped_ms = the two step times
-        the vote compared, maxima over the ranks)."""
+        other ranks, the measured choice (state 3 = decided, 4 = gave up after _lib.OVERLAP_MAX_VOTES votes:
+        level 2; probes = the steps run as timed probes so far; seq_ms / overlapped_ms = the two step
+        times the vote compared, maxima over the ranks)."""
         i = _lib.OcnOverlapInfo()
         check(lib().ocn_ctx_overlap_info(self.ctx, C.byref(i)), "ocn_ctx_overlap_info")
-        return {"level": int(i.level), "state": int(i.state), "kind": int(i.kind),
+        return {"level": int(i.level), "state": int(i.state), "kind": int(i.kind), "probes": int(i.probes),
                 "seq_ms": round(float(i.seq_ms), 4), "overlapped_ms": round(float(i.overlapped_ms), 4)}
 
     def clock_info(self, reset: bool = False) -> dict:

@@ -59,6 +59,12 @@ Coast mask kinds (MASK_KINDS; each keeps the 2-point land frame; i, j are the 0-
               configuration
   comb        land where i is odd and j % 5 != 0: channels one point wide, joined every fifth row
   rough_drop  rough plus the two all-land blocks of "drop"
+  east_land   the closed box with the eastern half of the block grid (bm > bnx / 2) all land (not a coast
+              kind: only EMPTY_RANK below uses it)
+
+Rank layouts (RANK_LAYOUTS: a shape over FEWER ranks than it keeps blocks, so a rank holds several
+blocks and a halo plan mixes local copies with messages; rank_blocks restates the library's
+block-to-rank map): tests/test_halo_plan_cpu.py (the plans, on the CPU) and tests/test_gpu_rank_layouts.py.
 """
 import functools
 from typing import NamedTuple, Optional, Tuple
@@ -101,6 +107,34 @@ GRIDS = [Shape(7, 9, (3, 2)), Shape(10, 6, (5, 3)), Shape(5, 3, (5, 3)), Shape(1
 TRACER_GRIDS = [s._replace(tracers=t) for s in (Shape(13, 11, (3, 3)), Shape(17, 19, (2, 2)), DROPPED) for t in (1, 2)]
 RANK_GRIDS = [Shape(7, 9, (3, 2)), Shape(9, 8, (2, 2)), Shape(17, 19, (2, 2))]
 SINGLE_STEPS, GRID_STEPS = 8, 7   # the longest run of the sweep on a shape (calls [2, 6] / [2, 5])
+
+# ---------------------------------------------------------------- several blocks per rank, uneven ranks
+# (shape, nranks); what each reaches (tests/test_shapes_cpu.py asserts it):
+#   17x19 b2x2 / 2   1 x 2 blocks per rank: N / S a local copy, E / W and the diagonals remote; blocks
+#                    8-9 x 9-10, so x4 pairs run
+#   27x27 b3x3 / 3   1 x 3 per rank, the middle rank with peers on both sides; block (2, 2) has all 8
+#                    neighbours, 2 local and 6 remote
+#   36x36 b3x3 drop, rough_drop / 3   ranks hold 2, 2 and 3 blocks: neighbour tables with holes across a
+#                    rank boundary
+#   13x11 b4x2 / 2, 4   2 x 2 and 2 x 1 blocks per rank; blocks 3-4 x 5-6: x2 only, and h_r's copy goes 4
+#                    deep between blocks 3 wide
+#   23x12 b4x1 / 2   widths 5, 6, 6, 6: blocks (2, 1) and (3, 1) are fed from both sides and 6 wide, so
+#                    their x4 inner part is empty -- on BOTH ranks
+#   17x12 b3x1 / 3   one block per rank (the one layout here with as many ranks as blocks), widths 5, 6,
+#                    6: the x4 inner part is empty on rank 1 only -- ranks that differ in what their own
+#                    blocks allow
+#   17x19 b2x2 tr1 / 2, 36x36 b3x3 tr2 rough_drop / 3   tracer runs: with peers, x4 auto runs pairs with
+#                    tracer steps; the co-launch covers a rank's several blocks
+RANK_LAYOUTS = [(Shape(17, 19, (2, 2)), 2), (Shape(27, 27, (3, 3)), 3), (DROPPED, 3),
+                (Shape(36, 36, (3, 3), 0, "rough_drop"), 3), (Shape(13, 11, (4, 2)), 2), (Shape(13, 11, (4, 2)), 4),
+                (Shape(23, 12, (4, 1)), 2), (Shape(17, 12, (3, 1)), 3), (Shape(17, 19, (2, 2), 1), 2),
+                (Shape(36, 36, (3, 3), 2, "rough_drop"), 3)]
+# blocks (3, 1) and (4, 1) all land: over 2 ranks rank 1 owns no block (the reference allows it)
+EMPTY_RANK = (Shape(40, 12, (4, 1), 0, "east_land"), 2)
+
+
+def layout_id(shape, nranks):
+    return f"{shape.id}-r{nranks}"
 
 # ---------------------------------------------------------------- the coastline sweep's shapes
 # (tests/test_gpu_coast.py; the smallest shapes of the sweep above at which each tile edge exists)
@@ -202,9 +236,14 @@ def _mask(shape):
     elif kind == "comb":
         land = (i % 2 == 1) & (j % 5 != 0)
     else:
-        assert kind == "drop", kind
+        assert kind in ("drop", "east_land"), kind
         land = np.zeros((W, H), dtype=bool)
     m[2:-2, 2:-2] = land
+    if kind == "east_land":
+        for bm in range(shape.grid[0] // 2 + 1, shape.grid[0] + 1):
+            for bn in range(1, shape.grid[1] + 1):
+                x0, y0, w, h = _block_origin(shape, bm, bn)
+                m[x0:x0 + w, y0:y0 + h] = 1
     if kind in ("drop", "rough_drop"):
         for bm, bn in [((shape.grid[0] + 1) // 2, (shape.grid[1] + 1) // 2), (1, 1)]:
             x0, y0, w, h = _block_origin(shape, bm, bn)
@@ -229,6 +268,35 @@ def dropped_blocks(shape):
             if m[x0:x0 + w, y0:y0 + h].all():
                 out.append((bm, bn))
     return out
+
+
+def kept_blocks(shape):
+    """(bm, bn) of the blocks the decomposition keeps, in global (column-major) order."""
+    drop = set(dropped_blocks(shape))
+    return [(bm, bn) for bn in range(1, shape.grid[1] + 1) for bm in range(1, shape.grid[0] + 1) if (bm, bn) not in drop]
+
+
+def dims_create(n):
+    """MPI_Dims_create(n, 2) as ctx_setup.hip dims_create restates it: balanced, non-increasing factors."""
+    f = int(np.floor(np.sqrt(n)))
+    while n % f:
+        f -= 1
+    return n // f, f
+
+
+def rank_blocks(shape, nranks):
+    """The library's block-to-rank map (ctx_setup.hip decompose after the reference's
+    create_uniform_decomposition): per rank the sorted (bm, bn) of its blocks -- the process grid
+    p1 x p2 = MPI_Dims_create(nranks), a rank's patch bnx / p1 x bny / p2 blocks, rank = c1 p2 + c2 of the
+    patch coordinates, dropped blocks left out (a rank may be left with none)."""
+    p1, p2 = dims_create(nranks)
+    bnx, bny = shape.grid
+    assert bnx % p1 == 0 and bny % p2 == 0, (shape.grid, nranks)
+    lbx, lby = bnx // p1, bny // p2
+    out = [[] for _ in range(nranks)]
+    for bm, bn in kept_blocks(shape):
+        out[((bm - 1) // lbx) * p2 + (bn - 1) // lby].append((bm, bn))
+    return [sorted(b) for b in out]
 
 
 def min_block(shape):

@@ -45,7 +45,7 @@ def test_python_binding_covers_header(lib):
 
 STRUCTS = {"ocn_block": "OcnBlock", "ocn_basin": "OcnBasin", "ocn_sw_params": "OcnSwParams",
            "ocn_decomp": "OcnDecomp", "ocn_block_info": "OcnBlockInfo", "ocn_halo_msg": "OcnHaloMsg",
-           "ocn_comm_info": "OcnCommInfo"}
+           "ocn_comm_info": "OcnCommInfo", "ocn_overlap_info": "OcnOverlapInfo"}
 
 
 def test_struct_layouts(tmp_path):

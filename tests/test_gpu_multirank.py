@@ -1,5 +1,7 @@
 """GPU parity of the multi-rank path (one block per rank, halos between ranks) and of the
-BASELINE.json configurations at full size, against the reference.
+BASELINE.json configurations at full size, against the reference.  (Ranks that hold several blocks,
+different numbers and sizes of them: tests/test_gpu_rank_layouts.py; the overlap choice on uneven ranks
+and short calls: tests/test_gpu_x4.py.)
 
 The ranks run as contexts of this one process on the one GPU, joined by the library's loopback
 transport (ocn_ctx_attach_loopback), each driven by its own host thread.  The loopback replaces
@@ -356,13 +358,14 @@ def test_random_rank_sequences_match_oracle(amd, tracers, seed):
     _ranks_sequence(amd, seed, 20, tracers=tracers)
 
 
-def _ranks_sequence(amd, seed, nops=20, tracers=0, n=120, grid=(2, 2)):
-    """The same over loopback ranks (one block per rank, the RCCL path's plans, votes and
-    exchanges): every rank runs the same seeded op list on its block; the oracle replays it after."""
+def _ranks_sequence(amd, seed, nops=20, tracers=0, n=120, grid=(2, 2), nranks=None):
+    """The same over loopback ranks (the RCCL path's plans, votes and exchanges; one block per rank, or
+    with nranks below the grid's block count several: tests/test_gpu_rank_layouts.py): every rank runs the
+    same seeded op list on its blocks; the oracle replays it after."""
     import numpy as np
     from tests.test_gpu_parity import OracleTwin, bits_equal
     rng = np.random.default_rng(seed)
-    nranks = grid[0] * grid[1]
+    nranks = nranks or grid[0] * grid[1]
     ops = []
     for _ in range(nops):
         op = str(rng.choice(["step", "step", "step", "tau", "sync", "read", "ssh", "hr", "kc", "uv", "mu", "rhs",

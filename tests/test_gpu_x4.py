@@ -251,3 +251,100 @@ def test_overlap_choice_is_measured_and_voted(amd, delay_us):
     assert i0["level"] == (2 if i0["overlapped_ms"] < i0["seq_ms"] else 1), last
     if delay_us:
         assert i0["seq_ms"] > delay_us * 1e-3 and i0["overlapped_ms"] > 0.0, last
+
+
+# ---------------------------------------------------------------- the overlap choice settles
+def _overlap_settles(amd, shape, nranks, first, n):
+    """OCN_OPT_OVERLAP auto over loopback ranks on the `noise` class: first calls of `first` steps, a
+    synchronize() after each, then calls of n steps -- OVERLAP_MAX_VOTES voting calls in all
+    (ocn_overlap_info: the bound after which the choice is final one way or the other), then two more.
+    Returns per rank the overlap_info after every call; every field of every block is compared bitwise
+    with the oracle."""
+    from ocean_model_arch_amd._lib import OVERLAP_MAX_VOTES
+    from tests import shapes as S
+    from tests.test_gpu_shapes import _model
+    calls = list(first) + [n] * (OVERLAP_MAX_VOTES - len(first) + 2)
+    models = [_model(amd, shape, rank=r, nranks=nranks) for r in range(nranks)]
+    ups = S.uploads_for(shape, "noise")
+
+    def body(m):
+        m.init()
+        for b in m.blocks:
+            for nm, a in ups.get((b.bm, b.bn), {}).items():
+                m.upload(b.k, nm, a)
+        infos = []
+        for i, k in enumerate(calls):
+            m.step(k, tau=1.0, check_every=1)
+            if i < len(first):
+                m.synchronize()
+            infos.append(m.overlap_info())
+        m.synchronize()
+        return infos
+
+    try:
+        amd.OceanModel.attach_loopback(models)
+        infos = amd.run_ranks(models, body)
+        bad = S.mismatches(S.reference(shape, "noise", sum(calls)), S.model_getter(models))
+    finally:
+        for m in models:
+            m.close()
+    print("overlap", shape.id, nranks, calls, [[(i["state"], i["level"], i["kind"], i["probes"]) for i in r] for r in infos])
+    assert not bad, f"{shape.id} over {nranks} ranks {calls}: fields differ from the oracle: {bad}"
+    at = OVERLAP_MAX_VOTES - 1   # the info after the last of the bounded voting calls
+    for r in infos:
+        assert r[at]["state"] in (3, 4), (r[at], "not final after OVERLAP_MAX_VOTES voting calls")
+        assert r[at]["state"] == 3 or r[at]["level"] == 2, r[at]   # (gave up: level 2)
+        for later in r[at + 1:]:   # final: neither the state nor the level moves, and no step is a probe
+            assert (later["state"], later["level"], later["kind"], later["probes"]) == \
+                (r[at]["state"], r[at]["level"], r[at]["kind"], r[at]["probes"]), (r[at], later)
+    assert len({(r[at]["state"], r[at]["level"], r[at]["probes"]) for r in infos}) == 1, [r[at] for r in infos]
+    return infos
+
+
+@pytest.mark.parametrize("first", [(2,), (2, 2)], ids=["first2", "first2_2"])
+@pytest.mark.parametrize("w,h,grid,nranks", [(17, 12, (3, 1), 3), (23, 12, (4, 1), 2), (17, 19, (2, 2), 4)])
+def test_overlap_choice_settles_on_uneven_ranks(amd, w, h, grid, nranks, first):
+    """Ranks whose blocks differ in what they allow (tests/shapes.py RANK_LAYOUTS: the x4 inner part is
+    empty on rank 1 only / on a block of each rank; 2 x 2 equal blocks beside them) and calls of 6 steps,
+    which mix x4 pairs with a single x2 step: the measured choice (ocn_ctx.hip ov_begin, check_coherence)
+    must become final on every rank, the same level everywhere, and no step be a probe after that.
+    first2: one 2-step call, then the 6-step calls -- the first of those runs x2 steps only (the known-
+    constant verdict reaches the vote a call later), which is enough to measure both forms of the x2 kind
+    before any pair runs.  first2_2: two 2-step calls, each followed by synchronize() -- the pairs run from
+    the first 6-step call on, so every measuring call mixes the two kinds (and on 17 x 12 the ranks
+    differ in whether their own blocks could overlap a pair): the case the choice once never left."""
+    from tests import shapes as S
+    _overlap_settles(amd, S.Shape(w, h, grid), nranks, first, 6)
+
+
+@pytest.mark.parametrize("first", [(2,), (2, 2)], ids=["first2", "first2_2"])
+@pytest.mark.parametrize("n", [5, 3])
+def test_overlap_choice_settles_with_short_calls(amd, n, first):
+    """Calls [2, 5, 5, ...] and [2, 3, 3, ...] on 2 x 2 blocks over 4 ranks (first2_2: [2, 2, 5, ...] and
+    [2, 2, 3, ...] with the pairs from the first longer call on): a call of 3 steps with pairs is an opening
+    pair and the last step -- no step that may be timed -- so the choice has to give up (state 4, level 2)
+    unless the x2 steps before the first pairs were enough to decide."""
+    from tests import shapes as S
+    _overlap_settles(amd, S.Shape(17, 19, (2, 2)), 4, first, n)
+
+
+def test_x4_option_reads_back_as_set(amd):
+    """ocn_ctx_get_option(OCN_OPT_X4): 0, 1 or 3 as set while the last call ran no pairs, 2 after one that
+    did (x4_active)."""
+    from ocean_model_arch_amd import _lib
+    m = amd.OceanModel(amd.box_config(40), par=amd.ParallelConfig(2, 2))
+    try:
+        assert m.option(_lib.OPT_X4) == 1 and not m.x4_active
+        for on, want in ((3, 3), (False, 0), (True, 1), (0, 0), (3, 3)):
+            m.set_x4(on)
+            assert m.option(_lib.OPT_X4) == want and not m.x4_active, (on, want)
+        m.init()
+        m.step(2, check_every=1).synchronize()
+        m.step(6, check_every=1)
+        assert m.x4_active and m.option(_lib.OPT_X4) == 2
+        m.set_x4(False)
+        m.step(3, check_every=1)
+        assert not m.x4_active and m.option(_lib.OPT_X4) == 0
+        m.synchronize()
+    finally:
+        m.close()

@@ -9,6 +9,10 @@ or by leaving zeros.  The comparison helper must name exactly the block and fiel
 The same for the coastline sweep (tests/test_gpu_coast.py): every (shape, mask, class) it runs is finite
 and trips no check_ssh_err; the still class stays below udiv's range after every step; every mask kind
 has what it promises (tests/shapes.py MASK_KINDS) and a land / sea change across the tiles' column edges.
+
+The rank layouts (tests/shapes.py RANK_LAYOUTS) hold what their table promises: the per-rank block lists
+of rank_blocks are the library's own (domain.decompose, every rank), blocks with local and remote
+neighbours at once, and the blocks whose x4 inner part is empty.
 """
 import numpy as np
 import pytest
@@ -207,3 +211,87 @@ def test_coast_dropped_blocks_come_from_the_mask():
     # the masks are functions of (W, H): the same array again, and a caller's copy
     a, b = S.mask_of(S.COAST_DROPPED), S.mask_of(S.COAST_DROPPED)
     assert a is not b and np.array_equal(a, b)
+
+
+# ---------------------------------------------------------------- the rank layouts (several blocks per rank)
+LAYOUTS = S.RANK_LAYOUTS + [S.EMPTY_RANK]
+LAYOUT_IDS = [S.layout_id(s, n) for s, n in LAYOUTS]
+# blocks per rank, in rank order
+LAYOUT_COUNTS = {"17x19_b2x2-r2": [2, 2], "27x27_b3x3-r3": [3, 3, 3], "36x36_b3x3_drop-r3": [2, 2, 3],
+                 "36x36_b3x3_rough_drop-r3": [2, 2, 3], "13x11_b4x2-r2": [4, 4], "13x11_b4x2-r4": [2, 2, 2, 2],
+                 "23x12_b4x1-r2": [2, 2], "17x12_b3x1-r3": [1, 1, 1], "17x19_b2x2_tr1-r2": [2, 2],
+                 "36x36_b3x3_tr2_rough_drop-r3": [2, 2, 3], "40x12_b4x1_east_land-r2": [2, 0]}
+# the kept blocks whose x4 inner part is empty, on the layouts where x4 pairs can run at all
+EMPTY_X4_INNER = {"23x12_b4x1-r2": [(2, 1), (3, 1)], "17x12_b3x1-r3": [(2, 1)]}
+SIDES = {1: (5, 6), 2: (7, 8), 3: (5, 7), 4: (6, 8)}   # side -> its two diagonals (ocn_ctx.hip side_fed)
+
+
+def _decomposed(shape, nranks):
+    import ocean_model_arch_amd as amd
+    from ocean_model_arch_amd import domain
+    basin = amd.BasinConfig(mask=S.mask_of(shape), **S.basin_kwargs(shape))
+    return [domain.decompose(basin, amd.ParallelConfig(*shape.grid), r, nranks) for r in range(nranks)]
+
+
+def _x4_inner_empty(b):
+    """ocn_ctx.hip x4_inner restated for blocks narrower than 3 x 116: the interior less 4 on each side
+    fed by a neighbour (the side's own or one of its two diagonal ones)."""
+    fed = {s: any(b.nbr_rank[d - 1] >= 0 for d in (s,) + SIDES[s]) for s in SIDES}
+    w, h = b.nx_end - b.nx_start + 1, b.ny_end - b.ny_start + 1
+    assert w < 3 * 116
+    return w - 4 * (fed[1] + fed[2]) < 1 or h - 4 * (fed[3] + fed[4]) < 1
+
+
+@pytest.mark.parametrize("shape,nranks", LAYOUTS, ids=LAYOUT_IDS)
+def test_rank_layouts_have_what_they_promise(shape, nranks):
+    lid = S.layout_id(shape, nranks)
+    want = S.rank_blocks(shape, nranks)
+    ranks = _decomposed(shape, nranks)
+    assert [sorted((b.bm, b.bn) for b in blocks) for blocks in ranks] == want
+    assert [len(w) for w in want] == LAYOUT_COUNTS[lid]
+    assert sorted(sum(want, [])) == sorted(S.kept_blocks(shape))
+    if (shape, nranks) != S.EMPTY_RANK and lid != "17x12_b3x1-r3":
+        assert nranks < len(S.kept_blocks(shape))
+    # a block with a local AND a remote neighbour: every layout with several blocks on a rank
+    mixed = [(b.bm, b.bn) for r, blocks in enumerate(ranks) for b in blocks
+             if any(q == r for q in b.nbr_rank) and any(q >= 0 and q != r for q in b.nbr_rank)]
+    assert bool(mixed) == (max(LAYOUT_COUNTS[lid]) > 1 and (shape, nranks) != S.EMPTY_RANK), mixed
+    empty = sorted((b.bm, b.bn) for blocks in ranks for b in blocks if _x4_inner_empty(b))
+    if S.expect_x4(shape, "noise", 1, peers=True):
+        assert empty == EMPTY_X4_INNER.get(lid, []), empty
+    else:
+        assert shape.W == 13 and empty   # (blocks 3 wide: no pairs at all)
+
+
+def test_rank_layout_details():
+    by = {S.layout_id(s, n): _decomposed(s, n) for s, n in S.RANK_LAYOUTS}
+    # 17x19 over 2: N / S local, E / W and the diagonals remote (oracle.DIRS: 1 E, 2 W, 3 N, 4 S, 5 .. 8 diagonals)
+    for r, blocks in enumerate(by["17x19_b2x2-r2"]):
+        for b in blocks:
+            have = {d: q for d, q in enumerate(b.nbr_rank, 1) if q >= 0}
+            assert len(have) == 3 and all((q == r) == (d in (3, 4)) for d, q in have.items()), (b.bm, b.bn, have)
+    # 27x27 over 3: the middle block has all 8 neighbours, 2 local and 6 remote
+    mid = [b for b in by["27x27_b3x3-r3"][1] if (b.bm, b.bn) == (2, 2)][0]
+    assert sorted(mid.nbr_rank) == [0, 0, 0, 1, 1, 2, 2, 2]
+    # the dropped layouts: a hole across a rank boundary (block (1, 2) on rank 0 misses (2, 2) of rank 1)
+    for lid in ("36x36_b3x3_drop-r3", "36x36_b3x3_rough_drop-r3"):
+        b12 = [b for b in by[lid][0] if (b.bm, b.bn) == (1, 2)][0]
+        assert b12.nbr_rank[0] == -1 and b12.nbr_rank[5 - 1] == 1 and b12.nbr_rank[6 - 1] == 1, b12.nbr_rank
+    # 13x11 b4x2: x2 only, blocks 3 wide exist
+    s = S.Shape(13, 11, (4, 2))
+    assert S.block_sizes(s) == ([3, 3, 3, 4], [5, 6]) and S.expect_x2(s) and not S.expect_x4(s, "noise", 1, peers=True)
+    assert S.block_sizes(S.Shape(23, 12, (4, 1)))[0] == [5, 6, 6, 6] and S.block_sizes(S.Shape(17, 12, (3, 1)))[0] == [5, 6, 6]
+    assert S.dims_create(2) == (2, 1) and S.dims_create(3) == (3, 1) and S.dims_create(4) == (2, 2) and S.dims_create(8) == (4, 2)
+    # the rank without blocks
+    assert S.rank_blocks(*S.EMPTY_RANK) == [[(1, 1), (2, 1)], []]
+    assert sorted(S.dropped_blocks(S.EMPTY_RANK[0])) == [(3, 1), (4, 1)]
+
+
+@pytest.mark.parametrize("shape,nranks", S.RANK_LAYOUTS, ids=LAYOUT_IDS[:-1])
+def test_rank_layout_inputs_are_sound(shape, nranks):
+    """The classes tests/test_gpu_rank_layouts.py runs on the layouts not in the sweeps above."""
+    for cls in ("noise", "general") if shape.tracers else ("noise", "hr", "general"):
+        ref = S.reference(shape, cls, S.GRID_STEPS)   # raises FloatingPointError on a blow-up
+        for (bm, bn), f in ref.items():
+            for nm, a in f.items():
+                assert np.isfinite(a).all(), f"{cls} ({bm},{bn}):{nm} not finite"
