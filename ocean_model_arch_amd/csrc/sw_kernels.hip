@@ -2885,6 +2885,51 @@ static int nonnull(std::initializer_list<const void *> ps)
 
 #define RC_K(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 
+// ------------------------------------------------------------------ what the one-pass launchers share
+// tau = 2^k (MarchStep P2), with 1 / tau well inside the normal range
+static bool tau_is_pow2(double tau)
+{
+    int ex;
+    return std::frexp(tau, &ex) == 0.5 && ex > -1020 && ex < 1020;
+}
+
+// the switches every one-pass body is written for
+static bool onepass_switches(const ocn_sw_params &sw)
+{
+    return sw.full_free_surface == 1 && sw.trans_terms > 0 && sw.ksw_lat > 0;
+}
+// the launchers' common preconditions: the compact tables with the march, the switches, the three second
+// buffers -- and `more`, the caller's further conditions, which `tail` names in its message
+static int onepass_check(const char *who, const Compact *cp, const ocn_sw_params &sw, const double *sshp,
+                         const double *up, const double *vp, bool more = true, const char *tail = "")
+{
+    if (cp && cp->march && onepass_switches(sw) && sshp && up && vp && more) return OCN_OK;
+    return set_error(OCN_ERR_ARG, std::string(who) + ": compact tables, march, full_free_surface = 1, trans_terms and "
+                                                     "ksw_lat on, three second buffers" + tail);
+}
+
+// From a launch's run-time choices -- tau a power of two, the variant chosen on the host (OCN_KC_KNOWN,
+// OCN_KC_KNOWN_HR, OCN_KC_GENERAL) -- to the body's <P2, ZF, HR>: f(BodyTag<Body>{}), the launcher's fixed
+// arguments in the other places.  The bodies without NV go by MarchStep (see MarchStepT).  The inviscid and the
+// x4 bodies exist as known-constant variants only (MarchStepT's static_asserts): for them every mode but
+// OCN_KC_KNOWN_HR is OCN_KC_KNOWN (their launchers have refused the others).
+template <class T> struct BodyTag { using type = T; };
+template <bool P2, bool LAST, bool ZF, bool X2, bool HR, bool PAIR, bool WT, bool NV>
+using StepBody = std::conditional_t<NV, MarchStepT<P2, LAST, ZF, X2, HR, PAIR, WT, true>,
+                                    MarchStep<P2, LAST, ZF, X2, HR, PAIR, WT>>;
+template <bool LAST, bool X2, bool PAIR, bool WT, bool NV, class F> static auto step_dispatch(bool p2, int kc_mode, F &&f)
+{
+    if (kc_mode == OCN_KC_KNOWN_HR)
+        return p2 ? f(BodyTag<StepBody<true, LAST, true, X2, true, PAIR, WT, NV>>{})
+                  : f(BodyTag<StepBody<false, LAST, true, X2, true, PAIR, WT, NV>>{});
+    if constexpr (!NV && !(PAIR && X2))
+        if (kc_mode == OCN_KC_GENERAL)
+            return p2 ? f(BodyTag<StepBody<true, LAST, false, X2, false, PAIR, WT, NV>>{})
+                      : f(BodyTag<StepBody<false, LAST, false, X2, false, PAIR, WT, NV>>{});
+    return p2 ? f(BodyTag<StepBody<true, LAST, true, X2, false, PAIR, WT, NV>>{})
+              : f(BodyTag<StepBody<false, LAST, true, X2, false, PAIR, WT, NV>>{});
+}
+
 // ------------------------------------------------------------------ fused launches
 // cp == nullptr: the real(4) fields are read from the 2-D arrays; otherwise from the block's
 // compact tables (sw_stencils.h "compact static fields", built by launch_prepare).
@@ -3117,10 +3162,7 @@ int launch_onepass(const ocn_block *b, void *const *ptr, int nptr, const Compact
                    double tau, int32_t *nbad, double *sshp_out, double *up_out, double *vp_out, hipStream_t s,
                    const Range *range, bool last, const OnepassKC &kc, unsigned own, const Range *frame_of)
 {
-    if (!cp || !cp->march || sw.full_free_surface != 1 || sw.trans_terms <= 0 || sw.ksw_lat <= 0 || !sshp_out ||
-        !up_out || !vp_out)
-        return set_error(OCN_ERR_ARG, "one-pass step: compact tables, march, full_free_surface = 1, trans_terms and "
-                                      "ksw_lat on, three second buffers");
+    RC_K(onepass_check("one-pass step", cp, sw, sshp_out, up_out, vp_out));
     if (kc.mode != OCN_KC_GENERAL && (!kc.kc || (kc.mode == OCN_KC_DEVICE && !kc.flag)))
         return set_error(OCN_ERR_ARG, "one-pass step: known constants without their device words");
     if (own && last) return set_error(OCN_ERR_ARG, "one-pass step over neighbour-owned halos: not a last step");
@@ -3128,37 +3170,25 @@ int launch_onepass(const ocn_block *b, void *const *ptr, int nptr, const Compact
     const Tab<true> t = make_tab<true>(ptr, nptr, cp->bits, cp->rows, block_rows(b), 0);
     const Range r = range ? range_clip(range_interior(b), *range) : range_interior(b);
     if (range_empty(r)) return OCN_OK;
-    int ex;
-    const bool p2 = std::frexp(tau, &ex) == 0.5 && ex > -1020 && ex < 1020;   // tau = 2^k
+    const bool p2 = tau_is_pow2(tau);
+    // one variant's launch, gated or not (MarchStepT::gate)
+    auto variant = [&](int mode, int gate) -> int {
+        auto go = [&](auto tag) -> int {
+            const typename decltype(tag)::type k_{*b, t, sw, tau, nbad, sshp_out, up_out, vp_out, kc.kc, kc.flag, gate, own};
+            return frame_of ? launch_step_frame(b, r, *frame_of, k_, s) : launch_step(b, r, k_, s);
+        };
+        if (own) return step_dispatch<false, true, false, false, false>(p2, mode, go);
+        if (last) return step_dispatch<true, false, false, false, false>(p2, mode, go);
+        return step_dispatch<false, false, false, false, false>(p2, mode, go);
+    };
+    if (kc.mode == OCN_KC_KNOWN || kc.mode == OCN_KC_KNOWN_HR) return variant(kc.mode, 0);
+    if (kc.mode != OCN_KC_DEVICE) return variant(OCN_KC_GENERAL, 0);
     // OCN_KC_DEVICE: the known-constant variant runs if the device check found its conditions, the
     // general one otherwise (each launch's workgroups read the verdict and return at once if it
     // is not theirs)
-    const bool dev = kc.mode == OCN_KC_DEVICE;
-    const int gz = dev ? 1 : 0, gh = dev ? 3 : 0, gg = dev ? 2 : 0;
-#define OCN_STEP_LAUNCH(P, L, Z, X, H, G)                                                                        \
-    do {                                                                                                          \
-        const MarchStep<P, L, Z, X, H> k_{*b, t, sw, tau, nbad, sshp_out, up_out, vp_out, kc.kc, kc.flag, G, own}; \
-        RC_K(frame_of ? launch_step_frame(b, r, *frame_of, k_, s) : launch_step(b, r, k_, s));                   \
-    } while (0)
-#define OCN_STEP_VARIANT(Z, H, G)                                                                                \
-    do {                                                                                                         \
-        if (own) { if (p2) OCN_STEP_LAUNCH(true, false, Z, true, H, G); else OCN_STEP_LAUNCH(false, false, Z, true, H, G); } \
-        else if (last) { if (p2) OCN_STEP_LAUNCH(true, true, Z, false, H, G); else OCN_STEP_LAUNCH(false, true, Z, false, H, G); } \
-        else if (p2) OCN_STEP_LAUNCH(true, false, Z, false, H, G);                                                 \
-        else OCN_STEP_LAUNCH(false, false, Z, false, H, G);                                                        \
-    } while (0)
-    if (kc.mode == OCN_KC_KNOWN || dev) {
-        OCN_STEP_VARIANT(true, false, gz);
-        if (!dev) return OCN_OK;
-    }
-    if (kc.mode == OCN_KC_KNOWN_HR || dev) {
-        OCN_STEP_VARIANT(true, true, gh);
-        if (!dev) return OCN_OK;
-    }
-    OCN_STEP_VARIANT(false, false, gg);
-#undef OCN_STEP_VARIANT
-#undef OCN_STEP_LAUNCH
-    return OCN_OK;
+    RC_K(variant(OCN_KC_KNOWN, 1));
+    RC_K(variant(OCN_KC_KNOWN_HR, 3));
+    return variant(OCN_KC_GENERAL, 2);
 }
 
 // ------------------------------------------------------------------ several steps per launch
@@ -3239,32 +3269,40 @@ static int multi_rows(const Range &r)
     return 0;
 }
 
-// The multi-step kernels' resident capacity on the current device, in workgroups: the fewest of any
-// variant's occupancy x the device's CUs (a device with fewer CUs, a partition mode, another
-// compile of the march), queried once per device; 0 if a query fails (no multi-step launch then)
-template <bool P, bool Z, bool H> using MultiBody = MarchStep<P, false, Z, false, H, false, true>;
-static long multi_capacity()
+// the multi-step body (MarchStep WT) of the planner's variant id (onepass_multi_variant; + 6, the per-step
+// check, is the same body), as step_dispatch hands it over
+template <class F> static auto multi_dispatch(int variant, F &&f)
 {
-    static std::mutex mu;
-    static std::map<int, long> cap;
+    constexpr int mode[3] = {OCN_KC_KNOWN, OCN_KC_KNOWN_HR, OCN_KC_GENERAL};
+    return step_dispatch<false, false, false, true, false>((variant & 1) != 0, mode[(variant % 6) / 2], f);
+}
+
+// The resident capacity of a multi-step kernel on the current device, in workgroups: the fewest of `base`
+// and any variant's occupancy x the device's CUs (a device with fewer CUs, a partition mode, another
+// compile of the march), queried once per device into the caller's cache; 0 if a query fails (no
+// multi-step launch then).  kernel(tag) = the kernel of the body BodyTag tag names.
+struct CapacityCache { std::mutex mu; std::map<int, long> cap; };
+template <class K> static long resident_capacity(CapacityCache &cache, long base, K &&kernel)
+{
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> g(mu);
-    const auto it = cap.find(dev);
-    if (it != cap.end()) return it->second;
-    long c = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? LONG_MAX : 0;
-    auto occ = [&](auto kern) {
-        int per = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, 256, 0) != hipSuccess) per = 0;
-        c = std::min(c, (long)per * cus);
-    };
-    occ(k_march_multi<MultiBody<true, false, false>>);
-    occ(k_march_multi<MultiBody<false, false, false>>);
-    occ(k_march_multi<MultiBody<true, true, true>>);
-    occ(k_march_multi<MultiBody<false, true, true>>);
-    occ(k_march_multi<MultiBody<true, true, false>>);
-    occ(k_march_multi<MultiBody<false, true, false>>);
-    return cap[dev] = c;
+    std::lock_guard<std::mutex> g(cache.mu);
+    const auto it = cache.cap.find(dev);
+    if (it != cache.cap.end()) return it->second;
+    long c = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? base : 0;
+    for (int v = 0; v < 6; ++v)
+        multi_dispatch(v, [&](auto tag) {
+            int per = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel(tag), 256, 0) != hipSuccess) per = 0;
+            c = std::min(c, (long)per * cus);
+            return 0;
+        });
+    return cache.cap[dev] = c;
+}
+static long multi_capacity()
+{
+    static CapacityCache cache;
+    return resident_capacity(cache, LONG_MAX, [](auto tag) { return k_march_multi<typename decltype(tag)::type>; });
 }
 
 static long multi_tiles(const Range &r, int rows)
@@ -3283,10 +3321,7 @@ int launch_onepass_multi(const ocn_block *b, void *const *ptr, int nptr, const C
                          double tau, int nsteps, int32_t *nbad, double *sshp_alt, double *up_alt, double *vp_alt,
                          unsigned *ctr, int32_t *err, hipStream_t s, const OnepassKC &kc, int spin)
 {
-    if (!cp || !cp->march || sw.full_free_surface != 1 || sw.trans_terms <= 0 || sw.ksw_lat <= 0 || !sshp_alt ||
-        !up_alt || !vp_alt || !ctr || !err || nsteps < 1)
-        return set_error(OCN_ERR_ARG, "multi-step launch: compact tables, march, full_free_surface = 1, trans_terms "
-                                      "and ksw_lat on, three second buffers, barrier words");
+    RC_K(onepass_check("multi-step launch", cp, sw, sshp_alt, up_alt, vp_alt, ctr && err && nsteps >= 1, ", barrier words"));
     if (kc.mode == OCN_KC_DEVICE || (kc.mode != OCN_KC_GENERAL && !kc.kc))
         return set_error(OCN_ERR_ARG, "multi-step launch: a variant chosen on the host");
     RC_K(check_block(b));
@@ -3306,12 +3341,12 @@ int launch_onepass_multi(const ocn_block *b, void *const *ptr, int nptr, const C
     const Tab<true> t1 = make_tab<true>(odd.data(), nptr, cp->bits, cp->rows, block_rows(b), 0);
     MarchGrid g{};
     g.r[0] = MarchRect{};
-    int ex;
-    const bool p2 = std::frexp(tau, &ex) == 0.5 && ex > -1020 && ex < 1020;   // tau = 2^k
     if (batching(s)) return batch_violation();   // (a multi-step launch is not batched)
     RC_K(check_hip(hipMemsetAsync(ctr, 0, kMultiBarBytes, s), "multi-step launch: barrier words"));
-    auto go = [&](auto k0, auto k1) -> int {
-        using Body = decltype(k0);
+    return step_dispatch<false, false, false, true, false>(tau_is_pow2(tau), kc.mode, [&](auto tag) -> int {
+        using Body = typename decltype(tag)::type;
+        const Body k0{*b, t0, sw, tau, nbad, sshp_alt, up_alt, vp_alt, kc.kc, nullptr, 0, 0u};
+        const Body k1{*b, t1, sw, tau, nbad, alt[0], alt[1], alt[2], kc.kc, nullptr, 0, 0u};
         g.r[0] = march_rect<Body>(b, r, rows, true);
         g.nr = 1;
         g.ntiles = g.r[0].tiles;
@@ -3323,17 +3358,7 @@ int launch_onepass_multi(const ocn_block *b, void *const *ptr, int nptr, const C
         k_march_multi<Body><<<dim3((unsigned)g.ntiles), dim3(256), 0, s>>>(g, BodyPair<Body>{{k0, k1}}, nsteps, ctr, err,
                                                                              spin < 1 ? 1 : spin);
         return check_hip(hipGetLastError(), "multi-step launch");
-    };
-#define OCN_MULTI(P, Z, H)                                                                                       \
-    return go(MarchStep<P, false, Z, false, H, false, true>{*b, t0, sw, tau, nbad, sshp_alt, up_alt, vp_alt, kc.kc,  \
-                                                           nullptr, 0, 0u},                                       \
-              MarchStep<P, false, Z, false, H, false, true>{*b, t1, sw, tau, nbad, alt[0], alt[1], alt[2], kc.kc,    \
-                                                           nullptr, 0, 0u})
-    if (kc.mode == OCN_KC_GENERAL) { if (p2) OCN_MULTI(true, false, false); OCN_MULTI(false, false, false); }
-    if (kc.mode == OCN_KC_KNOWN_HR) { if (p2) OCN_MULTI(true, true, true); OCN_MULTI(false, true, true); }
-    if (p2) OCN_MULTI(true, true, false);
-    OCN_MULTI(false, true, false);
-#undef OCN_MULTI
+    });
 }
 
 // ------------------------------------------------------------------ ensembles: members per launch
@@ -3494,78 +3519,33 @@ __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_rec(const
 // + (tau a power of two), + 6 with the per-step check; -1: no variant chosen on the host
 int onepass_multi_variant(int kc_mode, double tau, bool check)
 {
-    int ex;
-    const int p2 = std::frexp(tau, &ex) == 0.5 && ex > -1020 && ex < 1020;
     const int v = kc_mode == OCN_KC_KNOWN ? 0 : kc_mode == OCN_KC_KNOWN_HR ? 1 : kc_mode == OCN_KC_GENERAL ? 2 : -1;
-    return v < 0 ? -1 : 2 * v + p2 + (check ? 6 : 0);
-}
-
-template <class T> struct BodyTag { using type = T; };
-template <class F> static auto multi_b_dispatch(int variant, F &&f)
-{
-    switch (variant % 6) {
-    case 0: return f(BodyTag<MultiBody<false, true, false>>{});
-    case 1: return f(BodyTag<MultiBody<true, true, false>>{});
-    case 2: return f(BodyTag<MultiBody<false, true, true>>{});
-    case 3: return f(BodyTag<MultiBody<true, true, true>>{});
-    case 4: return f(BodyTag<MultiBody<false, false, false>>{});
-    default: return f(BodyTag<MultiBody<true, false, false>>{});
-    }
+    return v < 0 ? -1 : 2 * v + (tau_is_pow2(tau) ? 1 : 0) + (check ? 6 : 0);
 }
 
 size_t onepass_multi_b_entry_bytes()
 {
     size_t n = 0;
     for (int v = 0; v < 6; ++v)
-        n = std::max(n, multi_b_dispatch(v, [](auto b) { return sizeof(EnsEntry<typename decltype(b)::type>); }));
+        n = std::max(n, multi_dispatch(v, [](auto b) { return sizeof(EnsEntry<typename decltype(b)::type>); }));
     return n;
 }
 
 // the resident capacity of the ensemble launch in workgroups: as multi_capacity, over both kernels
 long onepass_multi_b_capacity()
 {
-    static std::mutex mu;
-    static std::map<int, long> cap;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    long c = multi_capacity();
-    std::lock_guard<std::mutex> g(mu);
-    const auto it = cap.find(dev);
-    if (it != cap.end()) return it->second;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) c = 0;
-    for (int v = 0; v < 6; ++v)
-        multi_b_dispatch(v, [&](auto b) {
-            int per = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_march_multi_b<typename decltype(b)::type>, 256, 0) != hipSuccess)
-                per = 0;
-            c = std::min(c, (long)per * cus);
-            return 0;
-        });
-    return cap[dev] = c;
+    static CapacityCache cache;
+    return resident_capacity(cache, multi_capacity(),
+                             [](auto tag) { return k_march_multi_b<typename decltype(tag)::type>; });
 }
 
 // the resident capacity of the recording launch: onepass_multi_b_capacity() and the recording kernels' own
 // occupancy x CUs (kept apart: folding it into the other would change the plans of calls that record nothing)
 long onepass_multi_rec_capacity()
 {
-    static std::mutex mu;
-    static std::map<int, long> cap;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    long c = onepass_multi_b_capacity();
-    std::lock_guard<std::mutex> g(mu);
-    const auto it = cap.find(dev);
-    if (it != cap.end()) return it->second;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) c = 0;
-    for (int v = 0; v < 6; ++v)
-        multi_b_dispatch(v, [&](auto b) {
-            int per = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_march_multi_rec<typename decltype(b)::type>, 256, 0) != hipSuccess)
-                per = 0;
-            c = std::min(c, (long)per * cus);
-            return 0;
-        });
-    return cap[dev] = c;
+    static CapacityCache cache;
+    return resident_capacity(cache, onepass_multi_b_capacity(),
+                             [](auto tag) { return k_march_multi_rec<typename decltype(tag)::type>; });
 }
 
 // launch_onepass_multi_b (rec null) and launch_onepass_multi_rec behind their checks: one table of entries, one launch
@@ -3575,11 +3555,11 @@ static int launch_multi_b_impl(const EnsMember *m, int n, int variant, int rows,
 {
     if (!m || n < 1 || variant < 0 || variant >= 12 || rows < 1 || rows > 16 || nsteps < 1 || !d_tab || !h_tab)
         return set_error(OCN_ERR_ARG, "ensemble launch: members, a variant, 1..16 rows, a table");
-    if (sw.full_free_surface != 1 || sw.trans_terms <= 0 || sw.ksw_lat <= 0)
+    if (!onepass_switches(sw))
         return set_error(OCN_ERR_ARG, "ensemble launch: full_free_surface = 1, trans_terms and ksw_lat on");
     if (batching(s)) return batch_violation();
     const bool check = variant >= 6;
-    return multi_b_dispatch(variant, [&](auto proto) -> int {
+    return multi_dispatch(variant, [&](auto proto) -> int {
         using Body = typename decltype(proto)::type;
         using Entry = EnsEntry<Body>;
         if (sizeof(Entry) * (size_t)n > tab_bytes) return set_error(OCN_ERR_ARG, "ensemble launch: table too small");
@@ -3713,6 +3693,14 @@ static int pair_rows(const Range &r, int mult = 1)
 {
     return pair_plan((long)r.m1 - r.m0 + 1, (long)r.n1 - r.n0 + 1, mult);
 }
+// the two-step launch's rect over r: workgroup tiles of kPairCols columns x rows rows from r's corner, the
+// loaded columns clamped 4 past r into the block's arrays
+static MarchRect pair_rect(const ocn_block *b, const Range &r, int rows)
+{
+    const int cols = kPairColsHost, ntx = (r.m1 - r.m0 + cols) / cols;
+    return MarchRect{r.m0, r.m1, r.n0, r.n1, r.m0, ntx, ntx * ((r.n1 - r.n0 + rows) / rows), max(r.m0 - 4, b->bnd_x1),
+                     min(r.m1 + 4, b->bnd_x2), rows, 0};
+}
 
 // the fixed tile height in force (0: automatic): part of what a captured step depends on (ocn_ctx.hip graph_step)
 int pair_rows_fixed() { return g_pair_rows_fixed.load(std::memory_order_relaxed); }
@@ -3721,49 +3709,26 @@ int launch_onepass_pair(const ocn_block *b, void *const *ptr, int nptr, const Co
                         double tau, int32_t *nbad1, int32_t *nbad2, double *sshp_out, double *up_out, double *vp_out,
                         hipStream_t s, const OnepassKC &kc, bool last)
 {
-    if (!cp || !cp->march || sw.full_free_surface != 1 || sw.trans_terms <= 0 || sw.ksw_lat <= 0 || !sshp_out ||
-        !up_out || !vp_out)
-        return set_error(OCN_ERR_ARG, "two-step launch: compact tables, march, full_free_surface = 1, trans_terms and "
-                                      "ksw_lat on, three second buffers");
+    RC_K(onepass_check("two-step launch", cp, sw, sshp_out, up_out, vp_out));
     if (kc.mode == OCN_KC_DEVICE || (kc.mode != OCN_KC_GENERAL && !kc.kc))
         return set_error(OCN_ERR_ARG, "two-step launch: a variant chosen on the host");
     RC_K(check_block(b));
     const Tab<true> t = make_tab<true>(ptr, nptr, cp->bits, cp->rows, block_rows(b), 0);
     const Range r = range_interior(b);
     if (range_empty(r)) return OCN_OK;
-    const int cols = kPairColsHost, rows = pair_rows(r);
     MarchGrid g{};
-    const int ntx = (r.m1 - r.m0 + cols) / cols;
-    g.r[0] = MarchRect{r.m0, r.m1, r.n0, r.n1, r.m0, ntx, ntx * ((r.n1 - r.n0 + rows) / rows), max(r.m0 - 4, b->bnd_x1),
-                       min(r.m1 + 4, b->bnd_x2), rows, 0};
+    g.r[0] = pair_rect(b, r, pair_rows(r));
     g.nr = 1;
     g.ntiles = g.r[0].tiles;
-    int ex;
-    const bool p2 = std::frexp(tau, &ex) == 0.5 && ex > -1020 && ex < 1020;   // tau = 2^k
-    if (kc.nv && !last && (kc.mode == OCN_KC_KNOWN || kc.mode == OCN_KC_KNOWN_HR)) {   // the inviscid bodies (MarchStepT NV)
-#define OCN_PAIR_NV(P, H)                                                                                        \
-    return issue_march(g, MarchStepT<P, false, true, false, H, true, false, true>{*b, t, sw, tau, nbad1, sshp_out,   \
-                                                                                  up_out, vp_out, kc.kc, nullptr, 0, \
-                                                                                  0u, nbad2}, s)
-        const bool hr = kc.mode == OCN_KC_KNOWN_HR;
-        if (p2 && hr) OCN_PAIR_NV(true, true);
-        if (hr) OCN_PAIR_NV(false, true);
-        if (p2) OCN_PAIR_NV(true, false);
-        OCN_PAIR_NV(false, false);
-#undef OCN_PAIR_NV
-    }
-#define OCN_PAIR_LAUNCH(P, L, Z, H)                                                                              \
-    return issue_march(g, MarchStep<P, L, Z, false, H, true>{*b, t, sw, tau, nbad1, sshp_out, up_out, vp_out,        \
-                                                             kc.kc, nullptr, 0, 0u, nbad2}, s)
-#define OCN_PAIR_VARIANT(L)                                                                                      \
-    if (kc.mode == OCN_KC_GENERAL) { if (p2) OCN_PAIR_LAUNCH(true, L, false, false); OCN_PAIR_LAUNCH(false, L, false, false); } \
-    if (kc.mode == OCN_KC_KNOWN_HR) { if (p2) OCN_PAIR_LAUNCH(true, L, true, true); OCN_PAIR_LAUNCH(false, L, true, true); }    \
-    if (p2) OCN_PAIR_LAUNCH(true, L, true, false);                                                                \
-    OCN_PAIR_LAUNCH(false, L, true, false)
-    if (last) { OCN_PAIR_VARIANT(true); }
-    OCN_PAIR_VARIANT(false);
-#undef OCN_PAIR_VARIANT
-#undef OCN_PAIR_LAUNCH
+    const bool p2 = tau_is_pow2(tau);
+    auto go = [&](auto tag) -> int {
+        return issue_march(g, typename decltype(tag)::type{*b, t, sw, tau, nbad1, sshp_out, up_out, vp_out, kc.kc, nullptr,
+                                                           0, 0u, nbad2}, s);
+    };
+    if (kc.nv && !last && (kc.mode == OCN_KC_KNOWN || kc.mode == OCN_KC_KNOWN_HR))   // the inviscid bodies (MarchStepT NV)
+        return step_dispatch<false, false, true, false, true>(p2, kc.mode, go);
+    if (last) return step_dispatch<true, false, true, false, false>(p2, kc.mode, go);
+    return step_dispatch<false, false, true, false, false>(p2, kc.mode, go);
 }
 
 // Two one-pass steps per launch on a block with halo exchanges (ocn_ctx.hip one_step_x4): bx = the
@@ -3775,10 +3740,7 @@ int launch_onepass_pair_x4(const ocn_block *bx, void *const *ptr, int nptr, cons
                            hipStream_t s, const OnepassKC &kc, unsigned own, const Range *range, int nblk,
                            const Range *frame_of, double *const *trs)
 {
-    if (!cp || !cp->march || sw.full_free_surface != 1 || sw.trans_terms <= 0 || sw.ksw_lat <= 0 || !sshp_out ||
-        !up_out || !vp_out)
-        return set_error(OCN_ERR_ARG, "x4 two-step launch: compact tables, march, full_free_surface = 1, trans_terms "
-                                      "and ksw_lat on, three second buffers");
+    RC_K(onepass_check("x4 two-step launch", cp, sw, sshp_out, up_out, vp_out));
     if ((kc.mode != OCN_KC_KNOWN && kc.mode != OCN_KC_KNOWN_HR) || !kc.kc)
         return set_error(OCN_ERR_ARG, "x4 two-step launch: a known-constant variant chosen on the host");
     RC_K(check_block(bx));
@@ -3791,7 +3753,7 @@ int launch_onepass_pair_x4(const ocn_block *bx, void *const *ptr, int nptr, cons
     using KP = MarchStep<true, false, true, true, false, true>;
     // a batch puts up to P blocks' tiles in one launch (MarchBatch): their waves share its rounds
     constexpr int P = kPack<KP> < kBatchMax / 4 ? kPack<KP> : kBatchMax / 4;
-    const int cols = KP::kPairCols, mult = batching(s) ? std::max(1, std::min(nblk, P)) : 1;
+    const int mult = batching(s) ? std::max(1, std::min(nblk, P)) : 1;
     // the rects: the range, or (frame_of) its bands outside *frame_of -- one launch, up to 4 rects
     Range rs[4];
     int nr = 0;
@@ -3806,42 +3768,18 @@ int launch_onepass_pair_x4(const ocn_block *bx, void *const *ptr, int nptr, cons
     }
     MarchGrid g{};
     for (int i = 0; i < nr; ++i) {
-        const Range &r = rs[i];
-        const int rows = pair_rows(r, mult), ntx = (r.m1 - r.m0 + cols) / cols;
-        g.r[g.nr++] = MarchRect{r.m0, r.m1, r.n0, r.n1, r.m0, ntx, ntx * ((r.n1 - r.n0 + rows) / rows),
-                                max(r.m0 - 4, bx->bnd_x1), min(r.m1 + 4, bx->bnd_x2), rows, 0};
+        g.r[g.nr++] = pair_rect(bx, rs[i], pair_rows(rs[i], mult));
         g.ntiles += g.r[g.nr - 1].tiles;
     }
-    int ex;
-    auto go = [&](auto body) {
+    // (OCN_KC_KNOWN_HR: h_r read -- a topography: the rest depth varies --, its 4 rings exchanged)
+    auto go = [&](auto tag) -> int {
+        typename decltype(tag)::type body{*bx, t, sw, tau, nbad1, sshp_out, up_out, vp_out, kc.kc, nullptr, 0, own, nbad2};
         if (trs)
             for (int i = 0; i < 4; ++i) body.trs[i] = trs[i];
         return issue_march(g, body, s);
     };
-    const bool p2 = std::frexp(tau, &ex) == 0.5 && ex > -1020 && ex < 1020;   // tau = 2^k
-    if (kc.nv) {   // the inviscid bodies (MarchStepT NV)
-        const bool hr = kc.mode == OCN_KC_KNOWN_HR;
-#define OCN_X4_NV(P, H)                                                                                              \
-    return go(MarchStepT<P, false, true, true, H, true, false, true>{*bx, t, sw, tau, nbad1, sshp_out, up_out, vp_out, \
-                                                                    kc.kc, nullptr, 0, own, nbad2})
-        if (p2 && hr) OCN_X4_NV(true, true);
-        if (hr) OCN_X4_NV(false, true);
-        if (p2) OCN_X4_NV(true, false);
-        OCN_X4_NV(false, false);
-#undef OCN_X4_NV
-    }
-    if (kc.mode == OCN_KC_KNOWN_HR) {   // h_r read (a topography: the rest depth varies), its 4 rings exchanged
-        if (p2)
-            return go(MarchStep<true, false, true, true, true, true>{*bx, t, sw, tau, nbad1, sshp_out, up_out, vp_out,
-                                                                     kc.kc, nullptr, 0, own, nbad2});
-        return go(MarchStep<false, false, true, true, true, true>{*bx, t, sw, tau, nbad1, sshp_out, up_out, vp_out, kc.kc,
-                                                                  nullptr, 0, own, nbad2});
-    }
-    if (p2)
-        return go(MarchStep<true, false, true, true, false, true>{*bx, t, sw, tau, nbad1, sshp_out, up_out, vp_out, kc.kc,
-                                                                  nullptr, 0, own, nbad2});
-    return go(MarchStep<false, false, true, true, false, true>{*bx, t, sw, tau, nbad1, sshp_out, up_out, vp_out, kc.kc,
-                                                               nullptr, 0, own, nbad2});
+    if (kc.nv) return step_dispatch<false, true, true, false, true>(tau_is_pow2(tau), kc.mode, go);   // the inviscid bodies
+    return step_dispatch<false, true, true, false, false>(tau_is_pow2(tau), kc.mode, go);
 }
 
 // mask bytes of one_step_x4 over the widened geometry bx: at the halo points neighbour blocks own

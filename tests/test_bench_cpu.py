@@ -102,10 +102,12 @@ def test_profile_applies_to_unchanged_kernel_code(tmp_path, monkeypatch):
 
 
 def test_every_source_contributes_a_code_object():
-    """Each object file with device code brings its own gfx950 bundle.  gfx950_code_object stays the
-    first one -- sw_kernels.hip's, first on the link line, where bench.py looks up the march kernels'
-    code_sha -- and the halo segment kernels (ctx_comm.hip) are found only over all of them, which is
-    what scripts/codeobj_diff.py compares between two builds."""
+    """Each object file with device code brings its own gfx950 bundle, and no bundle has a role of its own:
+    every function symbol is in exactly one of them (the build has no relocatable device code: a kernel
+    template instantiated from two sources would be registered twice under one host stub), the march
+    kernels and the halo segment kernels (ctx_comm.hip) are found over their union, kernel_code_sha finds
+    a kernel that is not in the first bundle as it finds a stamped one, and scripts/codeobj_diff.py -- which
+    compares the union between two builds -- finds a library equal to itself."""
     import subprocess
     import sys
     import ocean_model_arch_amd as amd
@@ -113,15 +115,65 @@ def test_every_source_contributes_a_code_object():
     lib = amd._lib.LIB_PATH
     if not os.path.exists(lib):
         pytest.skip("library not built")
-    objs = list(_codeobj.gfx950_code_objects(lib))
-    assert len(objs) >= 2 and objs[0] == _codeobj.gfx950_code_object(lib)
-    first = _codeobj.kernel_symbols(objs[0])
-    assert _codeobj.march_step_symbol("true, false, true, false, false, true, false") in first
-    rest = [n for o in objs[1:] for n in _codeobj.kernel_symbols(o)]
-    assert any("k_segments" in n for n in rest) and not any("k_segments" in n for n in first)
+    objs = [_codeobj.kernel_symbols(o) for o in _codeobj.gfx950_code_objects(lib)]
+    assert len(objs) >= 2
+    names = [n for o in objs for n in o]
+    assert len(names) == len(set(names)), sorted(n for n in set(names) if names.count(n) > 1)
+    kernels = _codeobj.library_kernels(lib)
+    assert set(kernels) == set(names) and all(len(v) == 1 for v in kernels.values())
+    assert _codeobj.march_step_symbol("true, false, true, false, false, true, false") in kernels
+    assert any("k_segments" in n for n in kernels)
+    seg = next(n for o in objs[1:] for n in o if "k_segments" in n)   # (not in the first bundle)
+    assert seg not in objs[0] and _codeobj.kernel_code_sha(lib, seg) == _codeobj.code_sha(kernels[seg][0][1])
+    hh_init = json.load(open(os.path.join(bench.REPO, "profiles", "pmc_traffic.json")))["kernels"]["hh_init"]
+    assert "MarchHhInit" in hh_init["symbol"] and _codeobj.kernel_code_sha(lib, hh_init["symbol"]) == hh_init["code_sha"]
     r = subprocess.run([sys.executable, os.path.join(bench.REPO, "scripts", "codeobj_diff.py"), lib, lib],
                        capture_output=True, text=True)
-    assert r.returncode == 0 and "0 missing or different" in r.stdout, r.stdout + r.stderr
+    assert r.returncode == 0 and "0 missing or different" in r.stdout and \
+        "0 equal only after the literal replacement" in r.stdout, r.stdout + r.stderr
+
+
+def test_code_sha_is_position_independent():
+    """The hashed form of a kernel's bytes (_codeobj.position_independent) names the device global a
+    pc-relative literal addresses instead of holding the distance to it: the pair kernels sample the shader
+    clock into g_clk (three atomics: its three words), every other march kernel addresses no global and
+    hashes as its raw bytes.  Loading the same code elsewhere -- its address and its three literals moved by
+    one amount, as when code is added to or taken out of its code object -- leaves the hash what it was."""
+    import hashlib
+    import struct
+    import ocean_model_arch_amd as amd
+    from ocean_model_arch_amd import _codeobj
+    lib = amd._lib.LIB_PATH
+    if not os.path.exists(lib):
+        pytest.skip("library not built")
+    pair = _codeobj.march_step_symbol("true, false, true, false, false, true, false")
+    single = _codeobj.march_step_symbol("true, false, true, false, false, false, false")
+    found = 0
+    for code in _codeobj.gfx950_code_objects(lib):
+        data, addr, syms = _codeobj.data_symbols(code), _codeobj.kernel_addresses(code), _codeobj.kernel_symbols(code)
+        if single in syms:
+            form, refs = _codeobj.position_independent(syms[single], addr[single], data)
+            assert refs == [] and form == syms[single]
+            assert _codeobj.kernel_code_sha(lib, single) == hashlib.sha256(syms[single]).hexdigest()[:16]
+            found += 1
+        if pair in syms:
+            body = syms[pair]
+            form, refs = _codeobj.position_independent(body, addr[pair], data)
+            assert [(s, k) for _at, s, k in refs] == [("_ZN3ocn5g_clkE", 0), ("_ZN3ocn5g_clkE", 8), ("_ZN3ocn5g_clkE", 16)]
+            assert form != body and _codeobj.kernel_code_sha(lib, pair) == _codeobj.code_sha(form)
+            # the function d bytes further on, every distance to g_clk d shorter (moves that keep the function
+            # in front of the global, as the code of a code object lies in front of its data)
+            for d in (256, -4096, -(addr[pair] // 2 & ~0xFF)):
+                moved = bytearray(body)
+                for at, _s, _k in refs:
+                    lit, = struct.unpack_from("<I", body, at)
+                    struct.pack_into("<I", moved, at, (lit - d) & 0xFFFFFFFF)
+                assert bytes(moved) != body
+                assert _codeobj.position_independent(bytes(moved), addr[pair] + d, data) == (form, refs)
+            # (and a literal moved without its function is another kernel)
+            assert _codeobj.position_independent(bytes(moved), addr[pair], data)[0] != form
+            found += 1
+    assert found == 2
 
 
 def test_valu_needs_matching_stamp(tmp_path, monkeypatch):
