@@ -1,5 +1,5 @@
-// ocn_ctx.h -- the model context and what its sources share (ocn_ctx.hip, ctx_comm.hip, ctx_setup.hip,
-// ocn_ens.hip).  Internal: not part of the C ABI (include/ocn_sw.h), included by those four only.
+// ocn_ctx.h -- the model context and what its sources share (ocn_ctx.hip, ctx_comm.hip, ctx_setup.hip, and through
+// ocn_ens.h the ensemble's host sources).  Internal: not part of the C ABI (include/ocn_sw.h), included by those only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>

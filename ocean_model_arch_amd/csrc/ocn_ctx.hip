@@ -1,7 +1,7 @@
 // ocn_ctx.hip -- PSy layer of the MI355X shallow-water step: the stages, every step form, the call
 // planner (step_impl, complete_open, run_deferred, finish_call), check_coherence and the ocn_ctx_*
 // entries of the C ABI.  The context itself is ocn_ctx.h; its halo exchange is ctx_comm.hip, its
-// decomposition, storage and initial state ctx_setup.hip, the ensemble layer ocn_ens.hip.
+// decomposition, storage and initial state ctx_setup.hip, the ensemble layer ocn_ens*.hip.
 //
 // Reference counterparts (Andrcraft9/ocean_model_arch):
 //   dispatcher     core/kernel_interface.f90:48-119 (envoke) + interface/shallow_water/sw_interface.f90

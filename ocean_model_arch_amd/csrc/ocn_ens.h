@@ -1,0 +1,234 @@
+// ocn_ens.h -- the ensemble and what its host sources share (ocn_ens.hip, ocn_ens_diag.hip, ocn_ens_modify.hip,
+// ocn_ens_filter.hip, ocn_ens_record.hip).  Internal: not part of the C ABI (include/ocn_sw.h), included by those
+// five only.  No device code: the kernels behind these entries are in sw_kernels.hip and ens_*.hip.
+#pragma once
+#include "ocn_ctx.h"
+#include "ocn_ens_plan.h"
+
+// ------------------------------------------------------------------ the buffers of the entries
+// One device allocation and one pinned host copy of the same size, made or grown when a call needs more, and for
+// an entry that does not wait for its own copy an event: the stream has read the pinned side (awaited before it
+// is written again, and before it is freed).  A failed reserve() leaves bytes = 0: the next call tries again.
+struct EnsBuf {
+    void *d = nullptr, *h = nullptr;
+    size_t bytes = 0;
+    hipEvent_t ev = nullptr;
+    bool ev_set = false;
+
+    int await() { return ev_set ? check_hip(hipEventSynchronize(ev), "hipEventSynchronize") : OCN_OK; }
+    int sent(hipStream_t s) { HIPCHK(hipEventRecord(ev, s)); ev_set = true; return OCN_OK; }
+    // room for `need` bytes, in multiples of `granule`; event: the buffer's users call await() / sent()
+    int reserve(size_t need, size_t granule, bool event = false)
+    {
+        if (event && !ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        if (bytes >= need) return OCN_OK;
+        RC(await());
+        if (d) (void)hipFree(d);   // (waits for the launches that use it)
+        if (h) (void)hipHostFree(h);
+        d = h = nullptr;
+        bytes = 0;
+        const size_t grown = (need + granule - 1) / granule * granule;
+        HIPCHK(hipMalloc(&d, grown));
+        HIPCHK(hipHostMalloc(&h, grown, hipHostMallocDefault));
+        bytes = grown;
+        return OCN_OK;
+    }
+    void release()   // (the caller has waited for the stream, or hipFree does)
+    {
+        if (ev) (void)hipEventDestroy(ev);
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        *this = EnsBuf{};
+    }
+};
+
+// Tables that go up through pinned memory call after call with no wait in between: one device side (stream order
+// keeps its users apart) and two pinned copies -- a call fills one, the next call the other; ev[i]: the stream has
+// read copy i (awaited before it is written again).  slot: the copy whose turn it is; the owner moves it.
+struct EnsStage2 {
+    void *d = nullptr, *h[2] = {nullptr, nullptr};
+    size_t bytes = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool ev_set[2] = {false, false};
+    int slot = 0;
+
+    int await(int i) { return ev_set[i] ? check_hip(hipEventSynchronize(ev[i]), "hipEventSynchronize") : OCN_OK; }
+    int sent(int i, hipStream_t s) { HIPCHK(hipEventRecord(ev[i], s)); ev_set[i] = true; return OCN_OK; }
+    // room for `need` bytes, in multiples of `granule`.  Growing waits for the device; the new allocations whole
+    // before the old ones go, so a failed growth leaves the stage as it was
+    int reserve(size_t need, size_t granule)
+    {
+        if (need <= bytes) return OCN_OK;
+        for (int i = 0; i < 2; ++i) RC(await(i));
+        const size_t grown = (need + granule - 1) / granule * granule;
+        void *nd = nullptr, *nh[2] = {nullptr, nullptr};
+        int rc = check_hip(hipMalloc(&nd, grown), "hipMalloc");
+        for (int i = 0; i < 2 && !rc; ++i) rc = check_hip(hipHostMalloc(&nh[i], grown, hipHostMallocDefault), "hipHostMalloc");
+        for (int i = 0; i < 2 && !rc; ++i)
+            if (!ev[i]) rc = check_hip(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming), "hipEventCreate");
+        if (rc) {
+            if (nd) (void)hipFree(nd);
+            for (void *p : nh)
+                if (p) (void)hipHostFree(p);
+            return rc;
+        }
+        if (d) (void)hipFree(d);   // (waits for the launches that use it)
+        for (int i = 0; i < 2; ++i) {
+            if (h[i]) (void)hipHostFree(h[i]);
+            h[i] = nh[i];
+            ev_set[i] = false;
+        }
+        d = nd;
+        bytes = grown;
+        return OCN_OK;
+    }
+    void release()   // (the caller has waited for the stream, or hipFree does)
+    {
+        if (d) (void)hipFree(d);
+        for (int i = 0; i < 2; ++i) {
+            if (h[i]) (void)hipHostFree(h[i]);
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+        *this = EnsStage2{};
+    }
+};
+
+// ------------------------------------------------------------------ ensembles (ocn_sw.h)
+struct ocn_ens {
+    std::vector<ocn_ctx *> m;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    unsigned *d_bar = nullptr;     // kMultiBarBytes of barrier words per member
+    // the launches' member table (sw_kernels.hip EnsEntry), made by ocn_ens_create: a call's launches fill
+    // disjoint parts of one pinned copy, the next call takes the other
+    EnsStage2 tab;
+    int64_t cap_opt = 0;           // OCN_ENS_OPT_CAPACITY (0: none)
+    int64_t max_group = 0;         // OCN_ENS_OPT_MAX_GROUP (0: none)
+    ocn_ens_info_t last{};
+    // ocn_ens_stats: per local block, one buffer per statistic (mean, variance, spread, minimum, maximum)
+    // based like the members' arrays (raw: the allocations, made at first use), and the statistics the
+    // last call on that block formed (OCN_ENS_STAT_* bits)
+    struct Stats { void *raw[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+                   double *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; int formed = 0; };
+    std::vector<Stats> stats;
+    // ocn_ens_extrema: the blocks' interiors, the members' (field, lu) table, the per-tile partials and
+    // the results, in one device allocation made at first use; h_ext: the tables and the results in pinned host memory
+    void *d_ext = nullptr, *h_ext = nullptr;
+    // ocn_ens_transform: the weights transposed (ens_wt_stride x ens_wt_cols of all the members), made at first
+    // use.  stage: the staging arrays of the path beyond kEnsStatsReg members, stage_n of
+    // them stage_bytes apart, each the size of the largest block's array plus its base shift
+    EnsBuf w;
+    void *stage = nullptr;
+    size_t stage_bytes = 0;
+    int stage_n = 0;
+    // ocn_ens_sample, ocn_ens_sample_h, ocn_ens_record_sample: a call's tables and behind them its results
+    // (synchronous entries: no event)
+    EnsBuf samp;
+    // ocn_ens_local_update: the y and z rows, the taper and the blocks' observation lists
+    EnsBuf lu;
+    // ocn_ens_assimilate: the call's tables (taper, lists, values, variances, offsets, indices, blocks, the
+    // operator's or the recorder's observations, the members' arrays per block), then the device-formed rows hx, y, z and the innovation, prior and
+    // posterior vectors, the count and the gate's accept flags (the results come down into as.h at the offsets
+    // they have in as.d; the event: the stream has read as.h's tables).  as_last: the last successful call's
+    // results (nobs 0: none yet)
+    EnsBuf as;
+    struct AsLast { int nobs = 0, n = 0; size_t row = 0, hx_at = 0, vec_at = 0, count_at = 0; bool timed = false;
+                    size_t accept_at = 0; bool gated = false; } as_last;
+    // ocn_ens_set_gate: the squared threshold of the three entries' quality control (0.0: off, the ungated kernels)
+    double gate2 = 0.0;
+    // OCN_ENS_OPT_ASSIM_TIMING: events around the observation-space launch and the update's launches
+    bool as_timing = false;
+    hipEvent_t ev_t[3] = {nullptr, nullptr, nullptr};
+    // ocn_ens_spread_save / ocn_ens_inflate: per field named so far, per local block, the saved spread
+    // (buf[0]) and the factor applied (buf[1]), based like the members' arrays (raw: the allocations, made at
+    // first use); formed[i]: buf[i] holds a successful call's result on every block; in_use: the members of
+    // the save, one byte each
+    struct Inflate {
+        int32_t field = 0;
+        std::vector<void *> raw[2];
+        std::vector<double *> buf[2];
+        bool formed[2] = {false, false};
+        std::vector<uint8_t> in_use;
+    };
+    std::vector<Inflate> inflate;
+    // ocn_ens_perturb: per local block the int64 scratch of Z, one array per member of the ensemble stride[k]
+    // elements apart, based like the members' arrays (raw: the allocations, made at first use); n[k]: the
+    // members in use of the last noise launch on block k (0: none yet)
+    struct Perturb { std::vector<void *> raw; std::vector<long long *> z; std::vector<long> stride; std::vector<int> n; } perturb;
+    // ocn_ens_record_*: the station recorder.  use: one byte per member; field: the operator's distinct fields
+    // in the order of their first term; d_series: max_records x nobs x n doubles; d_op: the rows' starts, the
+    // terms as ocn_ens_sample_h resolves them (slot: into a gather's pointer table) and, with one local block,
+    // as the recording launch reads them (slot: the field's index in `field`), at start_at / term_at / lterm_at.
+    // stage: the tables a call brings -- the recording launches' EnsRecMember, one for every member, then one
+    // pointer table per gather, tab_b bytes each -- as the launches' member table goes up.
+    // steps, records: counted since ocn_ens_record_begin; in_launch: records a marching launch wrote
+    struct Recorder {
+        bool active = false;
+        int32_t nobs = 0, n = 0, every = 0, max_records = 0, records = 0;
+        int64_t steps = 0, in_launch = 0;
+        std::vector<uint8_t> use;
+        std::vector<int32_t> field;
+        void *d_series = nullptr, *d_op = nullptr;
+        size_t start_at = 0, term_at = 0, lterm_at = 0, tab_b = 0;
+        EnsStage2 stage;
+    } rec;
+    bool rec_in_launch = true;     // OCN_ENS_OPT_RECORD_IN_LAUNCH
+};
+
+namespace ocn {
+
+// ---- ocn_ens.hip: the members in use, the launch groups, the stepping loop, an array based like the members'
+std::vector<ocn_ctx *> ens_in_use(const ocn_ens *e, const uint8_t *use);
+int64_t ens_capacity(const ocn_ens *e);
+int ens_groups(const ocn_ens *e, const std::vector<int32_t> &variant, int64_t capacity, std::vector<ocn_ens_group> &groups);
+int32_t ens_variant(const ocn_ctx *c, double tau, bool check);
+// A recording call's part in ocn_ens_step's launches (ocn_ens_step_record's in-launch path): the capacity
+// in effect, the members' columns (-1: not in use), the first due step and its slot
+struct EnsRecCall { int64_t capacity; std::vector<int> col; int due0; double *slot0; };
+int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsRecCall *rec);
+void *ens_based_alloc(const LBlock &b, int32_t field, size_t bytes, void **raw);
+
+// The tail the three synchronous sampling entries share, in e->samp, reserved by the entry for up_b + res_b and
+// its pinned side filled up to up_b: the tables up, launch(d) -- d the device side, the results to d + up_b --,
+// the results down, one wait (nothing in flight reads the buffer afterwards), and out to `host`
+template <class F> static int ens_samp_run(ocn_ens *e, size_t up_b, size_t res_b, double *host, F &&launch)
+{
+    char *d = (char *)e->samp.d, *h = (char *)e->samp.h;
+    HIPCHK(hipMemcpyAsync(d, h, up_b, hipMemcpyHostToDevice, e->stream));
+    RC(launch(d));
+    HIPCHK(hipMemcpyAsync(h + up_b, d + up_b, res_b, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    memcpy(host, h + up_b, res_b);
+    return OCN_OK;
+}
+
+// ---- ocn_ens_filter.hip: what the localized update, the serial filter and the recorder's entries check and resolve alike
+int ens_lu_check(const ocn_ens *e, const std::string &who, const int32_t *field_ids, int32_t nfields,
+                 const std::vector<ocn_ctx *> &in, int32_t nobs, const int32_t *io, const int32_t *jo,
+                 const double *taper, int32_t ntaper);
+int ens_lu_reach(int32_t ntaper);
+size_t ens_lu_lists(const ocn_ctx *c0, int32_t nobs, const int32_t *io, const int32_t *jo, int reach,
+                    std::vector<std::vector<EnsLuObs>> &lists);
+void ens_lu_put_lists(const std::vector<std::vector<EnsLuObs>> &lists, char *h, size_t at, std::vector<size_t> &list_at);
+int ens_lu_launches(const std::vector<ocn_ctx *> &in, const int32_t *field_ids, int32_t nfields,
+                    const std::vector<std::vector<EnsLuObs>> &lists, const char *d, const std::vector<size_t> &list_at,
+                    const double *d_y, const double *d_z, const double *d_taper, int32_t ntaper, int reach, hipStream_t s);
+int ens_block_of(const ocn_ctx *c0, int32_t i, int32_t j);
+int ens_as_check(const std::string &who, int32_t nobs, const double *value, const double *variance);
+// A sparse linear observation operator (ocn_sw.h ocn_ens_sample_h), validated and resolved for n members in
+// use: its distinct fields in the order of their first term, and each term's pointer-table slot
+// (field slot * blocks + block) * n, element offset and weight.  Nothing is read beyond a bad row.
+struct EnsObsHost { std::vector<int32_t> fields; std::vector<EnsObsTerm> term; };
+int ens_obs_resolve(const ocn_ctx *c0, const std::string &who, size_t n, int32_t nobs, const int32_t *start,
+                    const int32_t *tfield, const int32_t *ti, const int32_t *tj, const double *tw, EnsObsHost &h);
+void ens_obs_table(const std::vector<ocn_ctx *> &in, const std::vector<int32_t> &fields, const double **tab);
+
+// ---- ocn_ens_record.hip: the recorder's buffers and events (ocn_ens_record_end, ocn_ens_record_begin over an
+// earlier one, ocn_ens_destroy), and what ocn_ens_record_sample and ocn_ens_assimilate_rec check alike
+void ens_rec_free(ocn_ens *e);
+int ens_rec_members(const ocn_ens *e, const std::string &who, const uint8_t *use, std::vector<ocn_ctx *> &in,
+                    std::vector<int> &col);
+int ens_rec_obs(const ocn_ens *e, const std::string &who, int32_t nobs, const int32_t *row, const int32_t *rec,
+                const double *wt, std::vector<EnsRecObs> &robs);
+
+}  // namespace ocn

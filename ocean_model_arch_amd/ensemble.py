@@ -496,6 +496,35 @@ class OceanEnsemble:
         check(lib().ocn_ens_gate_info(self.ens, C.byref(info)), "ocn_ens_gate_info")
         return {"gate2": float(info.gate2), "rejected": int(info.rejected)}
 
+    @staticmethod
+    def _assim_args(who, nobs, values, variances, taper, names):
+        """What the three device analyses coerce and check alike: (values, variances, taper) as contiguous float64
+        arrays and `names` as a tuple.  `who` opens the message."""
+        va = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
+        ra = np.ascontiguousarray(np.asarray(variances, dtype=np.float64).ravel())
+        ta = np.ascontiguousarray(np.asarray(taper, dtype=np.float64))
+        if len(va) != nobs or len(ra) != nobs:
+            raise ValueError(f"{who}: {len(va)} values and {len(ra)} variances for {nobs} observations")
+        if ta.ndim != 1 or not 1 <= len(ta) <= ens_local_rule.MAX_TAPER:
+            raise ValueError(f"{who}: a taper of shape {ta.shape}, not 1..{ens_local_rule.MAX_TAPER} entries")
+        return va, ra, ta, (names,) if isinstance(names, str) else tuple(names)
+
+    def _assim_results(self, nobs, n, gate2):
+        """The last device call's results (one wait each): the four arrays, "nonfinite" and, with a gate,
+        "accepted" and "rejected"."""
+        out = {}
+        for key in ("hx", "innovations", "prior_spread", "posterior_spread"):
+            a = np.zeros((nobs, n) if key == "hx" else nobs, dtype=np.float64)
+            check(lib().ocn_ens_assimilate_result(self.ens, _lib.ENS_ASSIM[key], a.ctypes.data_as(C.c_void_p)),
+                  "ocn_ens_assimilate_result")
+            out[key] = a
+        info = _lib.OcnEnsAssimInfo()
+        check(lib().ocn_ens_assimilate_info(self.ens, C.byref(info)), "ocn_ens_assimilate_info")
+        out["nonfinite"] = int(info.nonfinite)
+        if gate2 is not None:
+            out["accepted"], out["rejected"] = self._gate_results(nobs)
+        return out
+
     def _assimilate_device(self, name, obs_ij, values, variances, taper, names, members, defer: bool = False, gate2=None):
         """assimilate(device=True).  defer: return a function that reads the results back, so that the caller
         may issue more work behind the analysis before the first wait (one call's results stay in the
@@ -507,14 +536,7 @@ class OceanEnsemble:
         if ij.ndim != 2 or ij.shape[1] != 2 or len(ij) < 1:
             raise ValueError(f"assimilate: observation indices of shape {ij.shape}, not (nobs, 2)")
         nobs = len(ij)
-        va = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
-        ra = np.ascontiguousarray(np.asarray(variances, dtype=np.float64).ravel())
-        ta = np.ascontiguousarray(np.asarray(taper, dtype=np.float64))
-        if len(va) != nobs or len(ra) != nobs:
-            raise ValueError(f"assimilate: {len(va)} values and {len(ra)} variances for {nobs} observations")
-        if ta.ndim != 1 or not 1 <= len(ta) <= ens_local_rule.MAX_TAPER:
-            raise ValueError(f"assimilate: a taper of shape {ta.shape}, not 1..{ens_local_rule.MAX_TAPER} entries")
-        names = (names,) if isinstance(names, str) else tuple(names)
+        va, ra, ta, names = self._assim_args("assimilate", nobs, values, variances, taper, names)
         if nobs > ens_local_rule.MAX_OBS and name not in names:
             raise ValueError(f"assimilate: {nobs} observations of {name!r}, which is not among the updated fields {names}: "
                              f"calls of {ens_local_rule.MAX_OBS} would not compose")
@@ -522,24 +544,7 @@ class OceanEnsemble:
         io, jo = np.ascontiguousarray(ij[:, 0], dtype=np.int32), np.ascontiguousarray(ij[:, 1], dtype=np.int32)
         ptr = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
         L = lib()
-        parts = {k: [] for k in ("hx", "innovations", "prior_spread", "posterior_spread")}
-        nonfinite = rejected = 0
-        accepted = []
-
-        def read_back(count):   # the last call's results (one wait each)
-            nonlocal nonfinite, rejected
-            if gate2 is not None:
-                acc, rej = self._gate_results(count)
-                accepted.append(acc)
-                rejected += rej
-            for key in parts:
-                a = np.zeros((count, n) if key == "hx" else count, dtype=np.float64)
-                check(L.ocn_ens_assimilate_result(self.ens, _lib.ENS_ASSIM[key], ptr(a)), "ocn_ens_assimilate_result")
-                parts[key].append(a)
-            info = _lib.OcnEnsAssimInfo()
-            check(L.ocn_ens_assimilate_info(self.ens, C.byref(info)), "ocn_ens_assimilate_info")
-            nonfinite += int(info.nonfinite)
-
+        calls = []   # each call's results (a split list is read back call by call)
         later = defer and nobs <= ens_local_rule.MAX_OBS
         for k0 in range(0, nobs, ens_local_rule.MAX_OBS):
             k1 = min(k0 + ens_local_rule.MAX_OBS, nobs)
@@ -548,7 +553,7 @@ class OceanEnsemble:
             check(L.ocn_ens_assimilate(self.ens, _lib.FIELD_ID[name], ids, len(names), self._use(members), k1 - k0, ptr(i_),
                                        ptr(j_), ptr(v_), ptr(r_), ptr(ta), len(ta)), "ocn_ens_assimilate")
             if not later:
-                read_back(k1 - k0)
+                calls.append(self._assim_results(k1 - k0, n, gate2))
         resampled = None
         # (a row of an earlier call that a later call's observations reach: its final values are the fields')
         if nobs > ens_local_rule.MAX_OBS:
@@ -556,15 +561,13 @@ class OceanEnsemble:
 
         def finish():
             if later:
-                read_back(nobs)
-            out = {k: np.concatenate(v) for k, v in parts.items()}
+                calls.append(self._assim_results(nobs, n, gate2))
+            out = {k: (sum(c[k] for c in calls) if k in ("nonfinite", "rejected") else np.concatenate([c[k] for c in calls]))
+                   for k in calls[0]}
             if resampled is not None:
                 out["hx"] = resampled
                 with np.errstate(all="ignore"):
                     out["posterior_spread"] = np.array([ens_local_rule._spread(r) for r in out["hx"]])
-            out["nonfinite"] = nonfinite
-            if gate2 is not None:
-                out["accepted"], out["rejected"] = np.concatenate(accepted), rejected
             return out
         return finish if defer else finish()
 
@@ -628,14 +631,7 @@ class OceanEnsemble:
         if nobs > ens_local_rule.MAX_OBS:
             raise ValueError(f"assimilate_h: {nobs} observations, more than {ens_local_rule.MAX_OBS}: the rows are an "
                              f"augmented state, calls would not compose")
-        va = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
-        ra = np.ascontiguousarray(np.asarray(variances, dtype=np.float64).ravel())
-        ta = np.ascontiguousarray(np.asarray(taper, dtype=np.float64))
-        if len(va) != nobs or len(ra) != nobs:
-            raise ValueError(f"assimilate_h: {len(va)} values and {len(ra)} variances for {nobs} observations")
-        if ta.ndim != 1 or not 1 <= len(ta) <= ens_local_rule.MAX_TAPER:
-            raise ValueError(f"assimilate_h: a taper of shape {ta.shape}, not 1..{ens_local_rule.MAX_TAPER} entries")
-        names = (names,) if isinstance(names, str) else tuple(names)
+        va, ra, ta, names = self._assim_args("assimilate_h", nobs, values, variances, taper, names)
         if not device:
             hx = self.sample_h(op, members=members)
             Y, Z, info = ens_local_rule.ensrf_obs_space(hx, op.anchors, va, ra, ta, gate2=gate2)
@@ -651,18 +647,7 @@ class OceanEnsemble:
         check(L.ocn_ens_assimilate_h(self.ens, ids, len(names), self._use(members), nobs, ptr(io), ptr(jo),
                                      *[ptr(a) for a in arrays], ptr(va), ptr(ra), ptr(ta), len(ta)), "ocn_ens_assimilate_h")
 
-        def finish():   # the call's results (one wait each)
-            out = {}
-            for key in ("hx", "innovations", "prior_spread", "posterior_spread"):
-                a = np.zeros((nobs, n) if key == "hx" else nobs, dtype=np.float64)
-                check(L.ocn_ens_assimilate_result(self.ens, _lib.ENS_ASSIM[key], ptr(a)), "ocn_ens_assimilate_result")
-                out[key] = a
-            info = _lib.OcnEnsAssimInfo()
-            check(L.ocn_ens_assimilate_info(self.ens, C.byref(info)), "ocn_ens_assimilate_info")
-            out["nonfinite"] = int(info.nonfinite)
-            if gate2 is not None:
-                out["accepted"], out["rejected"] = self._gate_results(nobs)
-            return out
+        finish = lambda: self._assim_results(nobs, n, gate2)   # noqa: E731  (the call's results, one wait each)
         return finish if defer else finish()
 
     # ------------------------------------------------------------ station time series
@@ -813,14 +798,7 @@ class OceanEnsemble:
             raise TypeError(f"{who}: anchors of dtype {ij.dtype}, not integers")
         if ij.shape != (nobs, 2):
             raise ValueError(f"{who}: anchors of shape {ij.shape}, not {(nobs, 2)}")
-        va = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
-        ra_ = np.ascontiguousarray(np.asarray(variances, dtype=np.float64).ravel())
-        ta = np.ascontiguousarray(np.asarray(taper, dtype=np.float64))
-        if len(va) != nobs or len(ra_) != nobs:
-            raise ValueError(f"{who}: {len(va)} values and {len(ra_)} variances for {nobs} observations")
-        if ta.ndim != 1 or not 1 <= len(ta) <= ens_local_rule.MAX_TAPER:
-            raise ValueError(f"{who}: a taper of shape {ta.shape}, not 1..{ens_local_rule.MAX_TAPER} entries")
-        names = (names,) if isinstance(names, str) else tuple(names)
+        va, ra_, ta, names = self._assim_args(who, nobs, values, variances, taper, names)
         if rtps is not None:
             self.spread_save(names, members=eff)
         if not device:
@@ -839,18 +817,7 @@ class OceanEnsemble:
             check(L.ocn_ens_assimilate_rec(self.ens, ids, len(names), self._use(members), nobs, ptr(io), ptr(jo), ptr(ra),
                                            ptr(rec), ptr(wt), ptr(va), ptr(ra_), ptr(ta), len(ta)), "ocn_ens_assimilate_rec")
 
-            def finish():   # the call's results (one wait each)
-                out = {}
-                for key in ("hx", "innovations", "prior_spread", "posterior_spread"):
-                    a = np.zeros((nobs, n) if key == "hx" else nobs, dtype=np.float64)
-                    check(L.ocn_ens_assimilate_result(self.ens, _lib.ENS_ASSIM[key], ptr(a)), "ocn_ens_assimilate_result")
-                    out[key] = a
-                info = _lib.OcnEnsAssimInfo()
-                check(L.ocn_ens_assimilate_info(self.ens, C.byref(info)), "ocn_ens_assimilate_info")
-                out["nonfinite"] = int(info.nonfinite)
-                if gate2 is not None:
-                    out["accepted"], out["rejected"] = self._gate_results(nobs)
-                return out
+            finish = lambda: self._assim_results(nobs, n, gate2)   # noqa: E731  (the call's results, one wait each)
         if rtps is not None:   # (behind the analysis, before the device path's first wait)
             self.inflate(alpha, "rtps", names, members=eff)
         return finish()

@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 
 OK, ERR_ARG = 0, 1
 THREADS = 256        # ens_assim.hip kAsThreads: row j belongs to thread j mod THREADS
-STAGE_LAUNCHES = 1   # ocn_ens.hip kAsLaunches: the observation-space stage, whatever n and nobs
+STAGE_LAUNCHES = 1   # ocn_ens_filter.hip kAsLaunches: the observation-space stage, whatever n and nobs
 
 
 @pytest.fixture(scope="module")
