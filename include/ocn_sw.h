@@ -587,7 +587,8 @@ int ocn_ens_info(ocn_ens *ens, ocn_ens_info_t *out);
  * to ocn_ens_plan together (in member order), so that several shorter launches can be timed against
  * one taller one (scripts/ens_bench.py). */
 enum { OCN_ENS_OPT_CAPACITY = 1, OCN_ENS_OPT_MAX_GROUP = 2, OCN_ENS_OPT_ASSIM_TIMING = 3,
-       OCN_ENS_OPT_RECORD_IN_LAUNCH = 4 /* ocn_ens_step_record below: 1 (default) or 0 */ };
+       OCN_ENS_OPT_RECORD_IN_LAUNCH = 4 /* ocn_ens_step_record below: 1 (default) or 0 */,
+       OCN_ENS_OPT_FORCING_IN_LAUNCH = 5 /* ocn_ens_step_forced below: 1 (default) or 0 */ };
 int ocn_ens_set_option(ocn_ens *ens, int32_t key, int64_t value);
 
 /* Statistics over the members, formed on the device (the members' fields lie side by side in device
@@ -1066,6 +1067,104 @@ int ocn_ens_perturb(ocn_ens *ens, const int32_t *field_ids, const int32_t *mask_
                     int32_t nfields, const uint8_t *use, uint64_t seed, int32_t reach, int32_t passes,
                     int32_t centre, double amplitude);
 int ocn_ens_perturb_download(ocn_ens *ens, int32_t k, int32_t a, int64_t *host);
+
+/* Moving-storm forcing: the wind stress and the air pressure of a storm that moves across the basin, formed on
+ * the device into OCN_RHSX / OCN_RHSY (the external momentum forcing of sw_update_uv) from a few numbers per
+ * member, at each step's own time -- a storm-surge ensemble whose members differ in the storm's track, size
+ * and strength.  No counterpart in the reference.
+ *
+ * ocn_ens_storm (one per member): x0, y0 the centre at t = 0 in GLOBAL 1-based index coordinates (fractional);
+ * cx, cy index steps per second; radius (m, > 0); vmax (m/s, >= 0); dp (Pa, >= 0) the central pressure deficit;
+ * cos_in, sin_in the inflow angle's cosine and sine, formed by the host (the device takes no sin or cos); turn
+ * +1.0 or -1.0, the sense of rotation.  ocn_ens_forcing_model (one per ensemble): the densities, the drag
+ * cd = min(cd0 + cd1 |U|, cd_max) and a background wind ub, vb.
+ *
+ * The point function (csrc/ens_forcing_point.h, the one text the device and the CPU test compile; every line one
+ * IEEE double operation, -ffp-contract=off, IEEE division and sqrt, exp = csrc/ocn_exp.h exp_libm; real(4)
+ * operands promoted first; ocean_model_arch_amd/ens_forcing_rule.py restates it in numpy):
+ *   per storm and time t:   p = cx t, xc = x0 + p;  p = cy t, yc = y0 + p;  rr = R R;  sv = vmax / R;
+ *                           ra = rho_air / rho_water
+ *   offsets of the index position (xi, yj) with sx, sy metres per index step:
+ *                           d = xi - xc, ex = d sx;  d = yj - yc, ey = d sy
+ *                           a = ex ex, b = ey ey, s = a + b, q = s / rr
+ *   wind:                   h = 0.5 q, a = 0.5 - h, a = a > -500 ? a : -500;  e = exp(a), s = sv e
+ *                           (a Gaussian vortex: the speed is vmax at r = R; no division by r, no pow, no log)
+ *                           te = turn ey, a = te cos_in, a = -a, b = ex sin_in, c = a - b, c = s c, uw = ub + c
+ *                           te = turn ex, a = te cos_in,         b = ey sin_in, c = a - b, c = s c, vw = vb + c
+ *                           a = uw uw, b = vw vw, s = a + b, w = sqrt(s)
+ *                           c = cd1 w, c = cd0 + c, cd = c < cd_max ? c : cd_max;  k = ra cd, k = k w
+ *                           taux = k uw, tauy = k vw            (the kinematic stress)
+ *   pressure:               h = -0.5 q, h = h > -500 ? h : -500;  e = exp(h), pa = dp e, pa = -pa
+ *   RHSx(m, n), the u-point (m + 1/2, n), where lcu(m, n) > 0.5 (else +0.0):
+ *                           the wind at (m + 0.5, n) with sx = dxt(m, n), sy = dyh(m, n)
+ *                           pa0, pa1 = the pressure at (m, n) and (m + 1, n), each with its own point's dx, dy
+ *                           ar = dxt dyh, a = taux ar;  d = pa1 - pa0, d = d / rho_water, d = d dyh
+ *                           hu = h_r(m, n) + h_r(m + 1, n), hu = 0.5 hu;  d = d hu;  RHSx = a - d
+ *   RHSy(m, n), the v-point (m, n + 1/2), where lcv(m, n) > 0.5 (else +0.0):
+ *                           the wind at (m, n + 0.5) with sx = dxh(m, n), sy = dyt(m, n)
+ *                           pa0, pa1 = the pressure at (m, n) and (m, n + 1)
+ *                           ar = dyt dxh, a = tauy ar;  d = pa1 - pa0, d = d / rho_water, d = d dxh
+ *                           hv = h_r(m, n) + h_r(m, n + 1), hv = 0.5 hv;  d = d hv;  RHSy = a - d
+ * The pressure term is sw_update_uv's slx / sly with pa / rho_water in the place of g ssh, linearized about the
+ * rest depth h_r (OCN_HHQ_REST): nothing a call's tail forms is read.  Both arrays are written at the interior
+ * points nx_start..nx_end x ny_start..ny_end only (all the general one-pass variant reads), from global indices:
+ * the result does not depend on the block grid.
+ *
+ * ocn_ens_forcing_check (pure, no device, as ocn_ens_plan): what ocn_ens_forcing_set refuses in n storms and a
+ * model -- a null argument, n < 1, a value that is not finite, radius <= 0, vmax, dp, a density, cd0, cd1 or cd_max
+ * negative, rho_water = 0, turn neither +1 nor -1, cos_in^2 + sin_in^2 off 1 by more than 1e-12: OCN_ERR_ARG.
+ * ocn_ens_forcing_set(ens, use, storms, model): after that check, storms[i] (one entry per member of the
+ * ensemble, read where use[i] != 0; use NULL: all) becomes member i's storm and the member is FORCED until
+ * ocn_ens_forcing_clear; members not in use keep what they had; the model replaces the ensemble's.  A forced
+ * member steps with the general one-pass variant at once (as with OCN_OPT_KNOWN_CONSTANTS 0: no verdict to wait
+ * for) and runs no pair launches (OCN_OPT_PAIR 2 would defer steps whose forcing belongs to another time);
+ * nothing changes for a context that is not forced.  ocn_ens_forcing_clear: no member is forced any more; the
+ * arrays keep the last forcing.
+ * ocn_ens_forcing_apply(ens, t): both arrays of every forced member for time t, one launch per local block
+ * (k_ens_forcing, csrc/ens_forcing.hip).  The pending call tails of the forced members are formed first (a tail
+ * re-runs the last step and must find that step's forcing); afterwards the two fields count as UPLOADED
+ * (ocn_ctx_upload's bookkeeping).  Any block grid, with or without tracers.  Asynchronous.
+ * ocn_ens_step_forced(ens, tau, nsteps, check_every, t0): nsteps steps of every member, step s (0-based) of a
+ * forced member with the forcing of t_s = t0 + (double)s tau; the checks at the steps s + 1 of this call that
+ * check_every divides.  Every field of every member afterwards is bit for bit what
+ * ocn_ens_forcing_apply(t_s); ocn_ens_step(tau, 1, ...) per step leaves: OCN_RHSX / OCN_RHSY hold the LAST
+ * step's forcing, so a later ocn_ens_complete re-runs that step correctly.  Members that are not forced step as
+ * in ocn_ens_step.  Asynchronous on the ensemble's stream, no host wait.  Two routes, the same bits:
+ *   chunked (always available): that loop.  A forced member whose open sequence the next step goes on with
+ *     (ocn_ens_step's lazy call tail: same tau, nothing deferred) has its two arrays rewritten under it with no
+ *     tail formed and nothing dropped -- its state is current and the pending tail will be that next step's -- so
+ *     its sequence stays open; every other forced member goes through ocn_ens_forcing_apply's bookkeeping.
+ *   in the launch (OCN_ENS_OPT_FORCING_IN_LAUNCH 1, the default; 0 for tests and measurements): where every forced
+ *     member would go into a multi-step launch group that goes on with its open sequence (what ocn_ens_step batches:
+ *     one small block, no tracers, check_every 0 or 1, at least 2 steps -- an earlier ocn_ens_step or
+ *     ocn_ens_step_forced call has opened the sequence), the groups that hold a forced member go as forcing
+ *     launches (sw_kernels.hip k_march_multi_frc, the general bodies): the forcing of t0 is written by one
+ *     k_ens_forcing launch ahead of them, and between the member's barriers each marching workgroup writes its
+ *     share of the NEXT step's forcing into the other of two buffers (the arrays themselves and a second pair the
+ *     ensemble owns per forced member, made at the first such call).  After an even number of steps the last
+ *     step's forcing is in the second pair: one more k_ens_forcing launch behind the groups forms it into the
+ *     arrays themselves.  A capacity of its own (the forcing kernels' occupancy) applies to such calls only.
+ * OCN_ERR_STATE with no forced member or before ocn_ens_init_state, OCN_ERR_ARG for nsteps < 0 or a tau or t0 that
+ * is not finite.
+ * ocn_ens_forcing_info: attached = forced members; applies = k_ens_forcing passes so far (ocn_ens_forcing_apply's
+ * and ocn_ens_step_forced's); steps = steps ocn_ens_step_forced has run; in_launch = 1 if the last
+ * ocn_ens_step_forced took the in-launch route, else 0. */
+typedef struct ocn_ens_storm {
+    double x0, y0, cx, cy, radius, vmax, dp, cos_in, sin_in, turn;
+} ocn_ens_storm;
+typedef struct ocn_ens_forcing_model {
+    double rho_air, rho_water, cd0, cd1, cd_max, ub, vb;
+} ocn_ens_forcing_model;
+typedef struct ocn_ens_forcing_info_t {
+    int32_t attached, in_launch;
+    int64_t applies, steps;
+} ocn_ens_forcing_info_t;
+int ocn_ens_forcing_check(const ocn_ens_storm *storms, int32_t n, const ocn_ens_forcing_model *model);
+int ocn_ens_forcing_set(ocn_ens *ens, const uint8_t *use, const ocn_ens_storm *storms, const ocn_ens_forcing_model *model);
+int ocn_ens_forcing_clear(ocn_ens *ens);
+int ocn_ens_forcing_apply(ocn_ens *ens, double t);
+int ocn_ens_step_forced(ocn_ens *ens, double tau, int32_t nsteps, int32_t check_every, double t0);
+int ocn_ens_forcing_info(ocn_ens *ens, ocn_ens_forcing_info_t *out);
 
 const char *ocn_last_error(void);
 int ocn_abi_version(void);

@@ -374,10 +374,13 @@ struct ocn_ctx {
     // a member of an ensemble (ocn_ens_create): the ensemble owns the context and its compute stream,
     // which the members share.  ens_collect (inside ocn_ens_step): step_impl plans a multi-step launch
     // as ever but leaves it to the ensemble, which issues it with the other members' (ens_pending, ens_k).
-    // ens_probe (inside ocn_ens_step_record): step_impl only says whether it would plan one (ens_pending) and
-    // runs none of the call's steps
+    // ens_probe (inside ocn_ens_step_record and ocn_ens_step_forced): step_impl only says whether it would plan one
+    // (ens_pending), or go on with an open sequence at all (ens_go), and runs none of the call's steps
     ocn_ens *ens = nullptr;
-    bool ens_collect = false, ens_pending = false, ens_probe = false;
+    bool ens_collect = false, ens_pending = false, ens_probe = false, ens_go = false;
+    // forced (ocn_ens_forcing_set): the ensemble writes OCN_RHSX / OCN_RHSY of this member for each step's own
+    // time -- the general one-pass variant at once (prepare_kc), no pair launches (pair_ok)
+    bool forced = false;
     ocn::StepKind ens_k{};
 };
 

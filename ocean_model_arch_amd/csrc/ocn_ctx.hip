@@ -1240,6 +1240,7 @@ static int one_step_multi(ocn_ctx *c, double tau, const StepKind &k)
 #endif
 static bool pair_ok(ocn_ctx *c)
 {
+    if (c->forced) return false;   // (a pair would defer steps whose forcing belongs to another time)
     if (!c->pair || c->blocks.size() != 1 || has_exchange(c) || has_comm(c) || c->ring_sea || !c->compact || !c->march ||
         c->sw.use_tracers > 0)
         return false;
@@ -2024,7 +2025,7 @@ static void set_kc_mode(ocn_ctx *c, int mode)
 }
 static int prepare_kc(ocn_ctx *c, bool x2 = false)
 {
-    if (!c->known_const || c->r8_handed) { set_kc_mode(c, OCN_KC_GENERAL); return OCN_OK; }
+    if (!c->known_const || c->r8_handed || c->forced) { set_kc_mode(c, OCN_KC_GENERAL); return OCN_OK; }
     learn_fb_async(c);
     if (c->fb_state != kFbUnchecked && x2 && !c->fb_x2) c->fb_state = kFbUnchecked;
     if (c->fb_state == kFbUnchecked) {
@@ -2229,14 +2230,16 @@ extern "C++" int ocn::complete_open(ocn_ctx *c)
     return finish_call(c, run_step(c, c->open_tau, last_step(c, false)));
 }
 
-// step_impl's answer to ocn_ens_step_record's probe (ens_probe): ens_pending = this call would be planned as
-// ONE multi-step launch -- the conditions of the open sequence's branch below in their order, the variant's
-// choice (prepare_kc) included -- with none of its steps run.  (Steps an earlier call deferred stay deferred:
+// step_impl's answer to ocn_ens_step_record's and ocn_ens_step_forced's probe (ens_probe): ens_pending = this call
+// would be planned as ONE multi-step launch -- the conditions of the open sequence's branch below in their order, the
+// variant's choice (prepare_kc) included -- with none of its steps run; ens_go = it would go on with the open
+// sequence at all, no deferred step ahead of its first one.  (Steps an earlier call deferred stay deferred:
 // the call itself runs them first.)
 static int probe_multi(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every)
 {
-    c->ens_pending = false;
+    c->ens_pending = c->ens_go = false;
     if (!c->open || tau != c->open_tau || !c->onepass || !lazy_allowed(c, c->open_x2)) return OCN_OK;
+    c->ens_go = c->deferred == 0;   // (the call's first step would be the open sequence's next one-pass step)
     RC(prepare_kc(c, c->open_x2));
     const bool graph_ok = c->use_graph && !has_comm(c) && !c->stage_timing && !(c->sw.use_tracers > 0 && c->tr_step);
     const bool pairs = c->open_x2 ? x4_now(c) : pair_ok(c);

@@ -1,6 +1,6 @@
 // ocn_ens.h -- the ensemble and what its host sources share (ocn_ens.hip, ocn_ens_diag.hip, ocn_ens_modify.hip,
-// ocn_ens_filter.hip, ocn_ens_record.hip).  Internal: not part of the C ABI (include/ocn_sw.h), included by those
-// five only.  No device code: the kernels behind these entries are in sw_kernels.hip and ens_*.hip.
+// ocn_ens_filter.hip, ocn_ens_record.hip, ocn_ens_forcing.hip).  Internal: not part of the C ABI (include/ocn_sw.h),
+// included by those six only.  No device code: the kernels behind these entries are in sw_kernels.hip and ens_*.hip.
 #pragma once
 #include "ocn_ctx.h"
 #include "ocn_ens_plan.h"
@@ -173,6 +173,25 @@ struct ocn_ens {
         EnsStage2 stage;
     } rec;
     bool rec_in_launch = true;     // OCN_ENS_OPT_RECORD_IN_LAUNCH
+    // ocn_ens_forcing_*: the moving-storm forcing.  storm: one per member (read where forced[i]); attached: the
+    // forced members.  tab: the launches' table, EnsFrcMember block by block, member by member; held: what its
+    // device side holds -- a call sends the table again only where it differs (the storms, who is forced, an
+    // array that moved).  second: per member the second RHSx / RHSy buffers of the forcing launch (sw_kernels.hip
+    // k_march_multi_frc), based like the member's own (raw: the allocations), made for a forced member at its
+    // first such call.  applies, steps, in_launch: ocn_ens_forcing_info's counts
+    struct Forcing {
+        std::vector<ocn_ens_storm> storm;
+        std::vector<uint8_t> forced;
+        ocn_ens_forcing_model model{};
+        int attached = 0;
+        EnsStage2 tab;
+        std::vector<EnsFrcMember> held;
+        struct Second { void *raw[2] = {nullptr, nullptr}; double *p[2] = {nullptr, nullptr}; };
+        std::vector<Second> second;
+        int32_t in_launch = 0;
+        int64_t applies = 0, steps = 0;
+    } frc;
+    bool frc_in_launch = true;     // OCN_ENS_OPT_FORCING_IN_LAUNCH
 };
 
 namespace ocn {
@@ -185,7 +204,12 @@ int32_t ens_variant(const ocn_ctx *c, double tau, bool check);
 // A recording call's part in ocn_ens_step's launches (ocn_ens_step_record's in-launch path): the capacity
 // in effect, the members' columns (-1: not in use), the first due step and its slot
 struct EnsRecCall { int64_t capacity; std::vector<int> col; int due0; double *slot0; };
-int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsRecCall *rec);
+// A forced call's part in them (ocn_ens_step_forced's in-launch path): the capacity in effect and the time of the
+// call's first step.  The groups that hold a forced member go as forcing launches; the forcing of t0 is written
+// behind the call's planning, ahead of the launches, and the last step's comes home behind them
+struct EnsFrcCall { int64_t capacity; double t0; };
+int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsRecCall *rec,
+                 const EnsFrcCall *frc = nullptr);
 void *ens_based_alloc(const LBlock &b, int32_t field, size_t bytes, void **raw);
 
 // The tail the three synchronous sampling entries share, in e->samp, reserved by the entry for up_b + res_b and
@@ -230,5 +254,10 @@ int ens_rec_members(const ocn_ens *e, const std::string &who, const uint8_t *use
                     std::vector<int> &col);
 int ens_rec_obs(const ocn_ens *e, const std::string &who, int32_t nobs, const int32_t *row, const int32_t *rec,
                 const double *wt, std::vector<EnsRecObs> &robs);
+
+// ---- ocn_ens_forcing.hip: RHSx / RHSy of every forced member for time t into the fields' own arrays -- the table
+// where it has changed, one launch per block, the known-constant verdicts dropped -- and nothing else: no tail is
+// formed, no other bookkeeping touched (the caller knows the members' sequences go on, or does the rest itself)
+int ens_frc_write(ocn_ens *e, double t);
 
 }  // namespace ocn

@@ -8,6 +8,7 @@
 //   ocn_ens_filter.hip  their localized observation update (ens_local.hip) and the serial filter's
 //                       observation-space loop in front of it (ens_assim.hip)
 //   ocn_ens_record.hip  the station recorder in their launches (sw_kernels.hip k_march_multi_rec)
+//   ocn_ens_forcing.hip the moving-storm forcing of their momentum equations (ens_forcing.hip)
 #include "ocn_ens.h"
 
 namespace ocn {
@@ -86,8 +87,8 @@ int32_t ens_variant(const ocn_ctx *c, double tau, bool check)
     return -1;
 }
 
-// ocn_ens_step, and with `rec` the same call with the recorder in its launches
-int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsRecCall *rec)
+// ocn_ens_step; with `rec` the same call with the recorder in its launches, with `frc` with the forcing in them
+int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsRecCall *rec, const EnsFrcCall *frc)
 {
     const int M = (int)e->m.size();
     e->last = ocn_ens_info_t{};
@@ -105,10 +106,21 @@ int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, co
         variant[(size_t)i] = ens_variant(c, tau, c->ens_k.check);
     }
     HIPCHK(hipSetDevice(e->device));
-    e->last.capacity = rec ? rec->capacity : ens_capacity(e);
+    e->last.capacity = rec ? rec->capacity : frc ? frc->capacity : ens_capacity(e);
     std::vector<ocn_ens_group> groups;
     note(ens_groups(e, variant, e->last.capacity, groups));
     std::vector<char> done((size_t)M, 0);
+    if (frc) {
+        // every forced member must be in a launch, as ocn_ens_step_forced's probe found it: one that planned
+        // otherwise has run its steps already, all under one forcing -- an error, never a silent result
+        std::vector<char> grouped((size_t)M, 0);
+        for (const ocn_ens_group &q : groups)
+            for (int j = 0; j < q.members; ++j) grouped[(size_t)q.member[j]] = 1;
+        for (int i = 0; i < M; ++i)
+            if (e->frc.forced[(size_t)i] && !grouped[(size_t)i])
+                note(set_error(OCN_ERR_STATE, "ens_step_forced: member " + std::to_string(i) + " planned its call otherwise than its probe"));
+        RC(ens_frc_write(e, frc->t0));   // (behind the planning, into the arrays step 0 reads)
+    }
     size_t rec_off = 0;   // (members of the recording launches so far: their EnsRecMember in the call's stage)
     if (!groups.empty()) {
         const int sl = e->tab.slot;
@@ -122,6 +134,7 @@ int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, co
             std::vector<EnsMember> ms((size_t)q.members);
             std::vector<ocn_ctx::Rec> recs((size_t)q.members);
             int rc = OCN_OK;
+            bool forcing = false;   // (the group holds a forced member of a forced call)
             for (int j = 0; j < q.members; ++j) {
                 ocn_ctx *c = e->m[(size_t)q.member[j]];
                 const LBlock &b = c->blocks[0];
@@ -132,6 +145,15 @@ int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, co
                                           {(double *)b.sshp_alt, (double *)b.up_alt, (double *)b.vp_alt},
                                           e->d_bar + (size_t)q.member[j] * (kMultiBarBytes / sizeof(unsigned)),
                                           c->d_nbad + 61, kc.kc, c->multi_spin};
+                if (frc && e->frc.forced[(size_t)q.member[j]]) {
+                    const ocn_ens::Forcing::Second &sec = e->frc.second[(size_t)q.member[j]];
+                    ms[(size_t)j].index = q.member[j];
+                    ms[(size_t)j].frc2[0] = sec.p[0];
+                    ms[(size_t)j].frc2[1] = sec.p[1];
+                    forcing = true;
+                } else if (frc) {
+                    ms[(size_t)j].index = q.member[j];
+                }
                 if (!c->fused) c->hn_fresh = false;
                 if (!rc) rc = timer_begin(c, OCN_TIMER_ONEPASS_MULTI, recs[(size_t)j]);
             }
@@ -149,6 +171,11 @@ int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, co
                 rc = launch_onepass_multi_rec(ms.data(), q.members, q.variant, q.rows, e->m[(size_t)q.member[0]]->sw, tau,
                                               nsteps, e->tab.d, (char *)e->tab.h[sl] + off, eb * (size_t)q.members,
                                               (long)e->last.capacity, rl, e->stream);
+            } else if (!rc && forcing) {
+                const EnsFrcLaunch fl{(const EnsFrcMember *)e->frc.tab.d, e->frc.model, frc->t0};
+                rc = launch_onepass_multi_frc(ms.data(), q.members, q.variant, q.rows, e->m[(size_t)q.member[0]]->sw, tau,
+                                              nsteps, e->tab.d, (char *)e->tab.h[sl] + off, eb * (size_t)q.members,
+                                              (long)e->last.capacity, fl, e->stream);
             } else if (!rc) {
                 rc = launch_onepass_multi_b(ms.data(), q.members, q.variant, q.rows, e->m[(size_t)q.member[0]]->sw, tau,
                                             nsteps, e->tab.d, (char *)e->tab.h[sl] + off, eb * (size_t)q.members,
@@ -180,6 +207,9 @@ int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, co
         }
         RC(e->tab.sent(sl, e->stream));
     }
+    // the last step's forcing home: after an even number of steps it is in the second buffers; formed again into
+    // the fields' own arrays behind the launches (the same operations: the same bits), where a later tail finds it
+    if (frc && ((nsteps - 1) & 1)) note(ens_frc_write(e, frc->t0 + (double)(nsteps - 1) * tau));
     // planned members in no group (no variant the launch takes, or too many tiles for the capacity in
     // effect): their own multi-step launch, as ocn_ctx_step issues it
     for (int i = 0; i < M; ++i) {
@@ -232,6 +262,10 @@ int ocn_ens_destroy(ocn_ens *e)
     for (void *r : e->perturb.raw)
         if (r) (void)hipFree(r);
     ens_rec_free(e);
+    e->frc.tab.release();
+    for (ocn_ens::Forcing::Second &q : e->frc.second)
+        for (void *r : q.raw)
+            if (r) (void)hipFree(r);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
     return OCN_OK;
@@ -334,6 +368,10 @@ int ocn_ens_set_option(ocn_ens *e, int32_t key, int64_t value)
     case OCN_ENS_OPT_RECORD_IN_LAUNCH:
         if (value != 0 && value != 1) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_RECORD_IN_LAUNCH: 0 or 1");
         e->rec_in_launch = value != 0;
+        return OCN_OK;
+    case OCN_ENS_OPT_FORCING_IN_LAUNCH:
+        if (value != 0 && value != 1) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_FORCING_IN_LAUNCH: 0 or 1");
+        e->frc_in_launch = value != 0;
         return OCN_OK;
     default: return set_error(OCN_ERR_ARG, "unknown ensemble option");
     }

@@ -214,6 +214,10 @@ struct EnsMember {
     int32_t *err;
     const double *kc;
     int spin;
+    // launch_onepass_multi_frc alone: the member's index in the ensemble (its entry of the forcing table) and,
+    // for a forced member, its second RHSx / RHSy buffers (the odd steps' table names them)
+    int index = 0;
+    double *frc2[2] = {nullptr, nullptr};
 };
 int onepass_multi_variant(int kc_mode, double tau, bool check);
 size_t onepass_multi_b_entry_bytes();
@@ -364,6 +368,32 @@ int launch_ens_noise(const ocn_block *b, const uint8_t *members, int n, uint64_t
                      long long *d_z, long zstride, int lead, hipStream_t s);
 int launch_ens_perturb_apply(const ocn_block *b, double *const *mem, int n, const long long *d_z, long zstride, bool centre,
                              double c, const float *d_mask, hipStream_t s);
+// The moving-storm forcing (ens_forcing.hip; ocn_sw.h ocn_ens_forcing_apply): OCN_RHSX / OCN_RHSY of every forced
+// member of one block geometry for time t, at the block's interior points.  d_tab: `members` entries on the
+// device, one per member of the ensemble -- its storm, its arrays of this block (the real(4) masks and metrics,
+// h_r, the two outputs) and whether it is forced (others are left alone).  lead: the lane of A(bnd_x1, :) within
+// its 256-B line.  ONE launch.  rx2, ry2: the member's second buffers (launch_onepass_multi_frc; else null).
+struct EnsFrcMember {
+    ocn_ens_storm s;
+    const float *lcu, *lcv, *dx, *dy, *dxt, *dyt, *dxh, *dyh;
+    const double *hr;
+    double *rx, *ry, *rx2, *ry2;
+    int forced, pad;
+};
+int launch_ens_forcing(const ocn_block *b, const EnsFrcMember *d_tab, int members, const ocn_ens_forcing_model &model,
+                       double t, int lead, hipStream_t s);
+// launch_onepass_multi_b with the forcing formed in the launch (sw_kernels.hip k_march_multi_frc; ocn_sw.h
+// ocn_ens_step_forced), for the general variants only: step s (0-based) of a forced member reads RHSx / RHSy from
+// buffer s & 1 -- 0 the fields' own arrays, 1 the member's second pair (EnsMember::frc2) -- and between its march
+// of step s and the barrier behind it every workgroup writes its share of the forcing of t0 + (double)(s + 1) tau
+// into buffer (s + 1) & 1.  The caller has written the forcing of t0 into the fields' own arrays ahead of the
+// launch.  d_tab: the forcing table of the block (launch_ens_forcing's), indexed by EnsMember::index; a member that
+// is not forced there marches as in launch_onepass_multi_b.  capacity: at most onepass_multi_frc_capacity().
+struct EnsFrcLaunch { const EnsFrcMember *d_tab; ocn_ens_forcing_model model; double t0; };
+long onepass_multi_frc_capacity();
+int launch_onepass_multi_frc(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
+                             int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, const EnsFrcLaunch &frc,
+                             hipStream_t s);
 // the known-constant precondition of launch_onepass over r (sw_kernels.hip FallbackCheck: the
 // fallback points and the forcing hold +0.0, h_r and mu are uniform): ORs 1 into *flag where it
 // does not hold; writes h_r and mu at (r.m0, r.n0) to kc[0], kc[1]

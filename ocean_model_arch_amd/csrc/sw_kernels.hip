@@ -31,6 +31,7 @@
 #include <mutex>
 #include <type_traits>
 
+#include "ens_forcing_point.h"
 #include "ocn_internal.h"
 #include "sw_stencils.h"
 
@@ -3515,6 +3516,82 @@ __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_rec(const
     }
 }
 
+// k_march_multi_frc: k_march_multi_b's loop with the moving-storm forcing formed in it (ocn_sw.h
+// ocn_ens_step_forced), for the general bodies (the variant a forced member runs).  The forcing is
+// double-buffered: body b[0]'s field table names the fields' own RHSx / RHSy arrays, b[1]'s a second pair the
+// ensemble owns, so step s reads buffer s & 1.  The host has written the forcing of t0 into buffer 0 ahead of the
+// launch.  Between its march_tile of step s and its arrival at the member's barrier, every workgroup of a forced
+// member writes its share -- a stride loop over the interior's points, as k_march_multi_rec shares the rows -- of
+// the forcing of t0 + (double)(s + 1) tau into buffer (s + 1) & 1, by ens_forcing_point.h frc_point: the
+// operations k_ens_forcing runs in the same order (-ffp-contract=off), so the same bits.
+// No race: buffer (s + 1) & 1 was last read by step s - 1, and no workgroup starts step s -- so none reaches
+// this loop -- before all have finished step s - 1 and passed the barrier behind it; step s itself reads the
+// other buffer.  The stores are the march's write-through form (st_on<16>: sc1 buffer stores), drained by the
+// barrier's vmcnt(0) before the arrival: the barrier has no L2 write-back and the XCDs share no L2.  The next
+// step reads them with the march's ordinary loads behind the barrier's acquire, as it reads the state.  The
+// masks, metrics and h_r are never written by a kernel of the launch: ordinary loads too.  The members' table
+// (EnsFrcMember, indexed by EnsEntry::pad: the member's index in the ensemble) is written by a copy ordered
+// before the launch: scalar loads through the constant address space.  A member that is not forced skips the
+// loop (workgroup-uniform) and marches as in k_march_multi_b.  No atomics or LDS beyond the barrier's.
+struct EnsFrcArgs {
+    const EnsFrcMember *tab;
+    ocn_ens_forcing_model mo;
+    double t0, tau;
+    int i0, i1, j0, j1;   // the interior, as offsets into the array
+    long pitch;
+    unsigned nbytes;      // the array's size (st_on's range)
+    int gx, gy;           // bnd_x1, bnd_y1: the global indices of the array's first element
+};
+typedef const EnsFrcMember __attribute__((address_space(4))) *ConstFrc;
+__device__ __forceinline__ void frc_fill(ConstFrc fm, const EnsFrcArgs &a, int step, int tile, int tiles)
+{
+    const ocn_ens_storm st = *(const ocn_ens_storm *)&fm->s;
+    const double ts = a.t0 + (double)step * a.tau;
+    const FrcAt c = frc_at(st, a.mo, ts);
+    const bool odd = __builtin_amdgcn_readfirstlane(step & 1) != 0;
+    double *const rx = odd ? fm->rx2 : fm->rx, *const ry = odd ? fm->ry2 : fm->ry;
+    const float *const lcu = fm->lcu, *const lcv = fm->lcv, *const dx = fm->dx, *const dy = fm->dy, *const dxt = fm->dxt,
+                *const dyt = fm->dyt, *const dxh = fm->dxh, *const dyh = fm->dyh;
+    const double *const hr = fm->hr;
+    const int w = a.i1 - a.i0 + 1, n = w * (a.j1 - a.j0 + 1);
+    for (int q = tile * 256 + (int)threadIdx.x; q < n; q += tiles * 256) {
+        const int j = q / w, i = q - j * w;
+        const long at = (long)(a.j0 + j) * a.pitch + (a.i0 + i);
+        FrcPoint p;
+        p.lcu = lcu[at]; p.lcv = lcv[at];
+        p.dxt = dxt[at]; p.dyt = dyt[at]; p.dxh = dxh[at]; p.dyh = dyh[at];
+        p.dx0 = dx[at]; p.dy0 = dy[at]; p.dx1 = dx[at + 1]; p.dy1 = dy[at + 1]; p.dx2 = dx[at + a.pitch]; p.dy2 = dy[at + a.pitch];
+        p.h0 = hr[at]; p.h1 = hr[at + 1]; p.h2 = hr[at + a.pitch];
+        double vx, vy;
+        frc_point(st, a.mo, c, a.gx + a.i0 + i, a.gy + a.j0 + j, p, vx, vy);
+        st_on<16>(rx, a.nbytes, (unsigned)at, vx, true);
+        st_on<16>(ry, a.nbytes, (unsigned)at, vy, true);
+    }
+}
+
+template <class Body>
+__global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_frc(const EnsEntry<Body> *__restrict__ tab, int tiles,
+                                                                           int nsteps, const EnsFrcArgs frc)
+{
+    typedef const EnsEntry<Body> __attribute__((address_space(4))) *ConstTab;
+    const int mem = __builtin_amdgcn_readfirstlane((int)blockIdx.x / tiles);
+    const int tile = (int)blockIdx.x - mem * tiles;
+    ConstTab e = (ConstTab)tab + mem;
+    ConstFrc fm = (ConstFrc)frc.tab + e->pad;
+    const MarchRect R = *(const MarchRect *)&e->R;
+    unsigned *const bar = e->bar;
+    int32_t *const err = e->err;
+    const int spin = e->spin;
+    const bool forced = fm->forced != 0;
+    if constexpr (HasPrologue<Body>::v) ((const Body *)&e->b[0])->prologue(R, tile / R.ntx);   // the same rows every step
+    for (int s = 0; s < nsteps; ++s) {
+        march_tile<Body, false>(R, tile, *(const Body *)&e->b[__builtin_amdgcn_readfirstlane(s & 1)]);
+        if (s + 1 == nsteps) break;
+        if (forced) frc_fill(fm, frc, s + 1, tile, tiles);
+        if (!member_barrier(bar, (unsigned)tiles, (unsigned)tile, (unsigned)(s + 1), err, spin)) return;
+    }
+}
+
 // the variant of a member's launch as the planner's id: 2 x (0 known-constant, 1 h_r-read, 2 general)
 // + (tau a power of two), + 6 with the per-step check; -1: no variant chosen on the host
 int onepass_multi_variant(int kc_mode, double tau, bool check)
@@ -3548,10 +3625,36 @@ long onepass_multi_rec_capacity()
                              [](auto tag) { return k_march_multi_rec<typename decltype(tag)::type>; });
 }
 
-// launch_onepass_multi_b (rec null) and launch_onepass_multi_rec behind their checks: one table of entries, one launch
+// the resident capacity of the forcing launch: onepass_multi_b_capacity() and the forcing kernels' own occupancy
+// x CUs (kept apart, as the recording launch's: no plan of a call without forcing changes)
+long onepass_multi_frc_capacity()
+{
+    static CapacityCache cache;
+    const long base = onepass_multi_b_capacity();
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    std::lock_guard<std::mutex> g(cache.mu);
+    const auto it = cache.cap.find(dev);
+    if (it != cache.cap.end()) return it->second;
+    long c = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? base : 0;
+    for (int p2 = 0; p2 < 2; ++p2)
+        step_dispatch<false, false, false, true, false>(p2 != 0, OCN_KC_GENERAL, [&](auto tag) {
+            using Body = typename decltype(tag)::type;
+            if constexpr (Body::kLds == 0) {   // (the general bodies: the only ones the kernel is built for)
+                int per = 0;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_march_multi_frc<Body>, 256, 0) != hipSuccess) per = 0;
+                c = std::min(c, (long)per * cus);
+            }
+            return 0;
+        });
+    return cache.cap[dev] = c;
+}
+
+// launch_onepass_multi_b (rec and frc null), launch_onepass_multi_rec and launch_onepass_multi_frc behind their
+// checks: one table of entries, one launch
 static int launch_multi_b_impl(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
                                int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, const EnsRecLaunch *rec,
-                               hipStream_t s)
+                               hipStream_t s, const EnsFrcLaunch *frc = nullptr)
 {
     if (!m || n < 1 || variant < 0 || variant >= 12 || rows < 1 || rows > 16 || nsteps < 1 || !d_tab || !h_tab)
         return set_error(OCN_ERR_ARG, "ensemble launch: members, a variant, 1..16 rows, a table");
@@ -3581,6 +3684,10 @@ static int launch_multi_b_impl(const EnsMember *m, int n, int variant, int rows,
             double *alt[3] = {e.alt[0], e.alt[1], e.alt[2]};
             const int ids[3] = {OCN_SSHP, OCN_UBRTRP, OCN_VBRTRP};
             for (int j = 0; j < 3; ++j) std::swap(odd[ocn_field_slot(ids[j])], *(void **)&alt[j]);
+            if (frc && e.frc2[0] && e.frc2[1]) {   // (a forced member: the odd steps read its second forcing buffers)
+                odd[ocn_field_slot(OCN_RHSX)] = e.frc2[0];
+                odd[ocn_field_slot(OCN_RHSY)] = e.frc2[1];
+            }
             const Tab<true> t0 = make_tab<true>(e.ptr, e.nptr, e.cp->bits, e.cp->rows, block_rows(e.b), 0);
             const Tab<true> t1 = make_tab<true>(odd.data(), e.nptr, e.cp->bits, e.cp->rows, block_rows(e.b), 0);
             int32_t *const nbad = check ? e.nbad : nullptr;
@@ -3592,13 +3699,14 @@ static int launch_multi_b_impl(const EnsMember *m, int n, int variant, int rows,
             tab[i].bar = e.ctr;
             tab[i].err = e.err;
             tab[i].spin = e.spin < 1 ? 1 : e.spin;
-            tab[i].pad = 0;
+            tab[i].pad = frc ? e.index : 0;
             if (tab[i].R.tiles != multi_tiles(r, rows) || (i && tab[i].R.tiles != tiles))
                 return set_error(OCN_ERR_ARG, "ensemble launch: the members' tile counts differ");
             tiles = tab[i].R.tiles;
         }
         // residency from the grid size alone, as the single-member launch: every workgroup at once
-        if ((long)n * tiles > capacity || capacity > (rec ? onepass_multi_rec_capacity() : onepass_multi_b_capacity()))
+        if ((long)n * tiles > capacity ||
+            capacity > (rec ? onepass_multi_rec_capacity() : frc ? onepass_multi_frc_capacity() : onepass_multi_b_capacity()))
             return set_error(OCN_ERR_ARG, "ensemble launch: grid larger than the resident capacity");
         EnsRecArgs ra{};
         if (rec) {   // the recorder's tables: per member the operator's fields in both parities' buffers, and the column
@@ -3626,10 +3734,21 @@ static int launch_multi_b_impl(const EnsMember *m, int n, int variant, int rows,
         RC_K(check_hip(hipMemcpyAsync(d_tab, h_tab, sizeof(Entry) * (size_t)n, hipMemcpyHostToDevice, s),
                        "ensemble launch: member table"));
         count_launch();
-        if (rec)
+        if (frc) {
+            if constexpr (Body::kLds == 0) {   // (the general bodies)
+                const ocn_block &g = *m[0].b;
+                const EnsFrcArgs fa{frc->d_tab, frc->model, frc->t0, tau, g.nx_start - g.bnd_x1, g.nx_end - g.bnd_x1,
+                                    g.ny_start - g.bnd_y1, g.ny_end - g.bnd_y1, (long)g.pitch,
+                                    (unsigned)(g.pitch * (g.bnd_y2 - g.bnd_y1 + 1) * 8), (int)g.bnd_x1, (int)g.bnd_y1};
+                k_march_multi_frc<Body><<<dim3((unsigned)(n * tiles)), dim3(256), 0, s>>>((const Entry *)d_tab, tiles, nsteps, fa);
+            } else {
+                return set_error(OCN_ERR_ARG, "ensemble launch: the forcing launch has the general bodies only");
+            }
+        } else if (rec) {
             k_march_multi_rec<Body><<<dim3((unsigned)(n * tiles)), dim3(256), 0, s>>>((const Entry *)d_tab, tiles, nsteps, ra);
-        else
+        } else {
             k_march_multi_b<Body><<<dim3((unsigned)(n * tiles)), dim3(256), 0, s>>>((const Entry *)d_tab, tiles, nsteps);
+        }
         return check_hip(hipGetLastError(), "ensemble launch");
     });
 }
@@ -3652,6 +3771,19 @@ int launch_onepass_multi_rec(const EnsMember *m, int n, int variant, int rows, c
             rec.field[f] != OCN_VBRTR && rec.field[f] != OCN_VBRTRP)
             return set_error(OCN_ERR_ARG, "ensemble launch: the recorder reads the six prognostic fields only");
     return launch_multi_b_impl(m, n, variant, rows, sw, tau, nsteps, d_tab, h_tab, tab_bytes, capacity, &rec, s);
+}
+
+int launch_onepass_multi_frc(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
+                             int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, const EnsFrcLaunch &frc,
+                             hipStream_t s)
+{
+    if (!frc.d_tab || variant < 0 || (variant % 6) / 2 != 2)
+        return set_error(OCN_ERR_ARG, "ensemble launch: the forcing's table, or a variant that is not the general one");
+    for (int i = 0; m && i < n; ++i) {
+        if (m[i].index < 0 || m[i].index >= OCN_ENS_MAX_MEMBERS || !m[i].b || (i && std::memcmp(m[i].b, m[0].b, sizeof(ocn_block))))
+            return set_error(OCN_ERR_ARG, "ensemble launch: a member's index in the forcing table, or members of different blocks");
+    }
+    return launch_multi_b_impl(m, n, variant, rows, sw, tau, nsteps, d_tab, h_tab, tab_bytes, capacity, nullptr, s, &frc);
 }
 
 // Rows per workgroup tile of the two-step launch: the fewest iterations in total, counting

@@ -12,7 +12,7 @@ import operator
 
 import numpy as np
 
-from . import _lib, ens_local_rule, ens_obs_rule, ens_perturb_rule, ens_record_rule
+from . import _lib, ens_forcing_rule, ens_local_rule, ens_obs_rule, ens_perturb_rule, ens_record_rule
 from ._lib import check, lib
 from .config import BasinConfig, ParallelConfig, SWConfig
 from .model import BlockInfo, OceanModel
@@ -821,6 +821,87 @@ class OceanEnsemble:
         if rtps is not None:   # (behind the analysis, before the device path's first wait)
             self.inflate(alpha, "rtps", names, members=eff)
         return finish()
+
+    # ------------------------------------------------------------ moving-storm forcing
+    def set_storms(self, storms, model=None, members=None):
+        """Attach a moving storm to members (ocn_ens_forcing_set; the rule is in include/ocn_sw.h, its numpy
+        restatement in ens_forcing_rule.py): `storms` holds one ens_forcing_rule.Storm per member in use --
+        `members` (indices; None: all) in member order, or a {member index: Storm} dict, which then names the
+        members itself.  `model`: an ens_forcing_rule.ForcingModel (None: its defaults) for the whole ensemble.
+        A member with a storm is forced until clear_storms(): forcing(t) and step_forced() write its RHSx / RHSy,
+        it steps with the general one-pass variant and runs no pair launches.  TypeError for an argument of the
+        wrong type, ValueError for a value the library refuses."""
+        model = ens_forcing_rule.ForcingModel() if model is None else model
+        ens_forcing_rule.check_model(model)
+        if isinstance(storms, dict):
+            if members is not None:
+                raise ValueError("set_storms: a dict of storms names the members itself")
+            idx = sorted(operator.index(i) for i in storms)
+            by = {operator.index(i): s for i, s in storms.items()}
+        else:
+            idx = list(range(len(self.members))) if members is None else sorted({operator.index(i) for i in members})
+            seq = list(storms)
+            if len(seq) != len(idx):
+                raise ValueError(f"set_storms: {len(seq)} storms for {len(idx)} members in use")
+            by = dict(zip(idx, seq))
+        if not idx:
+            raise ValueError("set_storms: no member in use")
+        use = self._use(idx)
+        arr = (_lib.OcnEnsStorm * len(self.members))()
+        for i in idx:
+            ens_forcing_rule.check_storm(by[i], f"set_storms: member {i}")
+            arr[i] = _lib.OcnEnsStorm(*ens_forcing_rule.storm_values(by[i]))
+        cm = _lib.OcnEnsForcingModel(*ens_forcing_rule.model_values(model))
+        check(lib().ocn_ens_forcing_set(self.ens, use, arr, C.byref(cm)), "ocn_ens_forcing_set")
+        return self
+
+    def clear_storms(self):
+        """No member is forced any more (ocn_ens_forcing_clear); RHSx / RHSy keep the last forcing."""
+        check(lib().ocn_ens_forcing_clear(self.ens), "ocn_ens_forcing_clear")
+        return self
+
+    def forcing(self, t: float):
+        """RHSx / RHSy of every forced member for time t (seconds), on the device, one launch per block
+        (ocn_ens_forcing_apply).  Pending call tails of the forced members are formed first; the two fields then
+        count as uploaded.  Asynchronous."""
+        if isinstance(t, (str, bytes, bool)) or np.ndim(t) != 0:
+            raise TypeError(f"forcing: t = {t!r}, not a number")
+        if not np.isfinite(float(t)):
+            raise ValueError("forcing: a time that is not finite")
+        check(lib().ocn_ens_forcing_apply(self.ens, float(t)), "ocn_ens_forcing_apply")
+        return self
+
+    def step_forced(self, nsteps: int, tau: float, t0: float, check_every: int = 1):
+        """nsteps steps of every member, step s (0-based) of a forced member under the forcing of
+        t0 + s * tau (ocn_ens_step_forced): the members end up bit for bit as after forcing(t0 + s * tau);
+        step(1, tau) per step, with no host work in between.  Where the forced members' calls are multi-step
+        launches that go on with an open sequence (a step() or step_forced() call before this one has opened it),
+        the marching launches form the forcing themselves between their steps (forcing_info()["in_launch"]).
+        Members without a storm step as in step()."""
+        if isinstance(nsteps, bool) or not isinstance(nsteps, (int, np.integer)):
+            raise TypeError(f"step_forced: nsteps = {nsteps!r}, not an integer")
+        if nsteps < 0:
+            raise ValueError(f"step_forced: nsteps = {nsteps} < 0")
+        for what, v in (("tau", tau), ("t0", t0)):
+            if isinstance(v, (str, bytes, bool)) or np.ndim(v) != 0:
+                raise TypeError(f"step_forced: {what} = {v!r}, not a number")
+            if not np.isfinite(float(v)):
+                raise ValueError(f"step_forced: a {what} that is not finite")
+        check(lib().ocn_ens_step_forced(self.ens, float(tau), int(nsteps), int(check_every), float(t0)), "ocn_ens_step_forced")
+        return self
+
+    def forcing_info(self) -> dict:
+        """ocn_ens_forcing_info: attached (forced members), applies (forcing passes so far, step_forced's included),
+        steps (steps step_forced has run) and in_launch (whether the last step_forced formed the forcing inside
+        its marching launches; False: one forcing launch ahead of each step)."""
+        i = _lib.OcnEnsForcingInfo()
+        check(lib().ocn_ens_forcing_info(self.ens, C.byref(i)), "ocn_ens_forcing_info")
+        return {"attached": int(i.attached), "in_launch": bool(i.in_launch), "applies": int(i.applies), "steps": int(i.steps)}
+
+    def set_forcing_in_launch(self, on: bool = True):
+        """Tests and measurements: off, step_forced() always takes the chunked route."""
+        check(lib().ocn_ens_set_option(self.ens, _lib.ENS_OPT_FORCING_IN_LAUNCH, int(bool(on))), "ocn_ens_set_option")
+        return self
 
     def set_record_in_launch(self, on: bool = True):
         """Tests and measurements: off, step_record() always takes the chunked route."""
