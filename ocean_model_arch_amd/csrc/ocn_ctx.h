@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "ocn_internal.h"
+#include "ocn_step_plan.h"
 
 namespace ocn {
 
@@ -145,36 +146,6 @@ struct HaloPlan {
     SegList pack, unpack;
 };
 
-namespace ocn {
-// What one step of an ocn_ctx_step call runs: check = check_ssh_err; first / last step of the
-// call; flip = role-flip step; a_done = its fused A already ran (fused into the previous step's
-// hh_init launch); next_a = fuse the next step's fused A into this step's hh_init (MarchCA),
-// next_reuse = the next step is a reuse step; rc = recompute steps (fused B forms hhq, hhu_p,
-// hhv_p itself and writes sshp's filter into the second sshp buffer), rc_next = the next step is
-// one (this step's hh_init + A launch then does not store hhq on the interior, hhu_p, hhv_p).
-// one = one-pass step (sw_kernels.hip MarchStep), next_one = the next step is one (this step
-// then runs no hh_init: the one-pass step forms hh_init's values itself).
-// x2 = the one-pass step as one_step_x2 (2-deep state exchange, whole-interior march); x2_save = the
-// first of a sequence (the reference's second halo ring of the state is saved first); x2_end = a
-// last step after such a sequence (that ring restored and the state's first ring exchanged first).
-// pair = this one-pass step and the next as one launch (one_step_pair), check2 = the next one's check.
-// multi = this many one-pass steps in one launch (one_step_multi), each checked if check.
-struct StepKind {
-    bool check, first, last, flip, a_done, next_a, next_reuse, rc, rc_next, one, next_one, one_last;
-    bool x2, x2_save, x2_end;
-    bool pair = false, check2 = false;
-    int multi = 0;
-    bool operator==(const StepKind &o) const
-    {
-        return check == o.check && first == o.first && last == o.last && flip == o.flip && a_done == o.a_done &&
-               next_a == o.next_a && next_reuse == o.next_reuse && rc == o.rc && rc_next == o.rc_next &&
-               one == o.one && next_one == o.next_one && one_last == o.one_last && x2 == o.x2 &&
-               x2_save == o.x2_save && x2_end == o.x2_end && pair == o.pair && check2 == o.check2 && multi == o.multi;
-    }
-};
-
-}  // namespace ocn
-
 // ocn_ctx::fb_state
 enum { kFbUnchecked = 0, kFbDevice = 1, kFbZero = 2, kFbGeneral = 3, kFbHr = 4 };
 
@@ -263,6 +234,7 @@ struct ocn_ctx {
     // OCN_OPT_MULTI: the one-pass steps of a small single block as one launch per call
     // (one_step_multi); multi_used: the last call ran one
     bool multi = true, multi_used = false;
+    mutable int multi_fits = -1;   // onepass_multi_fits of the one block (-1: not asked yet; geometry and device stay)
     // OCN_OPT_TRACER_STEP: tracer runs with one-pass steps -- expl_tracer of each step as one launch per
     // tracer (run_tracer_step), run with the next step, after its exchange; tr_call: this call does;
     // tr_pending: the current state's tracer step has not run yet; tr_alt_ok: the second ff1p
@@ -372,12 +344,11 @@ struct ocn_ctx {
     bool batch = true;           // OCN_OPT_BATCH
     ocn::Batcher batcher;
     // a member of an ensemble (ocn_ens_create): the ensemble owns the context and its compute stream,
-    // which the members share.  ens_collect (inside ocn_ens_step): step_impl plans a multi-step launch
-    // as ever but leaves it to the ensemble, which issues it with the other members' (ens_pending, ens_k).
-    // ens_probe (inside ocn_ens_step_record and ocn_ens_step_forced): step_impl only says whether it would plan one
-    // (ens_pending), or go on with an open sequence at all (ens_go), and runs none of the call's steps
+    // which the members share.  Inside ocn_ens_step (step_entry with collect) step_impl plans a multi-step
+    // launch as ever but leaves it to the ensemble, which issues it with the other members': ens_pending = the
+    // call left one, ens_k = its kind.  (What a call would plan, with none of its steps run: step_probe.)
     ocn_ens *ens = nullptr;
-    bool ens_collect = false, ens_pending = false, ens_probe = false, ens_go = false;
+    bool ens_pending = false;
     // forced (ocn_ens_forcing_set): the ensemble writes OCN_RHSX / OCN_RHSY of this member for each step's own
     // time -- the general one-pass variant at once (prepare_kc), no pair launches (pair_ok)
     bool forced = false;
@@ -462,7 +433,8 @@ void swap_alt3(ocn_ctx *c);
 int run_step(ocn_ctx *c, double tau, const StepKind &k);
 int finish_call(ocn_ctx *c, int rc);
 int complete_open(ocn_ctx *c);
-int step_entry(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every);
+int step_entry(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every, bool collect = false);
+int step_probe(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every, bool *multi, bool *go);
 // field id counts as uploaded: ocn_ctx_upload's bookkeeping and nothing else, for an entry that has
 // rewritten the field's current array on the context's stream (ocn_ens_transform); no pending tail open
 void field_uploaded(ocn_ctx *c, int id);

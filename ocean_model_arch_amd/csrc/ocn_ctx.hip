@@ -1,5 +1,6 @@
 // ocn_ctx.hip -- PSy layer of the MI355X shallow-water step: the stages, every step form, the call
-// planner (step_impl, complete_open, run_deferred, finish_call), check_coherence and the ocn_ctx_*
+// driver (step_impl, step_probe, complete_open, run_deferred, finish_call: the device phases around the plans
+// of ocn_step_plan.h), check_coherence and the ocn_ctx_*
 // entries of the C ABI.  The context itself is ocn_ctx.h; its halo exchange is ctx_comm.hip, its
 // decomposition, storage and initial state ctx_setup.hip, the ensemble layer ocn_ens*.hip.
 //
@@ -604,10 +605,7 @@ static int check_coherence(ocn_ctx *c, const VoteIn &in, VoteOut &out)
 // swapped roles (get_plan), the ring launch (a8 + a9 on the halo ring) runs after sync B, and
 // each hh_init's sync and the next step's sync A are one exchange (sync_ca); the exchanges do
 // not overlap computation in these steps.
-static bool flip_eligible(ocn_ctx *c)
-{
-    return c->flip && c->fused && c->compact && c->march;
-}
+// (the condition: ocn_step_plan.h flip_eligible)
 
 // The reuse steps (sw_stencils.h) leave hh_update's n-level depths unexchanged: a9 then forms the
 // p levels on the halo ring from stale values, which is harmless only because uv_trans's exchange of
@@ -1230,38 +1228,6 @@ static int one_step_multi(ocn_ctx *c, double tau, const StepKind &k)
         swap_roles(c);
     }
     return OCN_OK;
-}
-
-// one_step_pair possible in this call: one block without exchanges or ring work, the compact tables
-// and the march, the one-pass variant chosen by the host (kc_mode not OCN_KC_DEVICE; OCN_OPT_PAIR 1:
-// a known-constant one on blocks of 512^2 or more, 2: any)
-#ifndef OCN_PAIR_MIN_CELLS
-#define OCN_PAIR_MIN_CELLS (512L * 512L)
-#endif
-static bool pair_ok(ocn_ctx *c)
-{
-    if (c->forced) return false;   // (a pair would defer steps whose forcing belongs to another time)
-    if (!c->pair || c->blocks.size() != 1 || has_exchange(c) || has_comm(c) || c->ring_sea || !c->compact || !c->march ||
-        c->sw.use_tracers > 0)
-        return false;
-    if (c->kc_mode == OCN_KC_DEVICE) return false;   // (the variant the launches run is chosen on the device)
-    if (c->pair >= 2) return true;
-    // the default: the known-constant variants only -- the general variant's pair is VALU bound at
-    // twice its single launch (4096^2: 1.09 vs 0.54 ms), no faster
-    if (c->kc_mode == OCN_KC_GENERAL) return false;
-    const ocn_block &g = c->blocks[0].g;
-    return (long)(g.nx_end - g.nx_start + 1) * (g.ny_end - g.ny_start + 1) >= OCN_PAIR_MIN_CELLS;
-}
-
-// one_step_multi possible in this call (an open sequence, pairs not used): one block without exchanges or
-// ring work, the compact tables and the march, the variant chosen on the host, every step checked or
-// none, and a block small enough that its grid is resident at once -- the launch-latency-bound case
-static bool multi_ok(ocn_ctx *c, int32_t check_every)
-{
-    return c->multi && c->sw.use_tracers <= 0 && c->blocks.size() == 1 && !has_exchange(c) && !has_comm(c) &&
-           !c->ring_sea && c->compact &&
-           c->march && c->kc_mode != OCN_KC_DEVICE && (check_every == 0 || check_every == 1) &&
-           onepass_multi_fits(&c->blocks[0].g);
 }
 
 static int one_step_fused(ocn_ctx *c, double tau, const StepKind &k)
@@ -2077,372 +2043,224 @@ extern "C++" int ocn::finish_call(ocn_ctx *c, int rc)
     return rc;
 }
 
-// Lazy call tail possible: single process (a tail formed on one rank only would unbalance the
-// exchanges), no raw r8 pointers handed out, no tracers (expl_tracer reads hh_init's arrays after
-// every step), and the one-pass step as one launch per block (no exchange, no a8 / a9 work on the
-// halo ring: the redone step must find the previous state intact).
-static bool lazy_allowed(const ocn_ctx *c, bool x2)
+// The planner's snapshot of the context (ocn_step_plan.h StepFacts): taken once per call, where the call's
+// launches are planned -- behind prepare_static and a tail (complete_open), which change what it holds
+static StepFacts step_facts(const ocn_ctx *c)
 {
-    return c->lazy && !has_comm(c) && !c->r8_handed && (c->sw.use_tracers <= 0 || c->tr_step) &&
-           (x2 || (!c->ring_sea && !has_exchange(c)));
-}
-
-// one_step_x2's static conditions on this rank (the device checks come from check_coherence):
-// halo exchanges to do, the compact tables with the ext rows, no a8 / a9 work on a ring no neighbour
-// fills, every block of the grid at least 2 x 2 (its 2-deep strips lie in its interior)
-static bool x2_local(const ocn_ctx *c)
-{
-    if (!c->x2 || !c->compact || !c->rows_x_ok || c->edge_ring_sea || !has_exchange(c))
-        return false;
+    StepFacts f{};
+    f.onepass = c->onepass; f.lazy = c->lazy; f.multi = c->multi; f.x2 = c->x2; f.flip = c->flip;
+    f.recompute = c->recompute; f.known_const = c->known_const; f.last_hybrid = c->last_hybrid;
+    f.use_graph = c->use_graph; f.stage_timing = c->stage_timing; f.tr_step = c->tr_step;
+    f.compact = c->compact; f.march = c->march; f.fused = c->fused; f.forced = c->forced;
+    f.pair = c->pair; f.x4 = c->x4;
+    f.full_free_surface = c->sw.full_free_surface; f.trans_terms = c->sw.trans_terms;
+    f.ksw_lat = c->sw.ksw_lat; f.use_tracers = c->sw.use_tracers;
+    f.nblocks = (int)c->blocks.size();
+    f.has_exchange = has_exchange(c); f.has_comm = has_comm(c); f.remote_peers = f.has_comm && c->dec.nranks > 1;
+    f.ring_sea = c->ring_sea; f.edge_ring_sea = c->edge_ring_sea; f.rows_x_ok = c->rows_x_ok; f.x4_tab_ok = c->x4_tab_ok;
+    f.min_extent = INT32_MAX;
     for (const GBlock &g : c->gblocks)
-        if (g.rank >= 0 && (g.g.nx_end - g.g.nx_start < 1 || g.g.ny_end - g.g.ny_start < 1)) return false;
-    return true;
-}
-
-// one_step_x4's static conditions on this rank (with x2_local's): its tables, no tracers (expl_tracer
-// after every step), the known-constant variant allowed, every block of the grid at least 4 x 4 (its
-// 4-deep strips lie in its interior) and row padding for the extra rings
-static bool x4_local(const ocn_ctx *c)
-{
-    // (tracer runs: with the tracer steps, one_step_x4 runs them -- by default only where exchanges go to
-    // other ranks: a pair's second tracer step is one more launch after it, which with only local copies
-    // costs more than the exchange it saves -- C5 layout on one GPU 0.0281 (x2) vs 0.0338 ms per step,
-    // profiles/r06a; over RCCL each exchange is a group's latency)
-    if (!c->x4 || !c->x4_tab_ok || !c->known_const || c->r8_handed || (c->sw.use_tracers > 0 && !c->tr_step) ||
-        !c->march)
-        return false;
-    if (c->sw.use_tracers > 0 && c->x4 < 3 && !(has_comm(c) && c->dec.nranks > 1)) return false;
-    for (const GBlock &g : c->gblocks)
-        if (g.rank >= 0 && (g.g.nx_end - g.g.nx_start < 3 || g.g.ny_end - g.g.ny_start < 3)) return false;
+        if (g.rank >= 0) f.min_extent = std::min({f.min_extent, g.g.nx_end - g.g.nx_start, g.g.ny_end - g.g.ny_start});
+    f.x4_pitch_ok = true;
     for (const LBlock &b : c->blocks)
-        if (b.g.pitch < (int64_t)(b.g.bnd_x2 - b.g.bnd_x1 + 1 + 2 * kXRing)) return false;
-    return true;
+        if (b.g.pitch < (int64_t)(b.g.bnd_x2 - b.g.bnd_x1 + 1 + 2 * kXRing)) f.x4_pitch_ok = false;
+    if (f.nblocks == 1) {
+        const ocn_block &g = c->blocks[0].g;
+        f.cells0 = (long)(g.nx_end - g.nx_start + 1) * (g.ny_end - g.ny_start + 1);
+        if (c->multi_fits < 0) c->multi_fits = onepass_multi_fits(&g);   // (asked once: 1-step calls are host-bound)
+        f.multi_fits = c->multi_fits > 0;
+    }
+    f.r8_handed = c->r8_handed; f.reuse_allowed = reuse_allowed(c); f.hh_consistent = c->hh_consistent;
+    f.udiv_ok = c->udiv_ok; f.ring2_saved = c->ring2_saved;
+    return f;
 }
-// pairs of x2 steps in this call (after prepare_kc): x4_local on every rank (the vote) or this one
-// (one process), the known-constant variant chosen on the host
-static bool x4_now(const ocn_ctx *c)
-{
-    return (c->kc_mode == OCN_KC_KNOWN || c->kc_mode == OCN_KC_KNOWN_HR) &&
-           (has_comm(c) ? c->x4_dev_ok : x4_local(c) && c->fb_x2);
-}
+// what prepare_kc and the last vote left for the planner
+static Kc kc_state(const ocn_ctx *c) { return Kc{c->kc_mode, c->x4_dev_ok, c->fb_x2}; }
 
-// The first call of a sequence long enough for pairs, right after prepare_kc issued the known-
-// constant check: wait for the check's verdict (one host wait per check -- the check's pass over
-// the fields and a 4-byte copy, behind whatever the stream holds) so that the call's steps run as
-// pairs of the host-chosen variant instead of single launches of both variants with the device
-// picking (4096^2: 0.39 ms per single step against 0.28-0.30 ms per step in pairs; the single
-// steps' HBM traffic also pulls the shader clock down, 2.25 -> 1.55 GHz over 5 ms, and the pairs'
-// clock climbs back over ~30 ms: profiles/r06/clock_*.txt).  Not while a graph is captured (no
-// host wait there), not with a communicator (the ranks' votes carry the verdicts), not for calls
-// of 1-3 steps (no pair before their deferred last steps).
-static int await_kc(ocn_ctx *c, bool x2, int nsteps)
+// The first call of a sequence long enough for pairs, right after prepare_kc issued the known-constant
+// check: wait for its verdict where the call would then run pairs (ocn_step_plan.h await_kc_pays).  Not
+// while a graph is captured (no host wait there).
+static int await_kc(ocn_ctx *c, const StepFacts &f, bool x2, int nsteps)
 {
-    if (c->kc_mode != OCN_KC_DEVICE || !c->fb_copy || c->capturing || has_comm(c) || nsteps < 4) return OCN_OK;
-    c->kc_mode = OCN_KC_KNOWN;   // would the call run pairs with a host-chosen known-constant variant?
-    const bool pairs = x2 ? x4_now(c) : pair_ok(c);
-    c->kc_mode = OCN_KC_DEVICE;
-    if (!pairs) return OCN_OK;
+    if (!c->fb_copy || c->capturing || !await_kc_pays(f, kc_state(c), x2, nsteps)) return OCN_OK;
     HIPCHK(hipEventSynchronize(c->ev_fb));
     learn_fb_async(c);
     set_kc_mode(c, kc_of_fb(c));
     return OCN_OK;
 }
 
-// The step kinds of an open sequence and of the tail that ends one (a call's first steps are set up
-// one by one in step_impl's main loop).
-// A continuing one-pass step: nothing around its launch, the next step is one too
-static StepKind continuing_step(bool check, bool x2)
-{
-    StepKind k{};
-    k.check = check;
-    k.flip = k.one = k.next_one = k.a_done = true;
-    k.x2 = x2;   // (an x2 sequence: one_step_x2, as a pair one_step_x4)
-    return k;
-}
-// two of them as one launch (one_step_pair, one_step_x4)
-static StepKind continuing_pair(bool check, bool check2, bool x2)
-{
-    StepKind k = continuing_step(check, x2);
-    k.pair = true;
-    k.check2 = check2;
-    return k;
-}
-// nsteps of them as one launch (one_step_multi), each checked if check
-static StepKind multi_step(bool check, int nsteps)
-{
-    StepKind k = continuing_step(check, false);
-    k.multi = nsteps;
-    return k;
-}
-// The call's last step after one-pass steps.  It ends a sequence of x2 steps: the saved second ring is
-// restored and the first exchanged before it (x2_end), here and nowhere else
-static StepKind last_step(ocn_ctx *c, bool check)
-{
-    StepKind k{};
-    k.last = k.one_last = true;
-    k.check = check;
-    k.x2_end = c->ring2_saved;
-    c->ring2_saved = false;
-    return k;
-}
-// a one-pass step and the last step as one launch (one_step_pair with LAST: one block, no exchange)
-static StepKind last_pair(bool check, bool check2)
-{
-    StepKind k{};
-    k.last = k.one_last = k.pair = true;
-    k.check = check;
-    k.check2 = check2;
-    return k;
-}
-
 // The pending tail of an open sequence: the last step run (a one-pass step) is run again from the
 // previous state -- untouched in the other buffer of each pair and the other sshp / ubrtrp / vbrtrp
 // buffers -- as the call's last step (one_step_last: the same new state bit for bit, plus vort,
 // the stresses, the RHS terms, a8's copies and hh_init with every level).  Its check_ssh_err
-// count was taken the first time.
+// count was taken the first time.  (The kinds: ocn_step_plan.h plan_tail.)
 extern "C++" int ocn::complete_open(ocn_ctx *c)
 {
     if (!c->open) return OCN_OK;
     c->open = false;
     HIPCHK(hipSetDevice(c->dec.device));
-    if (c->deferred) {   // steps not yet run: the last ones, from the current state
-        const int d = c->deferred;
-        c->deferred = 0;
-        c->open_pair = false;
-        if (d == 2 && pair_ok(c))   // both in one launch, the second as the last step (pair + LAST)
-            return finish_call(c, run_step(c, c->open_tau, last_pair(c->deferred_check[0], c->deferred_check[1])));
-        if (d == 2) {   // (x2 sequences with pairs of x2 steps: one_step_x4 deferred it)
-            const StepKind k1 = continuing_step(c->deferred_check[0], c->open_x2);
-            if (const int rc = run_step(c, c->open_tau, k1)) return finish_call(c, rc);
-        }
-        return finish_call(c, run_step(c, c->open_tau, last_step(c, c->deferred_check[d - 1])));
+    const StepFacts f = step_facts(c);
+    const TailPlan t = plan_tail(c->deferred, c->deferred_check, c->open_pair, c->open_x2, pair_ok(f, c->kc_mode),
+                                 f.ring2_saved);
+    c->deferred = 0;
+    c->open_pair = false;
+    if (t.swap_back) {
+        swap_roles(c);
+        swap_alt3(c);
+        c->tr_pending = false;   // (the tracer step of the state before the last step has run)
     }
-    swap_roles(c);
-    swap_alt3(c);
-    c->tr_pending = false;   // (the tracer step of the state before the last step has run)
-    if (c->open_pair) {   // the last launch was a pair (one flip, two steps): both again, from the state
-        c->open_pair = false;   // before it, the second as the last step (counted the first time: no checks)
-        if (pair_ok(c)) return finish_call(c, run_step(c, c->open_tau, last_pair(false, false)));
-        // (a pair of x2 steps: its first step again, one_step_x2)
-        if (const int rc = run_step(c, c->open_tau, continuing_step(false, c->open_x2))) return finish_call(c, rc);
-        c->tr_pending = false;   // (tracer runs: the pair ran the tracer step of that state too)
+    for (int i = 0; i + 1 < t.n; ++i) {
+        if (const int rc = run_step(c, c->open_tau, t.k[i])) return finish_call(c, rc);
+        if (t.swap_back) c->tr_pending = false;   // (tracer runs: the pair ran the tracer step of that state too)
     }
-    return finish_call(c, run_step(c, c->open_tau, last_step(c, false)));
+    c->ring2_saved = t.ring2_saved;
+    return finish_call(c, run_step(c, c->open_tau, t.k[t.n - 1]));
 }
 
-// step_impl's answer to ocn_ens_step_record's and ocn_ens_step_forced's probe (ens_probe): ens_pending = this call
-// would be planned as ONE multi-step launch -- the conditions of the open sequence's branch below in their order, the
-// variant's choice (prepare_kc) included -- with none of its steps run; ens_go = it would go on with the open
-// sequence at all, no deferred step ahead of its first one.  (Steps an earlier call deferred stay deferred:
-// the call itself runs them first.)
-static int probe_multi(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every)
+// one kind of a call: replayed as a captured graph or run; the pair launches' flags
+static int run_kind(ocn_ctx *c, double tau, const StepKind &k, bool graph)
 {
-    c->ens_pending = c->ens_go = false;
-    if (!c->open || tau != c->open_tau || !c->onepass || !lazy_allowed(c, c->open_x2)) return OCN_OK;
-    c->ens_go = c->deferred == 0;   // (the call's first step would be the open sequence's next one-pass step)
+    if (k.pair) {
+        c->pair_used = true;
+        if (!k.one_last) c->nv_used = c->kc_nv;   // (a pair whose second step is the call's last runs the full body)
+    }
+    return graph ? graph_step(c, tau, k) : run_step(c, tau, k);
+}
+
+// A call while a sequence is open: goes_on = false if the sequence ends here (the caller forms the tail).
+// Else the one-pass variant is prepared -- a device verdict the host has read since selects one -- and the
+// call is planned (ocn_step_plan.h plan_open), its kinds handed to emit: step_impl runs them, step_probe none.
+extern "C++" {
+template <class Emit>
+static int open_call(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every, bool &goes_on, OpenPlan &p, Emit &&emit)
+{
+    const StepFacts f = step_facts(c);
+    goes_on = open_goes_on(f, tau == c->open_tau, c->open_x2);
+    if (!goes_on) return OCN_OK;
     RC(prepare_kc(c, c->open_x2));
-    const bool graph_ok = c->use_graph && !has_comm(c) && !c->stage_timing && !(c->sw.use_tracers > 0 && c->tr_step);
-    const bool pairs = c->open_x2 ? x4_now(c) : pair_ok(c);
-    c->ens_pending = !pairs && !c->open_x2 && !graph_ok && nsteps >= 2 && multi_ok(c, check_every);
+    p = plan_open(f, kc_state(c), c->open_x2, c->deferred, c->deferred_check, nsteps, check_every, emit);
     return OCN_OK;
 }
+}
 
-static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every)
+// collect (inside ocn_ens_step): a multi-step launch is planned as ever but left to the ensemble, which
+// issues it with the other members' (ens_pending, ens_k)
+static int step_impl(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every, bool collect)
 {
     HIPCHK(hipSetDevice(c->dec.device));
     if (nsteps < 0) return set_error(OCN_ERR_ARG, "nsteps < 0");
     if (nsteps == 0) return OCN_OK;
-    if (c->ens_probe) return probe_multi(c, tau, nsteps, check_every);
-    // (RCCL / events stay outside graphs; so do the tracer steps' calls: their launches follow pending state)
-    const bool graph_ok = c->use_graph && !has_comm(c) && !c->stage_timing && !(c->sw.use_tracers > 0 && c->tr_step);
     c->pair_used = c->nv_used = false;
     c->co_used = false;
     c->multi_used = false;
     if (c->open) {
-        if (tau == c->open_tau && c->onepass && lazy_allowed(c, c->open_x2)) {
-            // the open sequence goes on: every step of this call is a one-pass step (the state and
-            // the constants are what its last step left), and the tail stays pending; a device
-            // verdict the host has read since selects one variant
-            RC(prepare_kc(c, c->open_x2));
-            // (x2 sequences: pairs of x2 steps, one_step_x4)
-            const bool pairs = c->open_x2 ? x4_now(c) : pair_ok(c);
-            c->x4_used = c->open_x2 && pairs;
-            int rc = OCN_OK;
-            if (pairs) {   // two steps per launch -- the steps deferred by the last call first -- while
-                           // 3 or more are pending; the last 1 or 2 deferred (next call, complete_open)
-                std::vector<char> chk(c->deferred_check, c->deferred_check + c->deferred);
-                for (int s = 1; s <= nsteps; ++s) chk.push_back(check_every > 0 && (s % check_every == 0));
-                c->deferred = 0;
-                size_t i = 0;
-                for (; i + 2 < chk.size() && rc == OCN_OK; i += 2) {
-                    const StepKind k = continuing_pair(chk[i], chk[i + 1], c->open_x2);
-                    rc = graph_ok ? graph_step(c, tau, k) : run_step(c, tau, k);
-                    c->open_pair = c->pair_used = true;
-                    if (!k.one_last) c->nv_used = c->kc_nv;   // (a pair whose second step is the call's last runs the full body)
-                }
-                if (rc == OCN_OK) {
-                    c->deferred = (int)(chk.size() - i);   // 1 or 2
-                    for (int j = 0; j < c->deferred; ++j) c->deferred_check[j] = chk[i + j];
-                }
-            } else {
-                for (int j = 0; j < c->deferred && rc == OCN_OK; ++j)   // (no pairs now: deferred steps first)
-                    rc = run_step(c, tau, continuing_step(c->deferred_check[j], c->open_x2));
-                c->deferred = 0;
-                if (!c->open_x2 && !graph_ok && nsteps >= 2 && rc == OCN_OK && multi_ok(c, check_every)) {
-                    const StepKind k = multi_step(check_every == 1, nsteps);   // all the call's steps in one launch
-                    // (inside ocn_ens_step: planned here, issued with the other members' launches)
-                    if (c->ens_collect) { c->ens_k = k; c->ens_pending = true; }
-                    else rc = run_step(c, tau, k);
-                    c->open_pair = false;
-                    c->multi_used = true;
-                } else {
-                    for (int s = 1; s <= nsteps && rc == OCN_OK; ++s) {
-                        const StepKind k = continuing_step(check_every > 0 && (s % check_every == 0), c->open_x2);
-                        rc = graph_ok ? graph_step(c, tau, k) : run_step(c, tau, k);
-                        c->open_pair = false;
-                    }
-                }
-            }
+        bool goes_on = false;
+        OpenPlan p{};
+        int rc = OCN_OK;
+        RC(open_call(c, tau, nsteps, check_every, goes_on, p, [&](const StepKind &k, bool graph) {
+            if (k.multi) c->multi_used = true;
+            if (k.multi && collect) { c->ens_k = k; c->ens_pending = true; }
+            else rc = run_kind(c, tau, k, graph);
+            c->open_pair = k.pair;
+            return rc == OCN_OK;
+        }));
+        if (goes_on) {
+            c->x4_used = c->open_x2 && p.mode == kOpenPairs;   // (x2 sequences: pairs of x2 steps, one_step_x4)
             if (rc) { c->open = false; c->deferred = 0; c->open_pair = false; return finish_call(c, rc); }
+            c->deferred = p.deferred;   // (pairs: the last 1 or 2 steps wait for the next call or the tail)
+            c->deferred_check[0] = p.deferred_check[0];
+            c->deferred_check[1] = p.deferred_check[1];
             return OCN_OK;
         }
         RC(complete_open(c));
     }
     RC(prepare_static(c));   // (the stage path reads the compact tables too)
+    const StepFacts f = step_facts(c);
     // with RCCL every rank takes part in the decisions (check_coherence reduces the verdicts)
-    const bool eligible = flip_eligible(c);
-    const bool x2_here = x2_local(c);
-    // one_step_x4 possible on this rank: its static conditions and a known-constant verdict for the x2
-    // range its host has read (the variant the pairs run; kFbZero stays put through prepare_kc(x2))
-    const bool x4_here = x2_here && x4_local(c) && (c->fb_state == kFbZero || c->fb_state == kFbHr) && c->fb_x2;
-    // a lazy call is planned as the first nsteps steps of a call of nsteps + 1 (the last deferred)
-    const bool lazy_cand = eligible && c->onepass && lazy_allowed(c, x2_here);
-    bool udiv_ok = c->udiv_ok, first_one = c->hh_consistent, x2_ok = x2_here && c->x2_dev_ok;
-    int N = lazy_cand ? nsteps + 1 : nsteps;
-    if (N >= 2 && (eligible || (has_comm(c) && c->flip)) && !c->coherent_known) {
-        VoteOut v;
-        RC(check_coherence(c, VoteIn{eligible, c->udiv_ok, c->hh_consistent, x2_here, x4_here, nv_local(c)}, v));
-        udiv_ok = v.udiv_ok;
-        first_one = v.hh_consistent;
-        x2_ok = x2_here && v.x2_ok;
+    const bool x2_here = x2_local(f);
+    Vote v{c->coherent, f.udiv_ok, f.hh_consistent, x2_here && c->x2_dev_ok};
+    if (fresh_votes(f, nsteps, c->coherent_known)) {
+        // one_step_x4 possible on this rank: its static conditions and a known-constant verdict for the x2
+        // range its host has read (the variant the pairs run; kFbZero stays put through prepare_kc(x2))
+        const bool x4_here = x2_here && x4_local(f) && (c->fb_state == kFbZero || c->fb_state == kFbHr) && c->fb_x2;
+        VoteOut o;
+        RC(check_coherence(c, VoteIn{flip_eligible(f), f.udiv_ok, f.hh_consistent, x2_here, x4_here, nv_local(c)}, o));
+        v = Vote{c->coherent, o.udiv_ok, o.hh_consistent, x2_here && o.x2_ok};
     }
-    bool flip_call = false, ca = false, one_call = false;
-    // tracer runs with one-pass steps (tracer steps): the call's first step a one-pass step too, and
-    // with exchanges the x2 steps (their exchange carries the tracers); one block: no ring work
-    // and the last step a one-pass step (last_one below: it runs the pending tracer step)
-    const bool tr_ok = c->sw.use_tracers <= 0 ||
-                       (c->tr_step && first_one &&
-                        (has_exchange(c) ? x2_ok && c->last_hybrid
-                                         : !c->ring_sea && (c->last_hybrid || (c->blocks.size() == 1 && !has_comm(c)))));
-    auto decide = [&](int n) {
-        flip_call = n >= 2 && eligible && c->coherent && (c->sw.full_free_surface != 1 || reuse_allowed(c));
-        // role-flip calls with full_free_surface = 1 fuse each step's hh_init with the next step's A;
-        // their reuse steps recompute hhq / hhu_p / hhv_p in fused B, which then filters sshp into
-        // the second buffer (the ring launch completes it on the halo ring)
-        ca = flip_call && c->sw.full_free_surface == 1;
-        // one-pass steps 2..K-1 (all SW terms on, no tracers: expl_tracer reads hh_init's hhu / hhv /
-        // hhq_p, which a one-pass step keeps in registers; row divisors in udiv's range) -- the first
-        // step too when hh_init's stored depths match the state (hh_consistent)
-        one_call = ca && c->onepass && (n >= 3 || (n >= 2 && first_one)) && c->sw.trans_terms > 0 &&
-                   c->sw.ksw_lat > 0 && tr_ok && udiv_ok;
-    };
-    decide(N);
-    // one-pass steps with one 2-deep exchange each (one_step_x2) where there are exchanges
-    const bool x2_call = one_call && x2_ok && c->last_hybrid;   // (its sequences end in the hybrid last step)
-    // the last step run is a one-pass step (one launch per block, or an x2 step): the tail may wait
-    const bool lazy_end = lazy_cand && one_call && (nsteps >= 2 || first_one) &&
-                          (x2_call || (!c->ring_sea && !has_exchange(c)));
-    if (!lazy_end && N != nsteps) decide(N = nsteps);
-    c->x2_used = x2_call && one_call;
-    c->flip_used = flip_call;
-    c->tr_call = c->sw.use_tracers > 0 && one_call;
+    FreshPlan p = plan_fresh(f, v, nsteps);
+    c->x2_used = p.x2_call;
+    c->flip_used = p.flip_call;
+    c->tr_call = c->sw.use_tracers > 0 && p.one_call;
     c->tr_pending = false;
     if (c->tr_call && !c->tr_alt_ok) {   // the second ff1p buffers start as copies
         RC(copy_to_alt(c, 0, true));
         c->tr_alt_ok = true;
     }
     c->hh_consistent = false;   // until this call's last step has run
-    // the last step as one march + hh_init too (single block, no exchange, no ring work)
-    // (with exchanges or ring work: the hybrid last step, OCN_OPT_ONEPASS_LAST)
-    const bool last_one = one_call && ((c->blocks.size() == 1 && !has_exchange(c) && !has_comm(c) && !c->ring_sea) ||
-                                       c->last_hybrid);
-    c->one_used = one_call;
-    if (x2_call && one_call) {
+    c->one_used = p.one_call;
+    if (p.x2_call) {
         if (!c->hrx_ok || has_comm(c)) RC(refresh_hrx(c));   // (with RCCL: every rank, every call)
         RC(prebuild_x2(c));
     }
-    if (one_call) {
-        RC(prepare_kc(c, x2_call));
-        RC(await_kc(c, x2_call, nsteps));
+    if (p.one_call) {
+        RC(prepare_kc(c, p.x2_call));
+        RC(await_kc(c, f, p.x2_call, nsteps));
     }
-    const bool rc_call = ca && c->recompute && !one_call;
-    if (rc_call) c->alt_ok = false;
-    if (one_call && !c->alt_ok) {   // the second buffers start as copies (they agree outside a8's write set)
+    if (p.rc_call) c->alt_ok = false;
+    if (p.one_call && !c->alt_ok) {   // the second buffers start as copies (they agree outside a8's write set)
         RC(copy_to_alt(c, 3, false));
         c->alt_ok = true;
     }
-    c->rc_used = rc_call && N >= 3;
-    if (rc_call) RC(copy_to_alt(c, 1, false));   // the second sshp buffer starts as a copy: the two agree outside a8's write set
+    c->rc_used = p.rc_call && p.N >= 3;
+    if (p.rc_call) RC(copy_to_alt(c, 1, false));   // the second sshp buffer starts as a copy: the two agree outside a8's write set
     RC(join_sync(c));
-    // two one-pass steps per launch where both are plain one-pass steps and the second is not the
-    // last one run (a lazy tail redoes that one from the state before it, which a pair never writes)
-    // (with exchanges: pairs of x2 steps with one 4-deep exchange each, one_step_x4)
-    const bool x4_call = one_call && x2_call && x4_now(c);
-    c->x4_used = x4_call;
-    const bool pairs = one_call && (x2_call ? x4_call : pair_ok(c));
-    auto plain_one = [&](int s) {   // step s is a one-pass step that needs nothing around its launch
-        const bool one = one_call && (s >= 2 || first_one) && s <= N - 1, next_one = one_call && s + 1 <= N - 1;
-        const bool next_a = ca && flip_call && s != N && !next_one && !(last_one && s + 1 == N);
-        return one && !next_a && !(last_one && s == N);
-    };
+    p = fresh_pairs(f, p, kc_state(c));
+    c->x4_used = p.x4_call;
     int rc = OCN_OK;
-    for (int s = 1; s <= nsteps && rc == OCN_OK; ++s) {
-        StepKind k;
-        k.check = check_every > 0 && (s % check_every == 0);
-        k.first = s == 1;
-        k.last = s == N;
-        k.flip = flip_call && !k.last;
-        k.one = one_call && (s >= 2 || first_one) && s <= N - 1;
-        k.next_one = one_call && s + 1 <= N - 1;
-        k.one_last = last_one && k.last;
-        k.a_done = ca && !k.first;
-        k.next_a = ca && k.flip && !k.next_one && !(last_one && s + 1 == N);
-        k.next_reuse = k.next_a && s + 1 < N;
-        k.rc = rc_call && k.flip && !k.first;
-        k.rc_next = rc_call && s + 1 < N;
-        k.x2 = x2_call && k.one;
-        k.x2_save = k.x2 && !c->ring2_saved;
-        k.x2_end = k.one_last && c->ring2_saved;
-        if (k.x2_save) c->ring2_saved = true;
-        if (k.x2_end) c->ring2_saved = false;
-        if (pairs && k.one && s + 1 < nsteps && plain_one(s + 1)) {
-            k.pair = true;
-            k.check2 = check_every > 0 && ((s + 1) % check_every == 0);
-            k.next_one = one_call && s + 2 <= N - 1;
-            k.next_a = k.next_reuse = false;
-            ++s;
-            c->pair_used = true;
-            if (!k.one_last) c->nv_used = c->kc_nv;   // (launch_onepass_pair: the full body with last)
-        }
-        rc = graph_ok ? graph_step(c, tau, k) : run_step(c, tau, k);
+    for (int s = 1; s <= nsteps && rc == OCN_OK;) {
+        const FreshStep st = fresh_step(p, s, check_every, c->ring2_saved);
+        c->ring2_saved = st.ring2_saved;
+        s += st.steps;
+        rc = run_kind(c, tau, st.k, p.graph);
     }
-    if (lazy_end && rc == OCN_OK) {   // the pending tail: complete_open
+    if (p.lazy_end && rc == OCN_OK) {   // the pending tail: complete_open
         c->open = true;
         c->open_pair = false;   // (the call's last step ran single)
         c->deferred = 0;
         c->open_tau = tau;
-        c->open_x2 = x2_call;
+        c->open_x2 = p.x2_call;
         return OCN_OK;
     }
     return finish_call(c, rc);
 }
 
-// ocn_ctx_step's call (ocn_ens_step makes it for every member, under its own name)
-extern "C++" int ocn::step_entry(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every)
+// ocn_ctx_step's call (ocn_ens_step makes it for every member, under its own name, with collect)
+extern "C++" int ocn::step_entry(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every, bool collect)
 {
     // (a usage error before any collective: no peer waits on this rank yet, the communicator stays)
     if (!c->initialized) return set_error(OCN_ERR_STATE, "ocn_ctx_init_state not called");
-    return fail_fatal(c, step_impl(c, tau, nsteps, check_every));
+    return fail_fatal(c, step_impl(c, tau, nsteps, check_every, collect));
+}
+
+// ocn_ens_step_record's and ocn_ens_step_forced's question before any step runs: multi = this call would be
+// planned as ONE multi-step launch, the variant's choice (prepare_kc) included; go = it would go on with the open
+// sequence at all, no deferred step ahead of its first one.  None of its steps is run.  (Steps an earlier
+// call deferred stay deferred: the call itself runs them first.)
+extern "C++" int ocn::step_probe(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every, bool *multi, bool *go)
+{
+    *multi = *go = false;
+    if (!c->initialized) return set_error(OCN_ERR_STATE, "ocn_ctx_init_state not called");
+    return fail_fatal(c, [&]() -> int {
+        HIPCHK(hipSetDevice(c->dec.device));
+        if (nsteps < 0) return set_error(OCN_ERR_ARG, "nsteps < 0");
+        if (nsteps == 0 || !c->open) return OCN_OK;
+        bool goes_on = false;
+        OpenPlan p{};
+        RC(open_call(c, tau, nsteps, check_every, goes_on, p, [](const StepKind &, bool) { return true; }));
+        *multi = goes_on && p.mode == kOpenMulti;
+        *go = goes_on && p.go;
+        return OCN_OK;
+    }());
 }
 
 int ocn_ctx_step(ocn_ctx *c, double tau, int32_t nsteps, int32_t check_every)

@@ -200,7 +200,7 @@ namespace ocn {
 std::vector<ocn_ctx *> ens_in_use(const ocn_ens *e, const uint8_t *use);
 int64_t ens_capacity(const ocn_ens *e);
 int ens_groups(const ocn_ens *e, const std::vector<int32_t> &variant, int64_t capacity, std::vector<ocn_ens_group> &groups);
-int32_t ens_variant(const ocn_ctx *c, double tau, bool check);
+int32_t ens_variant(const ocn_ctx *c, double tau, bool check, bool multi);
 // A recording call's part in ocn_ens_step's launches (ocn_ens_step_record's in-launch path): the capacity
 // in effect, the members' columns (-1: not in use), the first due step and its slot
 struct EnsRecCall { int64_t capacity; std::vector<int> col; int due0; double *slot0; };

@@ -78,11 +78,11 @@ int ens_groups(const ocn_ens *e, const std::vector<int32_t> &variant, int64_t ca
     return first;
 }
 
-// the variant of a member whose call is planned as a multi-step launch (ens_pending), or -1: the launch takes
+// the variant of a member whose call is planned as a multi-step launch (multi), or -1: the launch takes
 // the library's fused path with the sw switches it needs; else the member's own launch
-int32_t ens_variant(const ocn_ctx *c, double tau, bool check)
+int32_t ens_variant(const ocn_ctx *c, double tau, bool check, bool multi)
 {
-    if (c->ens_pending && c->fused && c->sw.full_free_surface == 1 && c->sw.trans_terms > 0 && c->sw.ksw_lat > 0)
+    if (multi && c->fused && c->sw.full_free_surface == 1 && c->sw.trans_terms > 0 && c->sw.ksw_lat > 0)
         return onepass_multi_variant(c->kc_mode, tau, check);
     return -1;
 }
@@ -100,10 +100,8 @@ int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, co
     for (int i = 0; i < M; ++i) {
         ocn_ctx *c = e->m[(size_t)i];
         c->ens_pending = false;
-        c->ens_collect = true;
-        note(guarded(c, "ocn_ens_step", [&] { return step_entry(c, tau, nsteps, check_every); }));
-        c->ens_collect = false;
-        variant[(size_t)i] = ens_variant(c, tau, c->ens_k.check);
+        note(guarded(c, "ocn_ens_step", [&] { return step_entry(c, tau, nsteps, check_every, true); }));
+        variant[(size_t)i] = ens_variant(c, tau, c->ens_k.check, c->ens_pending);
     }
     HIPCHK(hipSetDevice(e->device));
     e->last.capacity = rec ? rec->capacity : frc ? frc->capacity : ens_capacity(e);

@@ -104,7 +104,7 @@ static int frc_apply(ocn_ens *e, double t, const char *who, const std::vector<ch
     return rc;
 }
 
-// every member's answer to the probe of a call of nsteps steps (step_impl: ens_probe): its variant if it would
+// every member's answer to the probe of a call of nsteps steps (step_probe): its variant if it would
 // plan ONE multi-step launch (else -1), and whether it would go on with its open sequence at all; forced_only:
 // the others are not asked
 static void frc_probe(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, bool forced_only,
@@ -116,14 +116,11 @@ static void frc_probe(ocn_ens *e, double tau, int32_t nsteps, int32_t check_ever
     for (size_t i = 0; i < M; ++i) {
         ocn_ctx *c = e->m[i];
         if (forced_only && !e->frc.forced[i]) continue;
-        c->ens_probe = true;
-        const int rc = guarded(c, "ocn_ens_step_forced", [&] { return step_entry(c, tau, nsteps, check_every); });
-        c->ens_probe = false;
-        if (!rc) {
-            variant[i] = ens_variant(c, tau, check_every == 1);
-            go[i] = c->ens_go ? 1 : 0;
+        bool multi = false, goes = false;
+        if (!guarded(c, "ocn_ens_step_forced", [&] { return step_probe(c, tau, nsteps, check_every, &multi, &goes); })) {
+            variant[i] = ens_variant(c, tau, check_every == 1, multi);
+            go[i] = goes ? 1 : 0;
         }
-        c->ens_pending = c->ens_go = false;
     }
 }
 

@@ -195,7 +195,7 @@ int ocn_ens_step_record(ocn_ens *e, double tau, int32_t nsteps, int32_t check_ev
 
     // In the launch only if every member in use would go in a recording launch -- known before any step of
     // the call runs (a member that has stepped without its records cannot be repaired): each member says
-    // whether it would plan a multi-step launch (step_impl's probe), the planner whether it lands in a group
+    // whether it would plan a multi-step launch (step_probe), the planner whether it lands in a group
     // under the recording capacity.  The call itself then plans the same way.
     EnsRecCall rc_call{std::min<int64_t>(ens_capacity(e), onepass_multi_rec_capacity()), std::vector<int>((size_t)M, -1), 0, nullptr};
     bool in_launch = e->rec_in_launch && nsteps >= 2 && e->m[0]->blocks.size() == 1;
@@ -203,11 +203,9 @@ int ocn_ens_step_record(ocn_ens *e, double tau, int32_t nsteps, int32_t check_ev
         std::vector<int32_t> variant((size_t)M, -1);
         for (int i = 0; i < M; ++i) {
             ocn_ctx *c = e->m[(size_t)i];
-            c->ens_probe = true;
-            const int rc = guarded(c, "ocn_ens_step_record", [&] { return step_entry(c, tau, nsteps, check_every); });
-            c->ens_probe = false;
-            if (!rc) variant[(size_t)i] = ens_variant(c, tau, check_every == 1);
-            c->ens_pending = false;
+            bool multi = false, go = false;
+            if (!guarded(c, "ocn_ens_step_record", [&] { return step_probe(c, tau, nsteps, check_every, &multi, &go); }))
+                variant[(size_t)i] = ens_variant(c, tau, check_every == 1, multi);
         }
         std::vector<ocn_ens_group> groups;
         if (ens_groups(e, variant, rc_call.capacity, groups)) in_launch = false;

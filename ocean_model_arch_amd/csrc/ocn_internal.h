@@ -141,7 +141,10 @@ int launch_fill_field(const ocn_block &g, double *p, double v, hipStream_t s);
 // word after it, flag[1]: nonzero if mu's one value is not +0.0 (read by the host only).
 // nv (OCN_KC_KNOWN / OCN_KC_KNOWN_HR chosen on the host): mu is +0.0 and every r_diss row +0.0f -- the
 // two-step launches run their inviscid bodies (MarchStep NV: no viscous or friction terms formed)
+#ifndef OCN_KC_DEFINED   // also in ocn_step_plan.h
+#define OCN_KC_DEFINED
 enum { OCN_KC_GENERAL = 0, OCN_KC_KNOWN = 1, OCN_KC_DEVICE = 2, OCN_KC_KNOWN_HR = 3 };
+#endif
 struct OnepassKC { int mode; const int32_t *flag; const double *kc; bool nv = false; };
 // own (sw_stencils.h own_class bits, not with last): the halo points neighbour blocks own hold the
 // neighbours' state two points deep -- D there is formed as on their interior (MarchStep X2).
