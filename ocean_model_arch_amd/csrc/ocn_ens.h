@@ -201,15 +201,22 @@ std::vector<ocn_ctx *> ens_in_use(const ocn_ens *e, const uint8_t *use);
 int64_t ens_capacity(const ocn_ens *e);
 int ens_groups(const ocn_ens *e, const std::vector<int32_t> &variant, int64_t capacity, std::vector<ocn_ens_group> &groups);
 int32_t ens_variant(const ocn_ctx *c, double tau, bool check, bool multi);
-// A recording call's part in ocn_ens_step's launches (ocn_ens_step_record's in-launch path): the capacity
-// in effect, the members' columns (-1: not in use), the first due step and its slot
-struct EnsRecCall { int64_t capacity; std::vector<int> col; int due0; double *slot0; };
-// A forced call's part in them (ocn_ens_step_forced's in-launch path): the capacity in effect and the time of the
-// call's first step.  The groups that hold a forced member go as forcing launches; the forcing of t0 is written
-// behind the call's planning, ahead of the launches, and the last step's comes home behind them
-struct EnsFrcCall { int64_t capacity; double t0; };
-int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsRecCall *rec,
-                 const EnsFrcCall *frc = nullptr);
+// Every asked member's answer to the probe of a call of nsteps steps (step_probe; who: the entry, for guarded's
+// message): variant[i], its variant if it would plan ONE multi-step launch (else -1), and go[i], whether it would
+// go on with its open sequence at all.  only (null: everyone): the members that are asked
+void ens_probe(ocn_ens *e, const char *who, double tau, int32_t nsteps, int32_t check_every, const uint8_t *only,
+               std::vector<int32_t> &variant, std::vector<char> &go);
+// one flag per member: it is in one of the groups
+std::vector<char> ens_grouped(const ocn_ens *e, const std::vector<ocn_ens_group> &groups);
+// What a call brings to ocn_ens_step's launches beyond the steps: the capacity in effect and ONE of
+//   rec (ocn_ens_step_record's in-launch path): the members' columns (-1: not in use), the first due step, its slot;
+//   frc (ocn_ens_step_forced's in-launch path): the time of the call's first step.  The groups that hold a forced
+//       member go as forcing launches; the forcing of t0 is written behind the call's planning, ahead of the
+//       launches, and the last step's comes home behind them
+struct EnsRecCall { std::vector<int> col; int due0; double *slot0; };
+struct EnsFrcCall { double t0; };
+struct EnsCall { int64_t capacity; const EnsRecCall *rec; const EnsFrcCall *frc; };
+int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsCall *call);
 void *ens_based_alloc(const LBlock &b, int32_t field, size_t bytes, void **raw);
 
 // The tail the three synchronous sampling entries share, in e->samp, reserved by the entry for up_b + res_b and

@@ -87,9 +87,36 @@ int32_t ens_variant(const ocn_ctx *c, double tau, bool check, bool multi)
     return -1;
 }
 
-// ocn_ens_step; with `rec` the same call with the recorder in its launches, with `frc` with the forcing in them
-int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsRecCall *rec, const EnsFrcCall *frc)
+void ens_probe(ocn_ens *e, const char *who, double tau, int32_t nsteps, int32_t check_every, const uint8_t *only,
+               std::vector<int32_t> &variant, std::vector<char> &go)
 {
+    const size_t M = e->m.size();
+    variant.assign(M, -1);
+    go.assign(M, 0);
+    for (size_t i = 0; i < M; ++i) {
+        ocn_ctx *c = e->m[i];
+        if (only && !only[i]) continue;
+        bool multi = false, goes = false;
+        if (!guarded(c, who, [&] { return step_probe(c, tau, nsteps, check_every, &multi, &goes); })) {
+            variant[i] = ens_variant(c, tau, check_every == 1, multi);
+            go[i] = goes ? 1 : 0;
+        }
+    }
+}
+
+std::vector<char> ens_grouped(const ocn_ens *e, const std::vector<ocn_ens_group> &groups)
+{
+    std::vector<char> grouped(e->m.size(), 0);
+    for (const ocn_ens_group &q : groups)
+        for (int j = 0; j < q.members; ++j) grouped[(size_t)q.member[j]] = 1;
+    return grouped;
+}
+
+// ocn_ens_step; with `call` the same call with the recorder (call->rec) or the forcing (call->frc) in its launches
+int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsCall *call)
+{
+    const EnsRecCall *const rec = call ? call->rec : nullptr;
+    const EnsFrcCall *const frc = call ? call->frc : nullptr;
     const int M = (int)e->m.size();
     e->last = ocn_ens_info_t{};
     e->last.members = M;
@@ -104,16 +131,14 @@ int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, co
         variant[(size_t)i] = ens_variant(c, tau, c->ens_k.check, c->ens_pending);
     }
     HIPCHK(hipSetDevice(e->device));
-    e->last.capacity = rec ? rec->capacity : frc ? frc->capacity : ens_capacity(e);
+    e->last.capacity = call ? call->capacity : ens_capacity(e);
     std::vector<ocn_ens_group> groups;
     note(ens_groups(e, variant, e->last.capacity, groups));
     std::vector<char> done((size_t)M, 0);
     if (frc) {
         // every forced member must be in a launch, as ocn_ens_step_forced's probe found it: one that planned
         // otherwise has run its steps already, all under one forcing -- an error, never a silent result
-        std::vector<char> grouped((size_t)M, 0);
-        for (const ocn_ens_group &q : groups)
-            for (int j = 0; j < q.members; ++j) grouped[(size_t)q.member[j]] = 1;
+        const std::vector<char> grouped = ens_grouped(e, groups);
         for (int i = 0; i < M; ++i)
             if (e->frc.forced[(size_t)i] && !grouped[(size_t)i])
                 note(set_error(OCN_ERR_STATE, "ens_step_forced: member " + std::to_string(i) + " planned its call otherwise than its probe"));
@@ -143,14 +168,12 @@ int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, co
                                           {(double *)b.sshp_alt, (double *)b.up_alt, (double *)b.vp_alt},
                                           e->d_bar + (size_t)q.member[j] * (kMultiBarBytes / sizeof(unsigned)),
                                           c->d_nbad + 61, kc.kc, c->multi_spin};
+                if (frc) ms[(size_t)j].index = q.member[j];
                 if (frc && e->frc.forced[(size_t)q.member[j]]) {
                     const ocn_ens::Forcing::Second &sec = e->frc.second[(size_t)q.member[j]];
-                    ms[(size_t)j].index = q.member[j];
                     ms[(size_t)j].frc2[0] = sec.p[0];
                     ms[(size_t)j].frc2[1] = sec.p[1];
                     forcing = true;
-                } else if (frc) {
-                    ms[(size_t)j].index = q.member[j];
                 }
                 if (!c->fused) c->hn_fresh = false;
                 if (!rc) rc = timer_begin(c, OCN_TIMER_ONEPASS_MULTI, recs[(size_t)j]);
@@ -159,26 +182,20 @@ int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, co
             bool recording = false;
             for (int j = 0; j < q.members && rec && rec->due0 < nsteps; ++j)
                 if ((col[(size_t)j] = rec->col[(size_t)q.member[j]]) >= 0) recording = true;
+            const EnsLaunch L{ms.data(), q.members, q.variant, q.rows, e->m[(size_t)q.member[0]]->sw, tau, nsteps, e->tab.d,
+                              (char *)e->tab.h[sl] + off, eb * (size_t)q.members, (long)e->last.capacity};
+            EnsRecLaunch rl{};
+            EnsFrcLaunch fl{};
             if (!rc && recording) {   // (the call's stage: ens_rec_stage; its other copy's turn at the next call)
                 const ocn_ens::Recorder &r = e->rec;
                 const char *d = (const char *)r.d_op;
-                const EnsRecLaunch rl{col.data(), r.field.data(), (int)r.field.size(), (const int *)(d + r.start_at),
-                                      (const EnsObsTerm *)(d + r.lterm_at), rec->slot0, rec->due0, r.every, r.nobs, r.n,
-                                      (EnsRecMember *)r.stage.h[r.stage.slot] + rec_off, (EnsRecMember *)r.stage.d + rec_off};
+                rl = EnsRecLaunch{col.data(), r.field.data(), (int)r.field.size(), (const int *)(d + r.start_at),
+                                  (const EnsObsTerm *)(d + r.lterm_at), rec->slot0, rec->due0, r.every, r.nobs, r.n,
+                                  (EnsRecMember *)r.stage.h[r.stage.slot] + rec_off, (EnsRecMember *)r.stage.d + rec_off};
                 rec_off += (size_t)q.members;
-                rc = launch_onepass_multi_rec(ms.data(), q.members, q.variant, q.rows, e->m[(size_t)q.member[0]]->sw, tau,
-                                              nsteps, e->tab.d, (char *)e->tab.h[sl] + off, eb * (size_t)q.members,
-                                              (long)e->last.capacity, rl, e->stream);
-            } else if (!rc && forcing) {
-                const EnsFrcLaunch fl{(const EnsFrcMember *)e->frc.tab.d, e->frc.model, frc->t0};
-                rc = launch_onepass_multi_frc(ms.data(), q.members, q.variant, q.rows, e->m[(size_t)q.member[0]]->sw, tau,
-                                              nsteps, e->tab.d, (char *)e->tab.h[sl] + off, eb * (size_t)q.members,
-                                              (long)e->last.capacity, fl, e->stream);
-            } else if (!rc) {
-                rc = launch_onepass_multi_b(ms.data(), q.members, q.variant, q.rows, e->m[(size_t)q.member[0]]->sw, tau,
-                                            nsteps, e->tab.d, (char *)e->tab.h[sl] + off, eb * (size_t)q.members,
-                                            (long)e->last.capacity, e->stream);
             }
+            if (forcing) fl = EnsFrcLaunch{(const EnsFrcMember *)e->frc.tab.d, e->frc.model, frc->t0};
+            if (!rc) rc = launch_onepass_multi_ens(L, recording ? &rl : nullptr, forcing ? &fl : nullptr, e->stream);
             off += eb * (size_t)q.members;
             for (int j = 0; j < q.members; ++j) {
                 ocn_ctx *c = e->m[(size_t)q.member[j]];

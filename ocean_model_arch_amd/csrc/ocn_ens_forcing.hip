@@ -104,26 +104,6 @@ static int frc_apply(ocn_ens *e, double t, const char *who, const std::vector<ch
     return rc;
 }
 
-// every member's answer to the probe of a call of nsteps steps (step_probe): its variant if it would
-// plan ONE multi-step launch (else -1), and whether it would go on with its open sequence at all; forced_only:
-// the others are not asked
-static void frc_probe(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, bool forced_only,
-                      std::vector<int32_t> &variant, std::vector<char> &go)
-{
-    const size_t M = e->m.size();
-    variant.assign(M, -1);
-    go.assign(M, 0);
-    for (size_t i = 0; i < M; ++i) {
-        ocn_ctx *c = e->m[i];
-        if (forced_only && !e->frc.forced[i]) continue;
-        bool multi = false, goes = false;
-        if (!guarded(c, "ocn_ens_step_forced", [&] { return step_probe(c, tau, nsteps, check_every, &multi, &goes); })) {
-            variant[i] = ens_variant(c, tau, check_every == 1, multi);
-            go[i] = goes ? 1 : 0;
-        }
-    }
-}
-
 // the second RHSx / RHSy buffers of the forced members (one block), made where they are missing: zeroed, on the stream
 static int frc_second(ocn_ens *e)
 {
@@ -215,21 +195,20 @@ int ocn_ens_step_forced(ocn_ens *e, double tau, int32_t nsteps, int32_t check_ev
     // runs, as ocn_ens_step_record decides it: each member says whether it would plan ONE multi-step launch that
     // goes on with its open sequence (no tail to form, no deferred step that belongs to another time), the planner
     // whether it lands in a group under the forcing launch's capacity.  The call itself then plans the same way.
-    EnsFrcCall call{std::min<int64_t>(ens_capacity(e), onepass_multi_frc_capacity()), t0};
+    const EnsFrcCall frc_call{t0};
+    const EnsCall call{std::min<int64_t>(ens_capacity(e), onepass_multi_frc_capacity()), nullptr, &frc_call};
     bool in_launch = e->frc_in_launch && nsteps >= 2 && e->m[0]->blocks.size() == 1;
     if (in_launch) {
-        frc_probe(e, tau, nsteps, check_every, false, variant, go);
+        ens_probe(e, "ocn_ens_step_forced", tau, nsteps, check_every, nullptr, variant, go);
         std::vector<ocn_ens_group> groups;
         if (ens_groups(e, variant, call.capacity, groups)) in_launch = false;
-        std::vector<char> grouped((size_t)M, 0);
-        for (const ocn_ens_group &q : groups)
-            for (int j = 0; j < q.members; ++j) grouped[(size_t)q.member[j]] = 1;
+        const std::vector<char> grouped = ens_grouped(e, groups);
         for (int i = 0; i < M; ++i)
             if (f.forced[(size_t)i] && !(grouped[(size_t)i] && go[(size_t)i])) in_launch = false;
     }
     if (in_launch) {
         RC(frc_second(e));
-        note(ens_step_run(e, tau, nsteps, check_every, nullptr, &call));
+        note(ens_step_run(e, tau, nsteps, check_every, &call));
         f.in_launch = 1;
         f.steps += nsteps;
         return first;
@@ -239,7 +218,7 @@ int ocn_ens_step_forced(ocn_ens *e, double tau, int32_t nsteps, int32_t check_ev
     for (int32_t s = 0; s < nsteps; ++s) {
         const double ts = t0 + (double)s * tau;
         const int32_t ce = check_every > 0 && (s + 1) % check_every == 0 ? 1 : 0;
-        frc_probe(e, tau, 1, ce, true, variant, go);
+        ens_probe(e, "ocn_ens_step_forced", tau, 1, ce, f.forced.data(), variant, go);
         RC(frc_apply(e, ts, "ocn_ens_step_forced", &go));
         note(ens_step_run(e, tau, 1, ce, nullptr));
         ++f.steps;

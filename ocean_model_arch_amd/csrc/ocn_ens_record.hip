@@ -197,21 +197,16 @@ int ocn_ens_step_record(ocn_ens *e, double tau, int32_t nsteps, int32_t check_ev
     // the call runs (a member that has stepped without its records cannot be repaired): each member says
     // whether it would plan a multi-step launch (step_probe), the planner whether it lands in a group
     // under the recording capacity.  The call itself then plans the same way.
-    EnsRecCall rc_call{std::min<int64_t>(ens_capacity(e), onepass_multi_rec_capacity()), std::vector<int>((size_t)M, -1), 0, nullptr};
+    EnsRecCall rc_call{std::vector<int>((size_t)M, -1), 0, nullptr};
+    const EnsCall call{std::min<int64_t>(ens_capacity(e), onepass_multi_rec_capacity()), &rc_call, nullptr};
     bool in_launch = e->rec_in_launch && nsteps >= 2 && e->m[0]->blocks.size() == 1;
     if (in_launch) {
-        std::vector<int32_t> variant((size_t)M, -1);
-        for (int i = 0; i < M; ++i) {
-            ocn_ctx *c = e->m[(size_t)i];
-            bool multi = false, go = false;
-            if (!guarded(c, "ocn_ens_step_record", [&] { return step_probe(c, tau, nsteps, check_every, &multi, &go); }))
-                variant[(size_t)i] = ens_variant(c, tau, check_every == 1, multi);
-        }
+        std::vector<int32_t> variant;
+        std::vector<char> go;
+        ens_probe(e, "ocn_ens_step_record", tau, nsteps, check_every, nullptr, variant, go);
         std::vector<ocn_ens_group> groups;
-        if (ens_groups(e, variant, rc_call.capacity, groups)) in_launch = false;
-        std::vector<char> grouped((size_t)M, 0);
-        for (const ocn_ens_group &q : groups)
-            for (int j = 0; j < q.members; ++j) grouped[(size_t)q.member[j]] = 1;
+        if (ens_groups(e, variant, call.capacity, groups)) in_launch = false;
+        const std::vector<char> grouped = ens_grouped(e, groups);
         for (int i = 0, col = 0; i < M; ++i) {
             if (!r.use[(size_t)i]) continue;
             rc_call.col[(size_t)i] = col++;
@@ -223,7 +218,7 @@ int ocn_ens_step_record(ocn_ens *e, double tau, int32_t nsteps, int32_t check_ev
         RC(ens_rec_stage(e, mem_b + (tail ? r.tab_b : 0)));
         rc_call.due0 = due.empty() ? nsteps : due[0];   // (nsteps: nothing due inside the launch)
         rc_call.slot0 = (double *)r.d_series + (size_t)r.records * (size_t)r.nobs * (size_t)r.n;
-        note(ens_step_run(e, tau, nsteps, check_every, &rc_call));
+        note(ens_step_run(e, tau, nsteps, check_every, &call));
         // the last step's record: no barrier behind it in the launch, so a gather behind the launch, from the
         // tables after the host's role swap (the six state fields are current in an open sequence: no tail)
         if (tail) note(ens_rec_gather(e, in, r.records + (int32_t)due.size() - 1, mem_b));

@@ -206,6 +206,8 @@ int launch_onepass_multi(const ocn_block *b, void *const *ptr, int nptr, const C
 // n x onepass_multi_b_entry_bytes()); the host copy is read when the stream reaches the copy.
 // capacity: workgroups that may be resident (at most onepass_multi_b_capacity(), the occupancy of
 // every variant of both multi-step kernels x the device's CUs): n x tiles above it is an error.
+// launch_onepass_multi_ens is that launch; with `rec` the recorder is in it, with `frc` the forcing (below;
+// both at once: an error, there is no such kernel).
 struct EnsMember {
     const ocn_block *b;
     void *const *ptr;
@@ -217,7 +219,7 @@ struct EnsMember {
     int32_t *err;
     const double *kc;
     int spin;
-    // launch_onepass_multi_frc alone: the member's index in the ensemble (its entry of the forcing table) and,
+    // the forcing launch alone: the member's index in the ensemble (its entry of the forcing table) and,
     // for a forced member, its second RHSx / RHSy buffers (the odd steps' table names them)
     int index = 0;
     double *frc2[2] = {nullptr, nullptr};
@@ -225,9 +227,20 @@ struct EnsMember {
 int onepass_multi_variant(int kc_mode, double tau, bool check);
 size_t onepass_multi_b_entry_bytes();
 long onepass_multi_b_capacity();
-int launch_onepass_multi_b(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
-                           int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, hipStream_t s);
-// launch_onepass_multi_b with a station recorder in the launch (sw_kernels.hip k_march_multi_rec; ocn_sw.h
+struct EnsLaunch {
+    const EnsMember *m;
+    int n, variant, rows;
+    const ocn_sw_params &sw;
+    double tau;
+    int nsteps;
+    void *d_tab, *h_tab;
+    size_t tab_bytes;
+    long capacity;
+};
+struct EnsRecLaunch;
+struct EnsFrcLaunch;
+int launch_onepass_multi_ens(const EnsLaunch &L, const EnsRecLaunch *rec, const EnsFrcLaunch *frc, hipStream_t s);
+// The ensemble launch with a station recorder in it (sw_kernels.hip k_march_multi_rec; ocn_sw.h
 // ocn_ens_step_record): after each due step but the call's last, every member with a column >= 0 stores
 // H_j of its state into slot[j * n + col], j < nobs.  The operator is one table for all the members of the
 // launch (one block, one geometry): start as EnsObsOp's, term[t].slot the index of the term's field in
@@ -248,9 +261,6 @@ struct EnsRecLaunch {
     EnsRecMember *h_mem, *d_mem;
 };
 long onepass_multi_rec_capacity();
-int launch_onepass_multi_rec(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
-                             int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, const EnsRecLaunch &rec,
-                             hipStream_t s);
 // Statistics over the members of an ensemble (ens_stats.hip; ocn_sw.h ocn_ens_stats): of the n arrays
 // src[0 .. n) (one field of one block geometry in member order, all with the lane of A(bnd_x1, :) in its
 // 256-B line that src[0] has) into out[0 .. 5) = mean, variance, spread, minimum, maximum (based like the
@@ -375,7 +385,7 @@ int launch_ens_perturb_apply(const ocn_block *b, double *const *mem, int n, cons
 // member of one block geometry for time t, at the block's interior points.  d_tab: `members` entries on the
 // device, one per member of the ensemble -- its storm, its arrays of this block (the real(4) masks and metrics,
 // h_r, the two outputs) and whether it is forced (others are left alone).  lead: the lane of A(bnd_x1, :) within
-// its 256-B line.  ONE launch.  rx2, ry2: the member's second buffers (launch_onepass_multi_frc; else null).
+// its 256-B line.  ONE launch.  rx2, ry2: the member's second buffers (the forcing launch's; else null).
 struct EnsFrcMember {
     ocn_ens_storm s;
     const float *lcu, *lcv, *dx, *dy, *dxt, *dyt, *dxh, *dyh;
@@ -385,18 +395,15 @@ struct EnsFrcMember {
 };
 int launch_ens_forcing(const ocn_block *b, const EnsFrcMember *d_tab, int members, const ocn_ens_forcing_model &model,
                        double t, int lead, hipStream_t s);
-// launch_onepass_multi_b with the forcing formed in the launch (sw_kernels.hip k_march_multi_frc; ocn_sw.h
+// The ensemble launch with the forcing formed in it (sw_kernels.hip k_march_multi_frc; ocn_sw.h
 // ocn_ens_step_forced), for the general variants only: step s (0-based) of a forced member reads RHSx / RHSy from
 // buffer s & 1 -- 0 the fields' own arrays, 1 the member's second pair (EnsMember::frc2) -- and between its march
 // of step s and the barrier behind it every workgroup writes its share of the forcing of t0 + (double)(s + 1) tau
 // into buffer (s + 1) & 1.  The caller has written the forcing of t0 into the fields' own arrays ahead of the
 // launch.  d_tab: the forcing table of the block (launch_ens_forcing's), indexed by EnsMember::index; a member that
-// is not forced there marches as in launch_onepass_multi_b.  capacity: at most onepass_multi_frc_capacity().
+// is not forced there marches as in the plain launch.  capacity: at most onepass_multi_frc_capacity().
 struct EnsFrcLaunch { const EnsFrcMember *d_tab; ocn_ens_forcing_model model; double t0; };
 long onepass_multi_frc_capacity();
-int launch_onepass_multi_frc(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
-                             int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, const EnsFrcLaunch &frc,
-                             hipStream_t s);
 // the known-constant precondition of launch_onepass over r (sw_kernels.hip FallbackCheck: the
 // fallback points and the forcing hold +0.0, h_r and mu are uniform): ORs 1 into *flag where it
 // does not hold; writes h_r and mu at (r.m0, r.n0) to kc[0], kc[1]

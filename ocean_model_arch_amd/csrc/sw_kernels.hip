@@ -3216,13 +3216,19 @@ int launch_onepass(const ocn_block *b, void *const *ptr, int nptr, const Compact
 // group g's arrivals, the group's last arriver adds to bar[0] and, once all groups are in, publishes
 // the epoch in bar[32 (9 + g)], which the group's other workgroups await -- 8 words polled instead of
 // one, and each atomic queue 1/8 as long.  (Words 128 B apart.)
-__device__ __forceinline__ bool grid_barrier(unsigned *bar, unsigned epoch, int32_t *err, int spin)
+// member_barrier is that barrier for the count() workgroups that share the words `bar`, `tile` this one's index
+// among them: k_march_multi's whole grid (gridDim.x, blockIdx.x), or one member of an ensemble launch.  (The
+// count is a callable so that the grid's is read where lane 0 needs it, as an argument is: an ordinary
+// unsigned parameter moves k_march_multi's load of gridDim.x and changes its code.)
+template <class Count>
+__device__ __forceinline__ bool member_barrier(unsigned *bar, Count count, unsigned tile, unsigned epoch, int32_t *err,
+                                               int spin)
 {
     __shared__ int ok_s;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's write-through stores reached memory
     __syncthreads();
     if (threadIdx.x == 0) {
-        const unsigned n = gridDim.x, g = blockIdx.x & 7u, ng = (n - g + 7u) / 8u, groups = n < 8u ? n : 8u;
+        const unsigned n = count(), g = tile & 7u, ng = (n - g + 7u) / 8u, groups = n < 8u ? n : 8u;
         const unsigned t = __hip_atomic_fetch_add(bar + 32 * (1 + g), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         int k = 0;
         if (t + 1 == ng * epoch) {   // the group's last arrival of this epoch
@@ -3244,7 +3250,34 @@ __device__ __forceinline__ bool grid_barrier(unsigned *bar, unsigned epoch, int3
     return ok_s != 0;
 }
 
+// The two bodies of a multi-step launch: step s runs b[s & 1], the even steps on the field table t0 and the
+// second buffers alt0, the odd steps on the odd steps' table t1 and alt1 (odd_table)
 template <class Body> struct BodyPair { Body b[2]; };
+template <class Body>
+static BodyPair<Body> body_pair(const ocn_block &b, const Tab<true> &t0, const Tab<true> &t1, const ocn_sw_params &sw,
+                                double tau, int32_t *nbad, double *const alt0[3], double *const alt1[3], const double *kc)
+{
+    return {{Body{b, t0, sw, tau, nbad, alt0[0], alt0[1], alt0[2], kc, nullptr, 0, 0u},
+             Body{b, t1, sw, tau, nbad, alt1[0], alt1[1], alt1[2], kc, nullptr, 0, 0u}}};
+}
+// The odd steps' table of a field table and the second buffers that go with it: the role pairs and the second
+// buffers swapped (ocn_ctx.hip swap_roles / swap_alt3); frc2 (null: none): a forced member's second RHSx / RHSy
+// buffers, which the odd steps read
+struct OddTable { std::vector<void *> ptr; double *alt[3]; };
+static OddTable odd_table(void *const *ptr, int nptr, double *const alt[3], double *const frc2[2])
+{
+    OddTable t{std::vector<void *>(ptr, ptr + nptr), {alt[0], alt[1], alt[2]}};
+    for (const auto &pr : {std::make_pair(OCN_SSH, OCN_SSHN), std::make_pair(OCN_UBRTR, OCN_UBRTRN),
+                           std::make_pair(OCN_VBRTR, OCN_VBRTRN)})
+        std::swap(t.ptr[ocn_field_slot(pr.first)], t.ptr[ocn_field_slot(pr.second)]);
+    const int ids[3] = {OCN_SSHP, OCN_UBRTRP, OCN_VBRTRP};
+    for (int i = 0; i < 3; ++i) std::swap(t.ptr[ocn_field_slot(ids[i])], *(void **)&t.alt[i]);
+    if (frc2 && frc2[0] && frc2[1]) {
+        t.ptr[ocn_field_slot(OCN_RHSX)] = frc2[0];
+        t.ptr[ocn_field_slot(OCN_RHSY)] = frc2[1];
+    }
+    return t;
+}
 template <class Body>
 __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi(MarchGrid g, BodyPair<Body> bp, int nsteps,
                                                                        unsigned *ctr, int32_t *err, int spin)
@@ -3255,7 +3288,7 @@ __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi(MarchGrid
     for (int s = 0; s < nsteps; ++s) {
         // ONE inlined march, the step's body picked at run time (two inlined copies: 93 KB of code)
         march_tile<Body, false>(R, tile, bp.b[__builtin_amdgcn_readfirstlane(s & 1)]);
-        if (s + 1 < nsteps && !grid_barrier(ctr, (unsigned)(s + 1), err, spin)) return;
+        if (s + 1 < nsteps && !member_barrier(ctr, [] { return gridDim.x; }, blockIdx.x, (unsigned)(s + 1), err, spin)) return;
     }
 }
 
@@ -3281,9 +3314,12 @@ template <class F> static auto multi_dispatch(int variant, F &&f)
 // The resident capacity of a multi-step kernel on the current device, in workgroups: the fewest of `base`
 // and any variant's occupancy x the device's CUs (a device with fewer CUs, a partition mode, another
 // compile of the march), queried once per device into the caller's cache; 0 if a query fails (no
-// multi-step launch then).  kernel(tag) = the kernel of the body BodyTag tag names.
+// multi-step launch then).  kernel(tag) = the kernel of the body BodyTag tag names; Which: the bodies the
+// kernel exists for.
 struct CapacityCache { std::mutex mu; std::map<int, long> cap; };
-template <class K> static long resident_capacity(CapacityCache &cache, long base, K &&kernel)
+struct AnyBody { template <class Body> static constexpr bool has = true; };
+struct GeneralBody { template <class Body> static constexpr bool has = Body::kLds == 0; };   // (the general variants')
+template <class Which = AnyBody, class K> static long resident_capacity(CapacityCache &cache, long base, K &&kernel)
 {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
@@ -3293,9 +3329,11 @@ template <class K> static long resident_capacity(CapacityCache &cache, long base
     long c = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? base : 0;
     for (int v = 0; v < 6; ++v)
         multi_dispatch(v, [&](auto tag) {
-            int per = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel(tag), 256, 0) != hipSuccess) per = 0;
-            c = std::min(c, (long)per * cus);
+            if constexpr (Which::template has<typename decltype(tag)::type>) {
+                int per = 0;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel(tag), 256, 0) != hipSuccess) per = 0;
+                c = std::min(c, (long)per * cus);
+            }
             return 0;
         });
     return cache.cap[dev] = c;
@@ -3330,24 +3368,17 @@ int launch_onepass_multi(const ocn_block *b, void *const *ptr, int nptr, const C
     if (range_empty(r)) return OCN_OK;
     const int rows = multi_rows(r);
     if (!rows) return set_error(OCN_ERR_ARG, "multi-step launch: block too large for one resident grid");
-    // the odd steps' table: the role pairs and the second buffers swapped (ocn_ctx.hip swap_roles / swap_alt3)
-    std::vector<void *> odd(ptr, ptr + nptr);
-    for (const auto &pr : {std::make_pair(OCN_SSH, OCN_SSHN), std::make_pair(OCN_UBRTR, OCN_UBRTRN),
-                           std::make_pair(OCN_VBRTR, OCN_VBRTRN)})
-        std::swap(odd[ocn_field_slot(pr.first)], odd[ocn_field_slot(pr.second)]);
-    double *alt[3] = {sshp_alt, up_alt, vp_alt};
-    const int ids[3] = {OCN_SSHP, OCN_UBRTRP, OCN_VBRTRP};
-    for (int i = 0; i < 3; ++i) std::swap(odd[ocn_field_slot(ids[i])], *(void **)&alt[i]);
+    double *const alt[3] = {sshp_alt, up_alt, vp_alt};
+    const OddTable odd = odd_table(ptr, nptr, alt, nullptr);
     const Tab<true> t0 = make_tab<true>(ptr, nptr, cp->bits, cp->rows, block_rows(b), 0);
-    const Tab<true> t1 = make_tab<true>(odd.data(), nptr, cp->bits, cp->rows, block_rows(b), 0);
+    const Tab<true> t1 = make_tab<true>(odd.ptr.data(), nptr, cp->bits, cp->rows, block_rows(b), 0);
     MarchGrid g{};
     g.r[0] = MarchRect{};
     if (batching(s)) return batch_violation();   // (a multi-step launch is not batched)
     RC_K(check_hip(hipMemsetAsync(ctr, 0, kMultiBarBytes, s), "multi-step launch: barrier words"));
     return step_dispatch<false, false, false, true, false>(tau_is_pow2(tau), kc.mode, [&](auto tag) -> int {
         using Body = typename decltype(tag)::type;
-        const Body k0{*b, t0, sw, tau, nbad, sshp_alt, up_alt, vp_alt, kc.kc, nullptr, 0, 0u};
-        const Body k1{*b, t1, sw, tau, nbad, alt[0], alt[1], alt[2], kc.kc, nullptr, 0, 0u};
+        const BodyPair<Body> bp = body_pair<Body>(*b, t0, t1, sw, tau, nbad, alt, odd.alt, kc.kc);
         g.r[0] = march_rect<Body>(b, r, rows, true);
         g.nr = 1;
         g.ntiles = g.r[0].tiles;
@@ -3356,8 +3387,7 @@ int launch_onepass_multi(const ocn_block *b, void *const *ptr, int nptr, const C
         if (g.ntiles != multi_tiles(r, rows) || g.ntiles > multi_capacity())
             return set_error(OCN_ERR_ARG, "multi-step launch: grid larger than the resident capacity");
         count_launch();
-        k_march_multi<Body><<<dim3((unsigned)g.ntiles), dim3(256), 0, s>>>(g, BodyPair<Body>{{k0, k1}}, nsteps, ctr, err,
-                                                                             spin < 1 ? 1 : spin);
+        k_march_multi<Body><<<dim3((unsigned)g.ntiles), dim3(256), 0, s>>>(g, bp, nsteps, ctr, err, spin < 1 ? 1 : spin);
         return check_hip(hipGetLastError(), "multi-step launch");
     });
 }
@@ -3372,8 +3402,8 @@ int launch_onepass_multi(const ocn_block *b, void *const *ptr, int nptr, const C
 // an ensemble of 64 would need 22 chunked launches -- one table read with scalar loads instead (the
 // constant address space: the table is written by a copy ordered before the launch and never by
 // the kernel, so the loads are uniform and go through the scalar cache as kernel arguments do).
-// Each member's barrier is its own: grid_barrier's arithmetic with the member's tile count and the
-// workgroup's tile index within the member in place of gridDim.x and blockIdx.x, on the member's own
+// Each member's barrier is its own: member_barrier with the member's tile count and the workgroup's
+// tile index within the member in place of gridDim.x and blockIdx.x, on the member's own
 // kMultiBarBytes of words.  A member whose barrier gives up ORs 1 into its own flag and its
 // workgroups end; the other members' workgroups never look at those words.  Every workgroup of the
 // launch must be resident at once (members x tiles <= the capacity, checked by the host): a member's
@@ -3383,37 +3413,8 @@ template <class Body> struct EnsEntry {
     MarchRect R;
     unsigned *bar;
     int32_t *err;
-    int spin, pad;
+    int spin, index;   // index: the member's index in the ensemble (the forcing launch's; else 0)
 };
-
-__device__ __forceinline__ bool member_barrier(unsigned *bar, unsigned n, unsigned tile, unsigned epoch, int32_t *err,
-                                               int spin)
-{
-    __shared__ int ok_s;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's write-through stores reached memory
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned g = tile & 7u, ng = (n - g + 7u) / 8u, groups = n < 8u ? n : 8u;
-        const unsigned t = __hip_atomic_fetch_add(bar + 32 * (1 + g), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int k = 0;
-        if (t + 1 == ng * epoch) {   // the group's last arrival of this epoch
-            __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < groups * epoch && ++k < spin)
-                __builtin_amdgcn_s_sleep(1);
-            __hip_atomic_store(bar + 32 * (9 + g), epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            while (__hip_atomic_load(bar + 32 * (9 + g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < epoch &&
-                   ++k < spin)
-                __builtin_amdgcn_s_sleep(1);
-        }
-        const bool ok = k < spin;
-        if (!ok) atomicOr(err, 1);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // drop stale lines: the next step's loads
-        ok_s = ok;
-    }
-    __syncthreads();
-    return ok_s != 0;
-}
 
 template <class Body>
 __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_b(const EnsEntry<Body> *__restrict__ tab, int tiles,
@@ -3430,7 +3431,9 @@ __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_b(const E
     if constexpr (HasPrologue<Body>::v) ((const Body *)&e->b[0])->prologue(R, tile / R.ntx);   // the same rows every step
     for (int s = 0; s < nsteps; ++s) {
         march_tile<Body, false>(R, tile, *(const Body *)&e->b[__builtin_amdgcn_readfirstlane(s & 1)]);
-        if (s + 1 < nsteps && !member_barrier(bar, (unsigned)tiles, (unsigned)tile, (unsigned)(s + 1), err, spin)) return;
+        if (s + 1 < nsteps &&
+            !member_barrier(bar, [tiles] { return (unsigned)tiles; }, (unsigned)tile, (unsigned)(s + 1), err, spin))
+            return;
     }
 }
 
@@ -3502,7 +3505,7 @@ __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_rec(const
     for (int s = 0; s < nsteps; ++s) {
         march_tile<Body, false>(R, tile, *(const Body *)&e->b[__builtin_amdgcn_readfirstlane(s & 1)]);
         if (s + 1 == nsteps) break;
-        if (!member_barrier(bar, (unsigned)tiles, (unsigned)tile, (unsigned)(s + 1), err, spin)) return;
+        if (!member_barrier(bar, [tiles] { return (unsigned)tiles; }, (unsigned)tile, (unsigned)(s + 1), err, spin)) return;
         if (s + 1 != due) continue;
         if (col >= 0) {   // state s + 1, in the table of its parity
             const int par = __builtin_amdgcn_readfirstlane((s + 1) & 1);
@@ -3530,7 +3533,7 @@ __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_rec(const
 // barrier's vmcnt(0) before the arrival: the barrier has no L2 write-back and the XCDs share no L2.  The next
 // step reads them with the march's ordinary loads behind the barrier's acquire, as it reads the state.  The
 // masks, metrics and h_r are never written by a kernel of the launch: ordinary loads too.  The members' table
-// (EnsFrcMember, indexed by EnsEntry::pad: the member's index in the ensemble) is written by a copy ordered
+// (EnsFrcMember, indexed by EnsEntry::index: the member's index in the ensemble) is written by a copy ordered
 // before the launch: scalar loads through the constant address space.  A member that is not forced skips the
 // loop (workgroup-uniform) and marches as in k_march_multi_b.  No atomics or LDS beyond the barrier's.
 struct EnsFrcArgs {
@@ -3577,7 +3580,7 @@ __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_frc(const
     const int mem = __builtin_amdgcn_readfirstlane((int)blockIdx.x / tiles);
     const int tile = (int)blockIdx.x - mem * tiles;
     ConstTab e = (ConstTab)tab + mem;
-    ConstFrc fm = (ConstFrc)frc.tab + e->pad;
+    ConstFrc fm = (ConstFrc)frc.tab + e->index;
     const MarchRect R = *(const MarchRect *)&e->R;
     unsigned *const bar = e->bar;
     int32_t *const err = e->err;
@@ -3588,7 +3591,7 @@ __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_frc(const
         march_tile<Body, false>(R, tile, *(const Body *)&e->b[__builtin_amdgcn_readfirstlane(s & 1)]);
         if (s + 1 == nsteps) break;
         if (forced) frc_fill(fm, frc, s + 1, tile, tiles);
-        if (!member_barrier(bar, (unsigned)tiles, (unsigned)tile, (unsigned)(s + 1), err, spin)) return;
+        if (!member_barrier(bar, [tiles] { return (unsigned)tiles; }, (unsigned)tile, (unsigned)(s + 1), err, spin)) return;
     }
 }
 
@@ -3630,43 +3633,45 @@ long onepass_multi_rec_capacity()
 long onepass_multi_frc_capacity()
 {
     static CapacityCache cache;
-    const long base = onepass_multi_b_capacity();
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> g(cache.mu);
-    const auto it = cache.cap.find(dev);
-    if (it != cache.cap.end()) return it->second;
-    long c = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? base : 0;
-    for (int p2 = 0; p2 < 2; ++p2)
-        step_dispatch<false, false, false, true, false>(p2 != 0, OCN_KC_GENERAL, [&](auto tag) {
-            using Body = typename decltype(tag)::type;
-            if constexpr (Body::kLds == 0) {   // (the general bodies: the only ones the kernel is built for)
-                int per = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_march_multi_frc<Body>, 256, 0) != hipSuccess) per = 0;
-                c = std::min(c, (long)per * cus);
-            }
-            return 0;
-        });
-    return cache.cap[dev] = c;
+    return resident_capacity<GeneralBody>(cache, onepass_multi_b_capacity(),
+                                          [](auto tag) { return k_march_multi_frc<typename decltype(tag)::type>; });
 }
 
-// launch_onepass_multi_b (rec and frc null), launch_onepass_multi_rec and launch_onepass_multi_frc behind their
-// checks: one table of entries, one launch
-static int launch_multi_b_impl(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
-                               int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, const EnsRecLaunch *rec,
-                               hipStream_t s, const EnsFrcLaunch *frc = nullptr)
+// The ensemble launch (ocn_internal.h EnsLaunch): one table of entries, one launch -- the plain kernel, the
+// recording one with `rec`, the forcing one with `frc`
+int launch_onepass_multi_ens(const EnsLaunch &L, const EnsRecLaunch *rec, const EnsFrcLaunch *frc, hipStream_t s)
 {
-    if (!m || n < 1 || variant < 0 || variant >= 12 || rows < 1 || rows > 16 || nsteps < 1 || !d_tab || !h_tab)
+    const EnsMember *const m = L.m;
+    const int n = L.n, variant = L.variant, rows = L.rows, nsteps = L.nsteps;
+    if (rec && frc) return set_error(OCN_ERR_ARG, "ensemble launch: a recorder and a forcing in one launch");
+    if (rec) {
+        if (!rec->col || !rec->field || rec->nfields < 1 || rec->nfields > OCN_ENS_OBS_MAX_FIELDS || !rec->d_start ||
+            !rec->d_term || !rec->slot0 || rec->due0 < 1 || rec->every < 1 || rec->nobs < 1 || rec->n < 1 || !rec->h_mem ||
+            !rec->d_mem)
+            return set_error(OCN_ERR_ARG, "ensemble launch: the recorder's tables, schedule or slot");
+        for (int f = 0; f < rec->nfields; ++f)
+            if (rec->field[f] != OCN_SSH && rec->field[f] != OCN_SSHP && rec->field[f] != OCN_UBRTR &&
+                rec->field[f] != OCN_UBRTRP && rec->field[f] != OCN_VBRTR && rec->field[f] != OCN_VBRTRP)
+                return set_error(OCN_ERR_ARG, "ensemble launch: the recorder reads the six prognostic fields only");
+    }
+    if (frc) {
+        if (!frc->d_tab || variant < 0 || (variant % 6) / 2 != 2)
+            return set_error(OCN_ERR_ARG, "ensemble launch: the forcing's table, or a variant that is not the general one");
+        for (int i = 0; m && i < n; ++i)
+            if (m[i].index < 0 || m[i].index >= OCN_ENS_MAX_MEMBERS || !m[i].b || (i && std::memcmp(m[i].b, m[0].b, sizeof(ocn_block))))
+                return set_error(OCN_ERR_ARG, "ensemble launch: a member's index in the forcing table, or members of different blocks");
+    }
+    if (!m || n < 1 || variant < 0 || variant >= 12 || rows < 1 || rows > 16 || nsteps < 1 || !L.d_tab || !L.h_tab)
         return set_error(OCN_ERR_ARG, "ensemble launch: members, a variant, 1..16 rows, a table");
-    if (!onepass_switches(sw))
+    if (!onepass_switches(L.sw))
         return set_error(OCN_ERR_ARG, "ensemble launch: full_free_surface = 1, trans_terms and ksw_lat on");
     if (batching(s)) return batch_violation();
     const bool check = variant >= 6;
     return multi_dispatch(variant, [&](auto proto) -> int {
         using Body = typename decltype(proto)::type;
         using Entry = EnsEntry<Body>;
-        if (sizeof(Entry) * (size_t)n > tab_bytes) return set_error(OCN_ERR_ARG, "ensemble launch: table too small");
-        Entry *tab = (Entry *)h_tab;
+        if (sizeof(Entry) * (size_t)n > L.tab_bytes) return set_error(OCN_ERR_ARG, "ensemble launch: table too small");
+        Entry *tab = (Entry *)L.h_tab;
         int tiles = 0;
         for (int i = 0; i < n; ++i) {
             const EnsMember &e = m[i];
@@ -3676,114 +3681,62 @@ static int launch_multi_b_impl(const EnsMember *m, int n, int variant, int rows,
             RC_K(check_block(e.b));
             const Range r = range_interior(e.b);
             if (range_empty(r)) return set_error(OCN_ERR_ARG, "ensemble launch: empty block");
-            // the odd steps' table, as launch_onepass_multi builds it
-            std::vector<void *> odd(e.ptr, e.ptr + e.nptr);
-            for (const auto &pr : {std::make_pair(OCN_SSH, OCN_SSHN), std::make_pair(OCN_UBRTR, OCN_UBRTRN),
-                                   std::make_pair(OCN_VBRTR, OCN_VBRTRN)})
-                std::swap(odd[ocn_field_slot(pr.first)], odd[ocn_field_slot(pr.second)]);
-            double *alt[3] = {e.alt[0], e.alt[1], e.alt[2]};
-            const int ids[3] = {OCN_SSHP, OCN_UBRTRP, OCN_VBRTRP};
-            for (int j = 0; j < 3; ++j) std::swap(odd[ocn_field_slot(ids[j])], *(void **)&alt[j]);
-            if (frc && e.frc2[0] && e.frc2[1]) {   // (a forced member: the odd steps read its second forcing buffers)
-                odd[ocn_field_slot(OCN_RHSX)] = e.frc2[0];
-                odd[ocn_field_slot(OCN_RHSY)] = e.frc2[1];
-            }
+            // (a forced member: the odd steps read its second forcing buffers)
+            const OddTable odd = odd_table(e.ptr, e.nptr, e.alt, frc ? e.frc2 : nullptr);
             const Tab<true> t0 = make_tab<true>(e.ptr, e.nptr, e.cp->bits, e.cp->rows, block_rows(e.b), 0);
-            const Tab<true> t1 = make_tab<true>(odd.data(), e.nptr, e.cp->bits, e.cp->rows, block_rows(e.b), 0);
-            int32_t *const nbad = check ? e.nbad : nullptr;
-            const Body k0{*e.b, t0, sw, tau, nbad, e.alt[0], e.alt[1], e.alt[2], e.kc, nullptr, 0, 0u};
-            const Body k1{*e.b, t1, sw, tau, nbad, alt[0], alt[1], alt[2], e.kc, nullptr, 0, 0u};
-            std::memcpy((void *)&tab[i].b[0], &k0, sizeof(Body));
-            std::memcpy((void *)&tab[i].b[1], &k1, sizeof(Body));
+            const Tab<true> t1 = make_tab<true>(odd.ptr.data(), e.nptr, e.cp->bits, e.cp->rows, block_rows(e.b), 0);
+            const BodyPair<Body> bp = body_pair<Body>(*e.b, t0, t1, L.sw, L.tau, check ? e.nbad : nullptr, e.alt, odd.alt, e.kc);
+            std::memcpy((void *)tab[i].b, &bp, sizeof(bp));
             tab[i].R = march_rect<Body>(e.b, r, rows, true);
             tab[i].bar = e.ctr;
             tab[i].err = e.err;
             tab[i].spin = e.spin < 1 ? 1 : e.spin;
-            tab[i].pad = frc ? e.index : 0;
+            tab[i].index = frc ? e.index : 0;
             if (tab[i].R.tiles != multi_tiles(r, rows) || (i && tab[i].R.tiles != tiles))
                 return set_error(OCN_ERR_ARG, "ensemble launch: the members' tile counts differ");
             tiles = tab[i].R.tiles;
         }
         // residency from the grid size alone, as the single-member launch: every workgroup at once
-        if ((long)n * tiles > capacity ||
-            capacity > (rec ? onepass_multi_rec_capacity() : frc ? onepass_multi_frc_capacity() : onepass_multi_b_capacity()))
+        const long resident = rec ? onepass_multi_rec_capacity() : frc ? onepass_multi_frc_capacity() : onepass_multi_b_capacity();
+        if ((long)n * tiles > L.capacity || L.capacity > resident)
             return set_error(OCN_ERR_ARG, "ensemble launch: grid larger than the resident capacity");
-        EnsRecArgs ra{};
         if (rec) {   // the recorder's tables: per member the operator's fields in both parities' buffers, and the column
             for (int i = 0; i < n; ++i) {
                 const EnsMember &e = m[i];
-                std::vector<void *> odd(e.ptr, e.ptr + e.nptr);   // (as above)
-                for (const auto &pr : {std::make_pair(OCN_SSH, OCN_SSHN), std::make_pair(OCN_UBRTR, OCN_UBRTRN),
-                                       std::make_pair(OCN_VBRTR, OCN_VBRTRN)})
-                    std::swap(odd[ocn_field_slot(pr.first)], odd[ocn_field_slot(pr.second)]);
-                const int ids[3] = {OCN_SSHP, OCN_UBRTRP, OCN_VBRTRP};
-                for (int j = 0; j < 3; ++j) odd[ocn_field_slot(ids[j])] = e.alt[j];
+                const OddTable odd = odd_table(e.ptr, e.nptr, e.alt, nullptr);
                 EnsRecMember &q = rec->h_mem[i];
                 for (int f = 0; f < OCN_ENS_OBS_MAX_FIELDS; ++f) {   // (unused entries: the first field's, never read)
                     const int slot = ocn_field_slot(rec->field[f < rec->nfields ? f : 0]);
                     q.f[0][f] = (const double *)e.ptr[slot];
-                    q.f[1][f] = (const double *)odd[slot];
+                    q.f[1][f] = (const double *)odd.ptr[slot];
                 }
                 q.col = rec->col[i];
                 q.pad = 0;
             }
             RC_K(check_hip(hipMemcpyAsync(rec->d_mem, rec->h_mem, sizeof(EnsRecMember) * (size_t)n, hipMemcpyHostToDevice, s),
                            "ensemble launch: recorder table"));
-            ra = EnsRecArgs{rec->d_mem, rec->d_start, rec->d_term, rec->slot0, rec->due0, rec->every, rec->nobs, rec->n};
         }
-        RC_K(check_hip(hipMemcpyAsync(d_tab, h_tab, sizeof(Entry) * (size_t)n, hipMemcpyHostToDevice, s),
+        RC_K(check_hip(hipMemcpyAsync(L.d_tab, L.h_tab, sizeof(Entry) * (size_t)n, hipMemcpyHostToDevice, s),
                        "ensemble launch: member table"));
         count_launch();
-        if (frc) {
-            if constexpr (Body::kLds == 0) {   // (the general bodies)
-                const ocn_block &g = *m[0].b;
-                const EnsFrcArgs fa{frc->d_tab, frc->model, frc->t0, tau, g.nx_start - g.bnd_x1, g.nx_end - g.bnd_x1,
-                                    g.ny_start - g.bnd_y1, g.ny_end - g.bnd_y1, (long)g.pitch,
-                                    (unsigned)(g.pitch * (g.bnd_y2 - g.bnd_y1 + 1) * 8), (int)g.bnd_x1, (int)g.bnd_y1};
-                k_march_multi_frc<Body><<<dim3((unsigned)(n * tiles)), dim3(256), 0, s>>>((const Entry *)d_tab, tiles, nsteps, fa);
-            } else {
-                return set_error(OCN_ERR_ARG, "ensemble launch: the forcing launch has the general bodies only");
-            }
-        } else if (rec) {
-            k_march_multi_rec<Body><<<dim3((unsigned)(n * tiles)), dim3(256), 0, s>>>((const Entry *)d_tab, tiles, nsteps, ra);
+        const dim3 grid((unsigned)(n * tiles)), block(256);
+        const Entry *const d_tab = (const Entry *)L.d_tab;
+        if (rec) {
+            const EnsRecArgs ra{rec->d_mem, rec->d_start, rec->d_term, rec->slot0, rec->due0, rec->every, rec->nobs, rec->n};
+            k_march_multi_rec<Body><<<grid, block, 0, s>>>(d_tab, tiles, nsteps, ra);
+        } else if (!frc) {
+            k_march_multi_b<Body><<<grid, block, 0, s>>>(d_tab, tiles, nsteps);
+        } else if constexpr (GeneralBody::has<Body>) {
+            const ocn_block &g = *m[0].b;
+            const EnsFrcArgs fa{frc->d_tab, frc->model, frc->t0, L.tau, g.nx_start - g.bnd_x1, g.nx_end - g.bnd_x1,
+                                g.ny_start - g.bnd_y1, g.ny_end - g.bnd_y1, (long)g.pitch,
+                                (unsigned)(g.pitch * (g.bnd_y2 - g.bnd_y1 + 1) * 8), (int)g.bnd_x1, (int)g.bnd_y1};
+            k_march_multi_frc<Body><<<grid, block, 0, s>>>(d_tab, tiles, nsteps, fa);
         } else {
-            k_march_multi_b<Body><<<dim3((unsigned)(n * tiles)), dim3(256), 0, s>>>((const Entry *)d_tab, tiles, nsteps);
+            return set_error(OCN_ERR_ARG, "ensemble launch: the forcing launch has the general bodies only");
         }
         return check_hip(hipGetLastError(), "ensemble launch");
     });
-}
-
-int launch_onepass_multi_b(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
-                           int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, hipStream_t s)
-{
-    return launch_multi_b_impl(m, n, variant, rows, sw, tau, nsteps, d_tab, h_tab, tab_bytes, capacity, nullptr, s);
-}
-
-int launch_onepass_multi_rec(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
-                             int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, const EnsRecLaunch &rec,
-                             hipStream_t s)
-{
-    if (!rec.col || !rec.field || rec.nfields < 1 || rec.nfields > OCN_ENS_OBS_MAX_FIELDS || !rec.d_start || !rec.d_term ||
-        !rec.slot0 || rec.due0 < 1 || rec.every < 1 || rec.nobs < 1 || rec.n < 1 || !rec.h_mem || !rec.d_mem)
-        return set_error(OCN_ERR_ARG, "ensemble launch: the recorder's tables, schedule or slot");
-    for (int f = 0; f < rec.nfields; ++f)
-        if (rec.field[f] != OCN_SSH && rec.field[f] != OCN_SSHP && rec.field[f] != OCN_UBRTR && rec.field[f] != OCN_UBRTRP &&
-            rec.field[f] != OCN_VBRTR && rec.field[f] != OCN_VBRTRP)
-            return set_error(OCN_ERR_ARG, "ensemble launch: the recorder reads the six prognostic fields only");
-    return launch_multi_b_impl(m, n, variant, rows, sw, tau, nsteps, d_tab, h_tab, tab_bytes, capacity, &rec, s);
-}
-
-int launch_onepass_multi_frc(const EnsMember *m, int n, int variant, int rows, const ocn_sw_params &sw, double tau,
-                             int nsteps, void *d_tab, void *h_tab, size_t tab_bytes, long capacity, const EnsFrcLaunch &frc,
-                             hipStream_t s)
-{
-    if (!frc.d_tab || variant < 0 || (variant % 6) / 2 != 2)
-        return set_error(OCN_ERR_ARG, "ensemble launch: the forcing's table, or a variant that is not the general one");
-    for (int i = 0; m && i < n; ++i) {
-        if (m[i].index < 0 || m[i].index >= OCN_ENS_MAX_MEMBERS || !m[i].b || (i && std::memcmp(m[i].b, m[0].b, sizeof(ocn_block))))
-            return set_error(OCN_ERR_ARG, "ensemble launch: a member's index in the forcing table, or members of different blocks");
-    }
-    return launch_multi_b_impl(m, n, variant, rows, sw, tau, nsteps, d_tab, h_tab, tab_bytes, capacity, nullptr, s, &frc);
 }
 
 // Rows per workgroup tile of the two-step launch: the fewest iterations in total, counting

@@ -254,7 +254,7 @@ def test_tracer_steps_after_inconsistent_mu_upload_match_oracle(amd):
 
 # ---------------------------------------------------------------- advisor regressions (round 4)
 def test_multi_barrier_timeout_reports_and_recovers(amd):
-    """The multi-step launch's grid barrier is bounded (sw_kernels.hip grid_barrier): forced to give up
+    """The multi-step launch's grid barrier is bounded (sw_kernels.hip member_barrier): forced to give up
     after one poll (OCN_OPT_MULTI_SPIN 1), every workgroup ends, synchronize() reports OCN_ERR_HIP once
     (no hang), and init() starts over: the next run is bitwise the oracle's."""
     n = 100
