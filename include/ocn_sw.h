@@ -1166,6 +1166,70 @@ int ocn_ens_forcing_apply(ocn_ens *ens, double t);
 int ocn_ens_step_forced(ocn_ens *ens, double tau, int32_t nsteps, int32_t check_every, double t0);
 int ocn_ens_forcing_info(ocn_ens *ens, ocn_ens_forcing_info_t *out);
 
+/* The peak map: per point and member the highest and / or lowest value a prognostic field has had after a step,
+ * and the number of that step, kept on the device between the steps of the ensemble's launches (csrc/ens_peak.hip
+ * k_ens_peak, csrc/sw_kernels.hip k_march_multi_pk; the rule is csrc/ens_peak_point.h, its numpy restatement
+ * ocean_model_arch_amd/ens_peak_rule.py).
+ *
+ * ocn_ens_peak_begin(ens, use, field_id, what): field_id one of OCN_SSH, OCN_SSHP, OCN_UBRTR, OCN_UBRTRP, OCN_VBRTR,
+ * OCN_VBRTRP (the recorder's set); what a mask of OCN_ENS_PEAK_MAX and OCN_ENS_PEAK_MIN.  For each extreme asked
+ * for, every tracked member (use as in ocn_ens_stats: one byte per member, NULL: all) gets per local block an array
+ * P of doubles in the members' layout and an array S of int32 with the same element indexing.  Steps that pair
+ * launches deferred are run first for the tracked members (no other call tail is formed); then P = the field's
+ * current value and S = 0 at every interior point nx_start..nx_end x ny_start..ny_end, land included; everything
+ * outside the interior is +0.0 / 0 and is never written again; the step counter k is 0.  A second begin starts
+ * over (the new arrays are whole before the earlier ones go).  Asynchronous.
+ * The rule: after the k-th step since begin, with x the field's value after that step (what the CPU oracle holds
+ * after as many step(tau) calls: the recorder's contract),
+ *     MAX:  if (x > P || P != P) { P = x; S = k; }          MIN: the same with <
+ * -- ocn_ens_stats' MIN / MAX comparisons: a tie, +-0 included, keeps the earlier step and its bits; a NaN in P goes
+ * as soon as a number arrives; a NaN x never replaces a number.
+ * Who steps the peaks: ocn_ens_step and ocn_ens_step_forced, after each of their steps, for the tracked members,
+ * while a peak is active (without one they take exactly the path they take without this section).  counted + nsteps
+ * beyond INT32_MAX is OCN_ERR_ARG.  ocn_ens_step_record with a peak active is OCN_ERR_STATE: recording and peaks
+ * in one launch are not built.  Entries that change the state without stepping (ocn_ens_transform, the
+ * assimilation entries, ocn_ens_inflate, ocn_ens_perturb, ocn_ctx_upload, ocn_ens_init_state) touch neither P, S
+ * nor k, and neither does stepping a member's own context (ocn_ctx_step): the peaks then miss those steps.
+ * Two routes, decided before any step of the call runs, the same bits:
+ *   in the launch (OCN_ENS_OPT_PEAK_IN_LAUNCH 1, the default; 0 for tests and measurements): with nsteps >= 2, one
+ *     local block, every tracked member planning ONE multi-step launch that lands in a group under the capacity of
+ *     the kernels with the update in them and, for ocn_ens_step_forced, its own in-launch conditions, the groups
+ *     that hold a tracked member go as k_march_multi_pk launches: behind the barrier of every step but the last the
+ *     marching workgroups update P and S themselves; one k_ens_peak launch behind the groups does the last step's.
+ *   chunked: per step the forcing of that step (a forced call), the step as a 1-step call (the checks at the
+ *     steps of THIS call that check_every divides), the tracked members' deferred steps, one k_ens_peak launch per
+ *     block.
+ * Everything runs on the ensemble's stream with no host wait.
+ * ocn_ens_peak_info: active, field, what, tracked members, steps counted (k), and in_launch, the steps whose
+ * update a marching launch did itself (cumulative since begin).
+ * ocn_ens_peak_download(ens, member, k, which, P_host, S_host): member's arrays of block k for which =
+ * OCN_ENS_PEAK_MAX or OCN_ENS_PEAK_MIN in ocn_ctx_download's layout (P_host doubles, S_host int32; either may be
+ * NULL, not both).  Synchronous.  ocn_ens_peak_end frees the arrays.
+ * ocn_ens_peak_stats(ens, k, which, use, stat_bits): ocn_ens_stats over the P arrays of `which` of the members in
+ * use (NULL: the tracked ones; otherwise a subset of them) on block k, into the buffers ocn_ens_stats owns: read
+ * them with ocn_ens_stats_download / ocn_ens_stats_output_r4.  Asynchronous.
+ * ocn_ens_peak_exceed(ens, k, use, threshold, host): per point of block k's array, c = the number of members in
+ * use, in member order, with Pmax > threshold (a NaN is not counted), host = (double)c / (double)n in
+ * ocn_ctx_download's layout.  One launch, downloaded through pinned memory; synchronous.  OCN_ENS_PEAK_MAX must be
+ * tracked; the threshold may be any double but NaN.
+ * Errors: OCN_ERR_ARG -- no member's tail, state or bookkeeping touched, no buffer touched, an earlier peak kept --
+ * for a null argument, a field outside the six, what or which outside the masks, an extreme that is not tracked,
+ * no member in use, a member in use that is not tracked, a bad member or block index, a NaN threshold;
+ * OCN_ERR_STATE for every entry except ocn_ens_peak_begin while no peak is active, and for ocn_ens_peak_begin
+ * before ocn_ens_init_state. */
+enum { OCN_ENS_PEAK_MAX = 1, OCN_ENS_PEAK_MIN = 2 };
+enum { OCN_ENS_OPT_PEAK_IN_LAUNCH = 6 /* ocn_ens_set_option: 1 (default) or 0 */ };
+typedef struct ocn_ens_peak_info_t {
+    int32_t active, field, what, tracked;
+    int64_t steps, in_launch;
+} ocn_ens_peak_info_t;
+int ocn_ens_peak_begin(ocn_ens *ens, const uint8_t *use, int32_t field_id, int32_t what);
+int ocn_ens_peak_end(ocn_ens *ens);
+int ocn_ens_peak_info(ocn_ens *ens, ocn_ens_peak_info_t *out);
+int ocn_ens_peak_download(ocn_ens *ens, int32_t member, int32_t k, int32_t which, double *P_host, int32_t *S_host);
+int ocn_ens_peak_stats(ocn_ens *ens, int32_t k, int32_t which, const uint8_t *use, int32_t stat_bits);
+int ocn_ens_peak_exceed(ocn_ens *ens, int32_t k, const uint8_t *use, double threshold, double *host);
+
 const char *ocn_last_error(void);
 int ocn_abi_version(void);
 /* Build id: a hash of the library's sources and compile flags (Makefile), e.g. to tie a

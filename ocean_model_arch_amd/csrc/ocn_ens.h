@@ -1,6 +1,6 @@
 // ocn_ens.h -- the ensemble and what its host sources share (ocn_ens.hip, ocn_ens_diag.hip, ocn_ens_modify.hip,
-// ocn_ens_filter.hip, ocn_ens_record.hip, ocn_ens_forcing.hip).  Internal: not part of the C ABI (include/ocn_sw.h),
-// included by those six only.  No device code: the kernels behind these entries are in sw_kernels.hip and ens_*.hip.
+// ocn_ens_filter.hip, ocn_ens_record.hip, ocn_ens_forcing.hip, ocn_ens_peak.hip).  Internal: not part of the C ABI
+// (include/ocn_sw.h), included by those seven only.  No device code: the kernels behind these entries are in sw_kernels.hip and ens_*.hip.
 #pragma once
 #include "ocn_ctx.h"
 #include "ocn_ens_plan.h"
@@ -192,6 +192,24 @@ struct ocn_ens {
         int64_t applies = 0, steps = 0;
     } frc;
     bool frc_in_launch = true;     // OCN_ENS_OPT_FORCING_IN_LAUNCH
+    // ocn_ens_peak_*: the peak map.  use: one byte per member; arr[k * M + i]: member i's arrays of local block k
+    // (x = 0 the maximum, 1 the minimum; null where not asked for or not tracked), P based like the field's array,
+    // S int32 with the same element index (raw: the allocations).  stage: the tables the launches read
+    // (EnsPeakMember), one part per launch taken from the pinned copy in turn (ens_peak_slot; used: bytes of it
+    // taken so far); tab_b: one table of every member of every block.  k: steps counted since
+    // ocn_ens_peak_begin; in_launch: those whose update a marching launch did
+    struct Peak {
+        bool active = false;
+        int32_t field = 0, what = 0, tracked = 0;
+        int64_t k = 0, in_launch = 0;
+        std::vector<uint8_t> use;
+        struct Arr { void *raw[4] = {nullptr, nullptr, nullptr, nullptr}; double *p[2] = {nullptr, nullptr};
+                     int32_t *s[2] = {nullptr, nullptr}; };
+        std::vector<Arr> arr;
+        EnsStage2 stage;
+        size_t used = 0, tab_b = 0;
+    } pk;
+    bool pk_in_launch = true;      // OCN_ENS_OPT_PEAK_IN_LAUNCH
 };
 
 namespace ocn {
@@ -213,9 +231,13 @@ std::vector<char> ens_grouped(const ocn_ens *e, const std::vector<ocn_ens_group>
 //   frc (ocn_ens_step_forced's in-launch path): the time of the call's first step.  The groups that hold a forced
 //       member go as forcing launches; the forcing of t0 is written behind the call's planning, ahead of the
 //       launches, and the last step's comes home behind them
+//   peak (an in-launch call of ocn_ens_step or ocn_ens_step_forced with a peak active; with frc, never with rec):
+//       the groups that hold a tracked member go as launches with the peak update in them, from step count k0; the
+//       last step's update is the caller's, behind the launches
 struct EnsRecCall { std::vector<int> col; int due0; double *slot0; };
 struct EnsFrcCall { double t0; };
-struct EnsCall { int64_t capacity; const EnsRecCall *rec; const EnsFrcCall *frc; };
+struct EnsPeakCall { int32_t k0; };
+struct EnsCall { int64_t capacity; const EnsRecCall *rec; const EnsFrcCall *frc; const EnsPeakCall *peak = nullptr; };
 int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsCall *call);
 void *ens_based_alloc(const LBlock &b, int32_t field, size_t bytes, void **raw);
 
@@ -266,5 +288,19 @@ int ens_rec_obs(const ocn_ens *e, const std::string &who, int32_t nobs, const in
 // where it has changed, one launch per block, the known-constant verdicts dropped -- and nothing else: no tail is
 // formed, no other bookkeeping touched (the caller knows the members' sequences go on, or does the rest itself)
 int ens_frc_write(ocn_ens *e, double t);
+// ocn_ens_step_forced's two pieces, for a forced call with a peak active (ocn_ens_peak.hip): the forced members'
+// second buffers made where they are missing; ocn_ens_forcing_apply behind its checks (go: the forced members whose
+// open sequence the next step goes on with)
+int ens_frc_second(ocn_ens *e);
+int ens_frc_apply(ocn_ens *e, double t, const char *who, const std::vector<char> *go);
+
+// ---- ocn_ens_peak.hip: the peak map's buffers and events (ocn_ens_peak_end, ocn_ens_peak_begin over an earlier
+// one, ocn_ens_destroy); `need` bytes of the launches' table stage, pinned side and device side (ens_step_run's
+// in-launch tables, k_ens_peak's); the entry of member i's arrays of block k without its sources; and a call of
+// ocn_ens_step / ocn_ens_step_forced (frc) while a peak is active, behind the entry's own checks
+void ens_peak_free(ocn_ens *e);
+int ens_peak_slot(ocn_ens *e, size_t need, void **h, void **d);
+EnsPeakMember ens_peak_entry(const ocn_ens *e, size_t k, size_t i);
+int ens_peak_step(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsFrcCall *frc);
 
 }  // namespace ocn

@@ -9,6 +9,7 @@
 //                       observation-space loop in front of it (ens_assim.hip)
 //   ocn_ens_record.hip  the station recorder in their launches (sw_kernels.hip k_march_multi_rec)
 //   ocn_ens_forcing.hip the moving-storm forcing of their momentum equations (ens_forcing.hip)
+//   ocn_ens_peak.hip    the peak map kept between their steps (ens_peak.hip, sw_kernels.hip k_march_multi_pk)
 #include "ocn_ens.h"
 
 namespace ocn {
@@ -144,7 +145,19 @@ int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, co
                 note(set_error(OCN_ERR_STATE, "ens_step_forced: member " + std::to_string(i) + " planned its call otherwise than its probe"));
         RC(ens_frc_write(e, frc->t0));   // (behind the planning, into the arrays step 0 reads)
     }
+    const EnsPeakCall *const peak = call ? call->peak : nullptr;
+    EnsPeakMember *pk_h = nullptr, *pk_d = nullptr;   // (the call's part of the peak stage: one entry per member)
+    if (peak) {
+        // every tracked member must be in a launch, as the entry's probe found it: one that planned otherwise has
+        // run its steps already with no update between them -- an error, never a silent result
+        const std::vector<char> grouped = ens_grouped(e, groups);
+        for (int i = 0; i < M; ++i)
+            if (e->pk.use[(size_t)i] && !grouped[(size_t)i])
+                note(set_error(OCN_ERR_STATE, "ens_step: tracked member " + std::to_string(i) + " planned its call otherwise than its probe"));
+        RC(ens_peak_slot(e, (size_t)M * sizeof(EnsPeakMember), (void **)&pk_h, (void **)&pk_d));
+    }
     size_t rec_off = 0;   // (members of the recording launches so far: their EnsRecMember in the call's stage)
+    size_t pk_off = 0;    // (likewise the launches with the peak update and their EnsPeakMember)
     if (!groups.empty()) {
         const int sl = e->tab.slot;
         e->tab.slot ^= 1;
@@ -195,7 +208,20 @@ int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, co
                 rec_off += (size_t)q.members;
             }
             if (forcing) fl = EnsFrcLaunch{(const EnsFrcMember *)e->frc.tab.d, e->frc.model, frc->t0};
-            if (!rc) rc = launch_onepass_multi_ens(L, recording ? &rl : nullptr, forcing ? &fl : nullptr, e->stream);
+            EnsPeakLaunch pl{};
+            bool tracking = false;   // (the group holds a tracked member of a call with a peak active)
+            for (int j = 0; j < q.members && peak; ++j)
+                if (e->pk.use[(size_t)q.member[j]]) tracking = true;
+            if (tracking) {   // (the launch adds the sources: the field in both parities' buffers)
+                for (int j = 0; j < q.members; ++j) {
+                    pk_h[pk_off + (size_t)j] = ens_peak_entry(e, 0, (size_t)q.member[j]);
+                    pk_h[pk_off + (size_t)j].k0 = peak->k0;
+                }
+                pl = EnsPeakLaunch{e->pk.field, pk_h + pk_off, pk_d + pk_off};
+                pk_off += (size_t)q.members;
+            }
+            if (!rc) rc = launch_onepass_multi_ens(L, recording ? &rl : nullptr, forcing ? &fl : nullptr, e->stream,
+                                                   tracking ? &pl : nullptr);
             off += eb * (size_t)q.members;
             for (int j = 0; j < q.members; ++j) {
                 ocn_ctx *c = e->m[(size_t)q.member[j]];
@@ -277,6 +303,7 @@ int ocn_ens_destroy(ocn_ens *e)
     for (void *r : e->perturb.raw)
         if (r) (void)hipFree(r);
     ens_rec_free(e);
+    ens_peak_free(e);
     e->frc.tab.release();
     for (ocn_ens::Forcing::Second &q : e->frc.second)
         for (void *r : q.raw)
@@ -338,6 +365,11 @@ int ocn_ens_complete(ocn_ens *e)
 int ocn_ens_step(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every)
 {
     if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
+    if (e->pk.active && nsteps >= 1) {   // (ocn_ens_peak_*: the tracked members' peaks follow every step)
+        if (e->pk.k + nsteps > INT32_MAX) return set_error(OCN_ERR_ARG, "ens_step: the peak's step count would pass INT32_MAX");
+        HIPCHK(hipSetDevice(e->device));
+        return ens_peak_step(e, tau, nsteps, check_every, nullptr);
+    }
     return ens_step_run(e, tau, nsteps, check_every, nullptr);
 }
 
@@ -387,6 +419,10 @@ int ocn_ens_set_option(ocn_ens *e, int32_t key, int64_t value)
     case OCN_ENS_OPT_FORCING_IN_LAUNCH:
         if (value != 0 && value != 1) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_FORCING_IN_LAUNCH: 0 or 1");
         e->frc_in_launch = value != 0;
+        return OCN_OK;
+    case OCN_ENS_OPT_PEAK_IN_LAUNCH:
+        if (value != 0 && value != 1) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_PEAK_IN_LAUNCH: 0 or 1");
+        e->pk_in_launch = value != 0;
         return OCN_OK;
     default: return set_error(OCN_ERR_ARG, "unknown ensemble option");
     }

@@ -124,6 +124,10 @@ static int frc_second(ocn_ens *e)
     return OCN_OK;
 }
 
+// (ocn_ens_peak.hip ens_peak_step: a forced call with a peak active runs the same two pieces)
+int ens_frc_second(ocn_ens *e) { return frc_second(e); }
+int ens_frc_apply(ocn_ens *e, double t, const char *who, const std::vector<char> *go) { return frc_apply(e, t, who, go); }
+
 static int frc_ready(const ocn_ens *e, const std::string &who)
 {
     if (!e->frc.attached) return set_error(OCN_ERR_STATE, who + ": no forced member (ocn_ens_forcing_set)");
@@ -180,11 +184,17 @@ int ocn_ens_step_forced(ocn_ens *e, double tau, int32_t nsteps, int32_t check_ev
     if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
     if (nsteps < 0) return set_error(OCN_ERR_ARG, "nsteps < 0");
     if (!std::isfinite(tau) || !std::isfinite(t0)) return set_error(OCN_ERR_ARG, "ens_step_forced: a tau or t0 that is not finite");
+    if (e->pk.active && e->pk.k + nsteps > INT32_MAX)
+        return set_error(OCN_ERR_ARG, "ens_step_forced: the peak's step count would pass INT32_MAX");
     RC(frc_ready(e, "ens_step_forced"));
     HIPCHK(hipSetDevice(e->device));
     ocn_ens::Forcing &f = e->frc;
     f.in_launch = 0;
     if (nsteps == 0) return OCN_OK;
+    // (ocn_ens_peak_*: the tracked members' peaks follow every step; the routes' conditions are this entry's own
+    // and the peak's)
+    const EnsFrcCall pk_frc{t0};
+    if (e->pk.active) return ens_peak_step(e, tau, nsteps, check_every, &pk_frc);
     const int M = (int)e->m.size();
     int first = OCN_OK;
     auto note = [&](int rc) { if (rc && !first) first = rc; };

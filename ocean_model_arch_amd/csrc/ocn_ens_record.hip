@@ -178,6 +178,7 @@ int ocn_ens_step_record(ocn_ens *e, double tau, int32_t nsteps, int32_t check_ev
     if (!e) return set_error(OCN_ERR_ARG, "null ensemble");
     ocn_ens::Recorder &r = e->rec;
     if (!r.active) return set_error(OCN_ERR_STATE, "ens_step_record: no recorder (ocn_ens_record_begin)");
+    if (e->pk.active) return set_error(OCN_ERR_STATE, "ens_step_record: a peak is active (recording and peaks in one launch are not built)");
     if (nsteps < 0) return set_error(OCN_ERR_ARG, "nsteps < 0");
     for (const ocn_ctx *c : e->m)
         if (!c->initialized) return set_error(OCN_ERR_STATE, "ocn_ctx_init_state not called");

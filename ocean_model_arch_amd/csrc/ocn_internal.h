@@ -206,8 +206,9 @@ int launch_onepass_multi(const ocn_block *b, void *const *ptr, int nptr, const C
 // n x onepass_multi_b_entry_bytes()); the host copy is read when the stream reaches the copy.
 // capacity: workgroups that may be resident (at most onepass_multi_b_capacity(), the occupancy of
 // every variant of both multi-step kernels x the device's CUs): n x tiles above it is an error.
-// launch_onepass_multi_ens is that launch; with `rec` the recorder is in it, with `frc` the forcing (below;
-// both at once: an error, there is no such kernel).
+// launch_onepass_multi_ens is that launch; with `rec` the recorder is in it, with `frc` the forcing, with `peak`
+// the peak update (below; `rec` with either of the others: an error, there is no such kernel; `peak` with `frc`
+// is one kernel).
 struct EnsMember {
     const ocn_block *b;
     void *const *ptr;
@@ -239,7 +240,9 @@ struct EnsLaunch {
 };
 struct EnsRecLaunch;
 struct EnsFrcLaunch;
-int launch_onepass_multi_ens(const EnsLaunch &L, const EnsRecLaunch *rec, const EnsFrcLaunch *frc, hipStream_t s);
+struct EnsPeakLaunch;
+int launch_onepass_multi_ens(const EnsLaunch &L, const EnsRecLaunch *rec, const EnsFrcLaunch *frc, hipStream_t s,
+                             const EnsPeakLaunch *peak = nullptr);
 // The ensemble launch with a station recorder in it (sw_kernels.hip k_march_multi_rec; ocn_sw.h
 // ocn_ens_step_record): after each due step but the call's last, every member with a column >= 0 stores
 // H_j of its state into slot[j * n + col], j < nobs.  The operator is one table for all the members of the
@@ -404,6 +407,39 @@ int launch_ens_forcing(const ocn_block *b, const EnsFrcMember *d_tab, int member
 // is not forced there marches as in the plain launch.  capacity: at most onepass_multi_frc_capacity().
 struct EnsFrcLaunch { const EnsFrcMember *d_tab; ocn_ens_forcing_model model; double t0; };
 long onepass_multi_frc_capacity();
+// The peak map (ens_peak.hip; ocn_sw.h ocn_ens_peak_*): per point the highest and / or lowest value one of the six
+// prognostic fields has had after a step, and that step's number, by ens_peak_point.h.  One EnsPeakMember per
+// member of a table in device memory, written by a copy ordered before the launch and never by a kernel (scalar
+// loads through the constant address space): src[0] the field's array as the member's field table names it (the
+// state after an even number of the launch's steps), src[1] the odd steps' table's (the marching launch alone);
+// pmax / smax and pmin / smin the peaks and their steps (null: that extreme is not followed), P based like the
+// field, S int32 with the same element index; tracked 0: the member is left alone.  The interior and the step
+// count ride in the entry too (k0: the steps counted before the launch), so that the marching launch's hook costs
+// one kernel argument.
+struct EnsPeakMember {
+    const double *src[2];
+    double *pmax; int32_t *smax;
+    double *pmin; int32_t *smin;
+    long off, pitch;    // the interior's first element, the array's pitch
+    int w, npts;        // the interior's width and its number of points
+    int k0, tracked;
+};
+// launch_ens_peak: every tracked member of one block geometry, one point per lane, grid.z = member; d_tab:
+// `members` entries.  k = 0: init -- P = the field, S = 0 at the interior's points; k >= 1: the rule with step k
+// (the entries' k0 is not read).  lead: the lane of A(bnd_x1, :) within its 256-B line.  ONE launch.
+int launch_ens_peak(const ocn_block *b, const EnsPeakMember *d_tab, int members, int k, int lead, hipStream_t s);
+// out[j * w + i] = (double)c / (double)n over the block's whole array (w x h, dense), c the number of the n arrays
+// pmax[0 .. n) (member order) with a value > threshold at the point (a NaN is not counted).  ONE launch.
+int launch_ens_exceed(const ocn_block *b, const double *const *pmax, int n, double threshold, double *d_out, hipStream_t s);
+// The ensemble launch with the peak update in it (sw_kernels.hip k_march_multi_pk): behind the barrier of every
+// step but the launch's last, the workgroups of a tracked member share the interior's points and apply the rule
+// with step k0 + (steps done) to the state in the table of that parity.  h_mem / d_mem: pinned host and device
+// memory for the launch's n entries, in the launch's member order, the caller's part (the peaks, the interior, k0,
+// tracked) filled in; the launch adds src[0] / src[1] of `field` (one of the six prognostic fields).  With `frc`
+// as well the forcing is formed in the same launch (the general bodies).  capacity: at most
+// onepass_multi_pk_capacity().
+struct EnsPeakLaunch { int32_t field; EnsPeakMember *h_mem, *d_mem; };
+long onepass_multi_pk_capacity();
 // the known-constant precondition of launch_onepass over r (sw_kernels.hip FallbackCheck: the
 // fallback points and the forcing hold +0.0, h_r and mu are uniform): ORs 1 into *flag where it
 // does not hold; writes h_r and mu at (r.m0, r.n0) to kc[0], kc[1]

@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "ens_forcing_point.h"
+#include "ens_peak_point.h"
 #include "ocn_internal.h"
 #include "sw_stencils.h"
 
@@ -3595,6 +3596,72 @@ __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_frc(const
     }
 }
 
+// k_march_multi_pk: k_march_multi_frc's loop with the peak update in it (ocn_sw.h ocn_ens_peak_*), for every body.
+// The forcing fill keeps its place ahead of the arrival; it is compiled for the general bodies only and skipped
+// (workgroup-uniform) where the launch brings no forcing table or the member is not forced.  Behind
+// member_barrier of epoch s + 1 -- for every step but the launch's last, which has no barrier behind it: its
+// update is a k_ens_peak launch behind this one, as the recorder's gather and the forcing's home-coming launch --
+// the workgroups of a tracked member share the interior's points, q = tile * 256 + tid with stride tiles * 256:
+// x is loaded from the table of the parity of the steps done (EnsPeakMember::src, as EnsRecMember::f[par]) and
+// ens_peak_point.h peak_takes decides whether P and S take x and the step k0 + s + 1.  A member that is not
+// tracked skips the loop (workgroup-uniform).
+// No race, in two parts.  The x loads sit where k_march_multi_rec's record loads sit, so its argument holds: the
+// state after step s + 1 is in memory and visible behind barrier s + 1 (write-through stores, vmcnt(0) before
+// every arrival, the barrier's acquire), step s + 2 writes the other buffer of each pair, and no workgroup begins
+// step s + 3 before THIS workgroup has arrived at barrier s + 2, whose vmcnt(0) retires these loads first.  P and
+// S: within a launch a point's pair is read and written by one thread only -- the mapping q -> (tile, tid) is the
+// same at every step -- in program order, with ordinary loads and plain stores through that workgroup's own
+// caches; no other thread of the launch touches it.  Across launches (the next group's, k_ens_peak behind the
+// call, the next call) the stream orders them and a kernel's end makes its stores visible.
+// Everything the hook needs is in the member's EnsPeakMember, read with scalar loads behind the barrier (the table
+// is written by a copy ordered before the launch and never by a kernel): one more kernel argument, nothing of the
+// hook live across march_tile.  member_barrier is used unchanged.  No atomics or LDS beyond the barrier's.
+typedef const EnsPeakMember __attribute__((address_space(4))) *ConstPk;
+__device__ __forceinline__ void pk_update(ConstPk pm, int done, int tile, int tiles)
+{
+    const bool odd = __builtin_amdgcn_readfirstlane(done & 1) != 0;
+    const double *const src = odd ? pm->src[1] : pm->src[0];
+    double *const pmax = pm->pmax, *const pmin = pm->pmin;
+    int32_t *const smax = pm->smax, *const smin = pm->smin;
+    const long off = pm->off, pitch = pm->pitch;
+    const int w = pm->w, n = pm->npts, k = pm->k0 + done;
+    for (int q = tile * 256 + (int)threadIdx.x; q < n; q += tiles * 256) {
+        const int j = q / w, i = q - j * w;
+        const long at = off + (long)j * pitch + i;
+        const double x = src[at];
+        if (pmax && peak_takes<false>(x, pmax[at])) { pmax[at] = x; smax[at] = k; }
+        if (pmin && peak_takes<true>(x, pmin[at])) { pmin[at] = x; smin[at] = k; }
+    }
+}
+
+template <class Body>
+__global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_pk(const EnsEntry<Body> *__restrict__ tab, int tiles,
+                                                                          int nsteps, const EnsFrcArgs frc,
+                                                                          const EnsPeakMember *__restrict__ pk)
+{
+    typedef const EnsEntry<Body> __attribute__((address_space(4))) *ConstTab;
+    const int mem = __builtin_amdgcn_readfirstlane((int)blockIdx.x / tiles);
+    const int tile = (int)blockIdx.x - mem * tiles;
+    ConstTab e = (ConstTab)tab + mem;
+    ConstPk pm = (ConstPk)pk + mem;
+    const MarchRect R = *(const MarchRect *)&e->R;
+    unsigned *const bar = e->bar;
+    int32_t *const err = e->err;
+    const int spin = e->spin;
+    bool forced = false;
+    if constexpr (GeneralBody::has<Body>)
+        if (frc.tab) forced = ((ConstFrc)frc.tab + e->index)->forced != 0;
+    if constexpr (HasPrologue<Body>::v) ((const Body *)&e->b[0])->prologue(R, tile / R.ntx);   // the same rows every step
+    for (int s = 0; s < nsteps; ++s) {
+        march_tile<Body, false>(R, tile, *(const Body *)&e->b[__builtin_amdgcn_readfirstlane(s & 1)]);
+        if (s + 1 == nsteps) break;
+        if constexpr (GeneralBody::has<Body>)
+            if (forced) frc_fill((ConstFrc)frc.tab + e->index, frc, s + 1, tile, tiles);
+        if (!member_barrier(bar, [tiles] { return (unsigned)tiles; }, (unsigned)tile, (unsigned)(s + 1), err, spin)) return;
+        if (pm->tracked) pk_update(pm, s + 1, tile, tiles);
+    }
+}
+
 // the variant of a member's launch as the planner's id: 2 x (0 known-constant, 1 h_r-read, 2 general)
 // + (tau a power of two), + 6 with the per-step check; -1: no variant chosen on the host
 int onepass_multi_variant(int kc_mode, double tau, bool check)
@@ -3637,13 +3704,28 @@ long onepass_multi_frc_capacity()
                                           [](auto tag) { return k_march_multi_frc<typename decltype(tag)::type>; });
 }
 
+// the resident capacity of the launch with the peak update: onepass_multi_b_capacity() and those kernels' own
+// occupancy x CUs (kept apart, as the other two: no plan of a call without an active peak changes)
+long onepass_multi_pk_capacity()
+{
+    static CapacityCache cache;
+    return resident_capacity(cache, onepass_multi_b_capacity(),
+                             [](auto tag) { return k_march_multi_pk<typename decltype(tag)::type>; });
+}
+
 // The ensemble launch (ocn_internal.h EnsLaunch): one table of entries, one launch -- the plain kernel, the
-// recording one with `rec`, the forcing one with `frc`
-int launch_onepass_multi_ens(const EnsLaunch &L, const EnsRecLaunch *rec, const EnsFrcLaunch *frc, hipStream_t s)
+// recording one with `rec`, the forcing one with `frc`, the one with the peak update with `peak` (and `frc`)
+int launch_onepass_multi_ens(const EnsLaunch &L, const EnsRecLaunch *rec, const EnsFrcLaunch *frc, hipStream_t s,
+                             const EnsPeakLaunch *peak)
 {
     const EnsMember *const m = L.m;
     const int n = L.n, variant = L.variant, rows = L.rows, nsteps = L.nsteps;
     if (rec && frc) return set_error(OCN_ERR_ARG, "ensemble launch: a recorder and a forcing in one launch");
+    if (rec && peak) return set_error(OCN_ERR_ARG, "ensemble launch: a recorder and a peak update in one launch");
+    if (peak && (!peak->h_mem || !peak->d_mem ||
+                 (peak->field != OCN_SSH && peak->field != OCN_SSHP && peak->field != OCN_UBRTR && peak->field != OCN_UBRTRP &&
+                  peak->field != OCN_VBRTR && peak->field != OCN_VBRTRP)))
+        return set_error(OCN_ERR_ARG, "ensemble launch: the peak update's table, or a field that is not one of the six prognostic ones");
     if (rec) {
         if (!rec->col || !rec->field || rec->nfields < 1 || rec->nfields > OCN_ENS_OBS_MAX_FIELDS || !rec->d_start ||
             !rec->d_term || !rec->slot0 || rec->due0 < 1 || rec->every < 1 || rec->nobs < 1 || rec->n < 1 || !rec->h_mem ||
@@ -3697,7 +3779,8 @@ int launch_onepass_multi_ens(const EnsLaunch &L, const EnsRecLaunch *rec, const 
             tiles = tab[i].R.tiles;
         }
         // residency from the grid size alone, as the single-member launch: every workgroup at once
-        const long resident = rec ? onepass_multi_rec_capacity() : frc ? onepass_multi_frc_capacity() : onepass_multi_b_capacity();
+        long resident = rec ? onepass_multi_rec_capacity() : frc ? onepass_multi_frc_capacity() : onepass_multi_b_capacity();
+        if (peak) resident = std::min(resident, onepass_multi_pk_capacity());
         if ((long)n * tiles > L.capacity || L.capacity > resident)
             return set_error(OCN_ERR_ARG, "ensemble launch: grid larger than the resident capacity");
         if (rec) {   // the recorder's tables: per member the operator's fields in both parities' buffers, and the column
@@ -3716,12 +3799,41 @@ int launch_onepass_multi_ens(const EnsLaunch &L, const EnsRecLaunch *rec, const 
             RC_K(check_hip(hipMemcpyAsync(rec->d_mem, rec->h_mem, sizeof(EnsRecMember) * (size_t)n, hipMemcpyHostToDevice, s),
                            "ensemble launch: recorder table"));
         }
+        if (peak) {   // the peak update's tables: per member the field in both parities' buffers (the rest is the caller's)
+            for (int i = 0; i < n; ++i) {
+                const EnsMember &e = m[i];
+                const OddTable odd = odd_table(e.ptr, e.nptr, e.alt, nullptr);
+                const int slot = ocn_field_slot(peak->field);
+                EnsPeakMember &q = peak->h_mem[i];
+                q.src[0] = (const double *)e.ptr[slot];
+                q.src[1] = (const double *)odd.ptr[slot];
+                // (every point of the share inside the array: the interior as the caller has put it)
+                const long rows_a = e.b->bnd_y2 - e.b->bnd_y1 + 1;
+                if (q.tracked && (q.w < 1 || q.npts < q.w || q.npts % q.w || q.off < 0 || q.pitch < q.w ||
+                                  q.off + (long)(q.npts / q.w - 1) * q.pitch + q.w > (long)e.b->pitch * rows_a ||
+                                  q.pitch != e.b->pitch || (!q.pmax && !q.pmin) || (q.pmax && !q.smax) || (q.pmin && !q.smin)))
+                    return set_error(OCN_ERR_ARG, "ensemble launch: a tracked member's peak arrays or interior");
+            }
+            RC_K(check_hip(hipMemcpyAsync(peak->d_mem, peak->h_mem, sizeof(EnsPeakMember) * (size_t)n, hipMemcpyHostToDevice, s),
+                           "ensemble launch: peak table"));
+        }
         RC_K(check_hip(hipMemcpyAsync(L.d_tab, L.h_tab, sizeof(Entry) * (size_t)n, hipMemcpyHostToDevice, s),
                        "ensemble launch: member table"));
         count_launch();
         const dim3 grid((unsigned)(n * tiles)), block(256);
         const Entry *const d_tab = (const Entry *)L.d_tab;
-        if (rec) {
+        if (peak) {
+            EnsFrcArgs fa{};   // (tab null: no forcing in this launch)
+            if constexpr (GeneralBody::has<Body>) {
+                if (frc) {
+                    const ocn_block &g = *m[0].b;
+                    fa = EnsFrcArgs{frc->d_tab, frc->model, frc->t0, L.tau, g.nx_start - g.bnd_x1, g.nx_end - g.bnd_x1,
+                                    g.ny_start - g.bnd_y1, g.ny_end - g.bnd_y1, (long)g.pitch,
+                                    (unsigned)(g.pitch * (g.bnd_y2 - g.bnd_y1 + 1) * 8), (int)g.bnd_x1, (int)g.bnd_y1};
+                }
+            }
+            k_march_multi_pk<Body><<<grid, block, 0, s>>>(d_tab, tiles, nsteps, fa, peak->d_mem);
+        } else if (rec) {
             const EnsRecArgs ra{rec->d_mem, rec->d_start, rec->d_term, rec->slot0, rec->due0, rec->every, rec->nobs, rec->n};
             k_march_multi_rec<Body><<<grid, block, 0, s>>>(d_tab, tiles, nsteps, ra);
         } else if (!frc) {

@@ -12,7 +12,7 @@ import operator
 
 import numpy as np
 
-from . import _lib, ens_forcing_rule, ens_local_rule, ens_obs_rule, ens_perturb_rule, ens_record_rule
+from . import _lib, ens_forcing_rule, ens_local_rule, ens_obs_rule, ens_peak_rule, ens_perturb_rule, ens_record_rule
 from ._lib import check, lib
 from .config import BasinConfig, ParallelConfig, SWConfig
 from .model import BlockInfo, OceanModel
@@ -901,6 +901,81 @@ class OceanEnsemble:
     def set_forcing_in_launch(self, on: bool = True):
         """Tests and measurements: off, step_forced() always takes the chunked route."""
         check(lib().ocn_ens_set_option(self.ens, _lib.ENS_OPT_FORCING_IN_LAUNCH, int(bool(on))), "ocn_ens_set_option")
+        return self
+
+    # ------------------------------------------------------------ the peak map
+    def peak_begin(self, field: str = "ssh", what=("max", "min"), members=None):
+        """Start following the extremes of `field` (one of ens_peak_rule.FIELDS) at every interior point of the
+        members in use (`members`: indices; None: all) through the steps of step() and step_forced()
+        (ocn_ens_peak_begin; the rule is in include/ocn_sw.h, its numpy restatement in ens_peak_rule.py): for each
+        extreme in `what` ("max", "min") an array P of the highest / lowest value after any step so far and an
+        array S of that step's number, both on the device, updated between the steps of the marching launches
+        themselves where a call is one (peak_info()["in_launch"]), else by one launch behind each step.  P starts as
+        the field's current value, S as 0.  An earlier peak is replaced.  TypeError for an argument of the wrong
+        type, ValueError for one the library refuses."""
+        ens_peak_rule.check_field(field)
+        bits = ens_peak_rule.what_bits(what)
+        use = self._use(members)
+        if members is not None and not any(use):
+            raise ValueError("peak_begin: no member in use")
+        check(lib().ocn_ens_peak_begin(self.ens, use, _lib.FIELD_ID[field], bits), "ocn_ens_peak_begin")
+        return self
+
+    def peak_end(self):
+        """Stop following the extremes and free their arrays (ocn_ens_peak_end)."""
+        check(lib().ocn_ens_peak_end(self.ens), "ocn_ens_peak_end")
+        return self
+
+    def peak_info(self) -> dict:
+        """ocn_ens_peak_info: active, field, what (names), tracked (members), steps (counted since peak_begin) and
+        in_launch (the steps whose update a marching launch did itself, cumulative).  OcnError (OCN_ERR_STATE)
+        while no peak is active."""
+        i = _lib.OcnEnsPeakInfo()
+        check(lib().ocn_ens_peak_info(self.ens, C.byref(i)), "ocn_ens_peak_info")
+        return {"active": bool(i.active), "field": _lib.FIELD_ID.name(int(i.field)),
+                "what": tuple(n for n, b in ens_peak_rule.WHAT.items() if i.what & b), "tracked": int(i.tracked),
+                "steps": int(i.steps), "in_launch": int(i.in_launch)}
+
+    def peak(self, member: int, k: int = 0, which: str = "max"):
+        """(P, S) of one tracked member on block k for `which` ("max" or "min"): a float64 and an int32 array of the
+        block's array shape, Fortran order (ocn_ens_peak_download).  Synchronous."""
+        bit = ens_peak_rule.which_bit(which)
+        shape = self.members[0].blocks[k].shape
+        P = np.zeros(shape, dtype=np.float64, order="F")
+        S = np.zeros(shape, dtype=np.int32, order="F")
+        check(lib().ocn_ens_peak_download(self.ens, operator.index(member), int(k), bit, P.ctypes.data_as(C.c_void_p),
+                                          S.ctypes.data_as(C.c_void_p)), "ocn_ens_peak_download")
+        return P, S
+
+    def peak_stats(self, what=("mean", "max"), which: str = "max", members=None, k: int = 0) -> dict[str, np.ndarray]:
+        """stats() over the tracked members' peaks instead of a field (ocn_ens_peak_stats: the same launch over the
+        P arrays of `which`): {statistic: float64 array of block k's array shape}.  `members`: None for the tracked
+        ones, otherwise a subset of them."""
+        names = (what,) if isinstance(what, str) else tuple(what)
+        bit = ens_peak_rule.which_bit(which, "peak_stats")
+        L = lib()
+        check(L.ocn_ens_peak_stats(self.ens, int(k), bit, self._use(members), self._what(names)), "ocn_ens_peak_stats")
+        out = {}
+        for n in names:
+            a = np.zeros(self.members[0].blocks[k].shape, dtype=np.float64, order="F")
+            check(L.ocn_ens_stats_download(self.ens, int(k), _lib.ENS_STATS[n], a.ctypes.data_as(C.c_void_p)),
+                  "ocn_ens_stats_download")
+            out[n] = a
+        return out
+
+    def peak_exceed(self, threshold: float, k: int = 0, members=None) -> np.ndarray:
+        """Per point of block k's array, the fraction of the members in use (None: the tracked ones; otherwise a
+        subset of them) whose highest value so far exceeds `threshold` (ocn_ens_peak_exceed; a NaN peak is not
+        counted): a float64 array of the block's array shape.  One launch and one wait."""
+        t = ens_peak_rule.check_threshold(threshold)
+        a = np.zeros(self.members[0].blocks[k].shape, dtype=np.float64, order="F")
+        check(lib().ocn_ens_peak_exceed(self.ens, int(k), self._use(members), t, a.ctypes.data_as(C.c_void_p)),
+              "ocn_ens_peak_exceed")
+        return a
+
+    def set_peak_in_launch(self, on: bool = True):
+        """Tests and measurements: off, step() and step_forced() with a peak active always take the chunked route."""
+        check(lib().ocn_ens_set_option(self.ens, _lib.ENS_OPT_PEAK_IN_LAUNCH, int(bool(on))), "ocn_ens_set_option")
         return self
 
     def set_record_in_launch(self, on: bool = True):
