@@ -1187,7 +1187,8 @@ int ocn_ens_forcing_info(ocn_ens *ens, ocn_ens_forcing_info_t *out);
  * Who steps the peaks: ocn_ens_step and ocn_ens_step_forced, after each of their steps, for the tracked members,
  * while a peak is active (without one they take exactly the path they take without this section).  counted + nsteps
  * beyond INT32_MAX is OCN_ERR_ARG.  ocn_ens_step_record with a peak active is OCN_ERR_STATE: recording and peaks
- * in one launch are not built.  Entries that change the state without stepping (ocn_ens_transform, the
+ * in one launch are built through ocn_ens_run (below), which steps both; ocn_ens_step_record itself still
+ * refuses.  Entries that change the state without stepping (ocn_ens_transform, the
  * assimilation entries, ocn_ens_inflate, ocn_ens_perturb, ocn_ctx_upload, ocn_ens_init_state) touch neither P, S
  * nor k, and neither does stepping a member's own context (ocn_ctx_step): the peaks then miss those steps.
  * Two routes, decided before any step of the call runs, the same bits:
@@ -1229,6 +1230,43 @@ int ocn_ens_peak_info(ocn_ens *ens, ocn_ens_peak_info_t *out);
 int ocn_ens_peak_download(ocn_ens *ens, int32_t member, int32_t k, int32_t which, double *P_host, int32_t *S_host);
 int ocn_ens_peak_stats(ocn_ens *ens, int32_t k, int32_t which, const uint8_t *use, int32_t stat_bits);
 int ocn_ens_peak_exceed(ocn_ens *ens, int32_t k, const uint8_t *use, double threshold, double *host);
+
+/* One entry that steps with everything that is active: the forcing (forced != 0: step s of a forced member under
+ * the forcing of t0 + (double)s tau; t0 is not read otherwise), the station recorder and the peak map.
+ *
+ * ocn_ens_run(ens, tau, nsteps, check_every, forced, t0).  The results are the composition of the three contracts
+ * above and nothing new numerically:
+ *   members   every member ends exactly as after ocn_ens_step_forced(tau, nsteps, check_every, t0) if forced, else
+ *             as after ocn_ens_step(tau, nsteps, check_every): the same bits, the same statuses at
+ *             ocn_ens_synchronize;
+ *   recorder  if one is active the call counts its steps and writes every record that falls due, exactly as
+ *             ocn_ens_step_record defines them (ocn_ens_record_due's schedule);
+ *   peak      if one is active, P / S of every tracked member follow every step by the rule above and k advances
+ *             by nsteps.
+ * With no recorder active the call IS ocn_ens_step_forced or ocn_ens_step (peaks included, as they are there);
+ * with a recorder, not forced and no peak active, it IS ocn_ens_step_record.  A recorder together with a peak
+ * and / or forced is this entry's own ground, in two routes decided before any step of the call runs, the same
+ * bits:
+ *   in the launch (OCN_ENS_OPT_RUN_IN_LAUNCH 1, the default, and the in-launch option of every feature that is
+ *     active; 0 for tests and measurements): with nsteps >= 2, one local block, every member that is recorded,
+ *     tracked or forced planning ONE multi-step launch that lands in a group under the least of the capacities
+ *     involved, and a forced call's own in-launch conditions for the forced members.  A group that holds a
+ *     recorded member and a forced or tracked one goes as one k_march_multi_all launch (csrc/sw_kernels.hip): the
+ *     next step's forcing ahead of each member barrier, the peak update and the due records behind it; every other
+ *     group goes as the launch it would be in the entry that covers it.  Behind the groups, in this order: the
+ *     forcing's home-coming launch (after an even number of steps), one k_ens_peak launch for the last step, one
+ *     gather launch if a record is due at the last step.
+ *   chunked: per step the forcing of that step (a forced call), the step as a 1-step call (the checks at the steps
+ *     of THIS call that check_every divides), the deferred steps of the tracked and recorded members, one
+ *     k_ens_peak launch per block if a peak is active, one gather launch if the step is due.
+ * The counters move as in the three entries: ocn_ens_record_info's in_launch by the records written inside
+ * launches, ocn_ens_peak_info's by nsteps - 1 for an in-launch call, ocn_ens_forcing_info's in_launch = 1 / 0 for
+ * a forced call.  Asynchronous on the ensemble's stream, no host wait.
+ * OCN_ERR_ARG or OCN_ERR_STATE -- nothing stepped, launched, written or counted -- for a null ensemble, nsteps < 0,
+ * a tau (or, forced, a t0) that is not finite, a call whose due records would pass max_records, a peak step count
+ * beyond INT32_MAX, forced with no storm attached, a member that is not initialised. */
+enum { OCN_ENS_OPT_RUN_IN_LAUNCH = 7 /* ocn_ens_set_option: 1 (default) or 0 */ };
+int ocn_ens_run(ocn_ens *ens, double tau, int32_t nsteps, int32_t check_every, int32_t forced, double t0);
 
 const char *ocn_last_error(void);
 int ocn_abi_version(void);

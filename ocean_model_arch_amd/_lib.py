@@ -114,7 +114,7 @@ ENS_SYMBOLS = ["ocn_ens_plan", "ocn_ens_create", "ocn_ens_destroy", "ocn_ens_siz
                "ocn_ens_set_gate", "ocn_ens_gate_info", "ocn_ens_forcing_check", "ocn_ens_forcing_set",
                "ocn_ens_forcing_clear", "ocn_ens_forcing_apply", "ocn_ens_step_forced", "ocn_ens_forcing_info",
                "ocn_ens_peak_begin", "ocn_ens_peak_end", "ocn_ens_peak_info", "ocn_ens_peak_download",
-               "ocn_ens_peak_stats", "ocn_ens_peak_exceed"]
+               "ocn_ens_peak_stats", "ocn_ens_peak_exceed", "ocn_ens_run"]
 ALL_SYMBOLS = KERNEL_SYMBOLS + CTX_SYMBOLS + ENS_SYMBOLS
 ENS_MAX_MEMBERS = 256          # OCN_ENS_MAX_MEMBERS
 ENS_OBS_MAX_TERMS = 16         # OCN_ENS_OBS_MAX_TERMS
@@ -125,6 +125,7 @@ ENS_OPT_ASSIM_TIMING = 3
 ENS_OPT_RECORD_IN_LAUNCH = 4
 ENS_OPT_FORCING_IN_LAUNCH = 5
 ENS_OPT_PEAK_IN_LAUNCH = 6
+ENS_OPT_RUN_IN_LAUNCH = 7
 # OCN_ENS_STAT_* (ocn_ens_stats), in the order of their bits
 ENS_STATS = {"mean": 1, "var": 2, "spread": 4, "min": 8, "max": 16}
 # OCN_ENS_ASSIM_* (ocn_ens_assimilate_result)
@@ -372,6 +373,7 @@ def lib() -> C.CDLL:
     L.ocn_ens_peak_download.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.ocn_ens_peak_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
     L.ocn_ens_peak_exceed.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p]
+    L.ocn_ens_run.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_double]
     L.ocn_pair_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                 C.POINTER(C.c_int)]
     L.ocn_set_pair_rows.argtypes = [C.c_int]

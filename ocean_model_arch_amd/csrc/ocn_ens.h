@@ -1,6 +1,6 @@
 // ocn_ens.h -- the ensemble and what its host sources share (ocn_ens.hip, ocn_ens_diag.hip, ocn_ens_modify.hip,
-// ocn_ens_filter.hip, ocn_ens_record.hip, ocn_ens_forcing.hip, ocn_ens_peak.hip).  Internal: not part of the C ABI
-// (include/ocn_sw.h), included by those seven only.  No device code: the kernels behind these entries are in sw_kernels.hip and ens_*.hip.
+// ocn_ens_filter.hip, ocn_ens_record.hip, ocn_ens_forcing.hip, ocn_ens_peak.hip, ocn_ens_run.hip).  Internal: not
+// part of the C ABI (include/ocn_sw.h), included by those eight only.  No device code: the kernels behind these entries are in sw_kernels.hip and ens_*.hip.
 #pragma once
 #include "ocn_ctx.h"
 #include "ocn_ens_plan.h"
@@ -210,6 +210,7 @@ struct ocn_ens {
         size_t used = 0, tab_b = 0;
     } pk;
     bool pk_in_launch = true;      // OCN_ENS_OPT_PEAK_IN_LAUNCH
+    bool run_in_launch = true;     // OCN_ENS_OPT_RUN_IN_LAUNCH (ocn_ens_run with a recorder and a peak and / or forced)
 };
 
 namespace ocn {
@@ -226,14 +227,18 @@ void ens_probe(ocn_ens *e, const char *who, double tau, int32_t nsteps, int32_t 
                std::vector<int32_t> &variant, std::vector<char> &go);
 // one flag per member: it is in one of the groups
 std::vector<char> ens_grouped(const ocn_ens *e, const std::vector<ocn_ens_group> &groups);
-// What a call brings to ocn_ens_step's launches beyond the steps: the capacity in effect and ONE of
+// What a call brings to ocn_ens_step's launches beyond the steps: the capacity in effect and rec, frc or frc with
+// peak (the three entries) or rec with frc and / or peak (ocn_ens_run):
 //   rec (ocn_ens_step_record's in-launch path): the members' columns (-1: not in use), the first due step, its slot;
 //   frc (ocn_ens_step_forced's in-launch path): the time of the call's first step.  The groups that hold a forced
 //       member go as forcing launches; the forcing of t0 is written behind the call's planning, ahead of the
 //       launches, and the last step's comes home behind them
-//   peak (an in-launch call of ocn_ens_step or ocn_ens_step_forced with a peak active; with frc, never with rec):
+//   peak (an in-launch call of ocn_ens_step, ocn_ens_step_forced or ocn_ens_run with a peak active):
 //       the groups that hold a tracked member go as launches with the peak update in them, from step count k0; the
 //       last step's update is the caller's, behind the launches
+// A group that holds a recorded member and a forced or tracked one goes as one launch with everything in it
+// (sw_kernels.hip k_march_multi_all).  With rec and another, a recorded member that planned otherwise than its probe
+// is an error, as a forced or tracked one always is.
 struct EnsRecCall { std::vector<int> col; int due0; double *slot0; };
 struct EnsFrcCall { double t0; };
 struct EnsPeakCall { int32_t k0; };
@@ -279,6 +284,11 @@ void ens_obs_table(const std::vector<ocn_ctx *> &in, const std::vector<int32_t> 
 // ---- ocn_ens_record.hip: the recorder's buffers and events (ocn_ens_record_end, ocn_ens_record_begin over an
 // earlier one, ocn_ens_destroy), and what ocn_ens_record_sample and ocn_ens_assimilate_rec check alike
 void ens_rec_free(ocn_ens *e);
+// ocn_ens_step_record's two pieces, for ocn_ens_run (ocn_ens_run.hip): the stage of one recording call -- `need`
+// bytes in the copy whose turn it is --, and record `index` gathered from the members `in` through the pointer
+// table at `at` of that stage.  The caller marks the stage sent (rec.stage.sent) behind the call's last use
+int ens_rec_stage(ocn_ens *e, size_t need);
+int ens_rec_gather(ocn_ens *e, const std::vector<ocn_ctx *> &in, int32_t index, size_t at);
 int ens_rec_members(const ocn_ens *e, const std::string &who, const uint8_t *use, std::vector<ocn_ctx *> &in,
                     std::vector<int> &col);
 int ens_rec_obs(const ocn_ens *e, const std::string &who, int32_t nobs, const int32_t *row, const int32_t *rec,
@@ -293,6 +303,8 @@ int ens_frc_write(ocn_ens *e, double t);
 // open sequence the next step goes on with)
 int ens_frc_second(ocn_ens *e);
 int ens_frc_apply(ocn_ens *e, double t, const char *who, const std::vector<char> *go);
+// what every forced entry asks first: a storm attached and every member initialised (`who` opens the message)
+int ens_frc_ready(const ocn_ens *e, const std::string &who);
 
 // ---- ocn_ens_peak.hip: the peak map's buffers and events (ocn_ens_peak_end, ocn_ens_peak_begin over an earlier
 // one, ocn_ens_destroy); `need` bytes of the launches' table stage, pinned side and device side (ens_step_run's
@@ -302,5 +314,7 @@ void ens_peak_free(ocn_ens *e);
 int ens_peak_slot(ocn_ens *e, size_t need, void **h, void **d);
 EnsPeakMember ens_peak_entry(const ocn_ens *e, size_t k, size_t i);
 int ens_peak_step(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsFrcCall *frc);
+// ens_peak_step's piece for ocn_ens_run: one k_ens_peak launch per local block over the tracked members with step k
+int ens_peak_launch(ocn_ens *e, int32_t k);
 
 }  // namespace ocn

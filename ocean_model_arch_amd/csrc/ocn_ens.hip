@@ -9,6 +9,7 @@
 //                       observation-space loop in front of it (ens_assim.hip)
 //   ocn_ens_record.hip  the station recorder in their launches (sw_kernels.hip k_march_multi_rec)
 //   ocn_ens_forcing.hip the moving-storm forcing of their momentum equations (ens_forcing.hip)
+//   ocn_ens_run.hip     the one entry that steps with everything that is active (sw_kernels.hip k_march_multi_all)
 //   ocn_ens_peak.hip    the peak map kept between their steps (ens_peak.hip, sw_kernels.hip k_march_multi_pk)
 #include "ocn_ens.h"
 
@@ -113,7 +114,8 @@ std::vector<char> ens_grouped(const ocn_ens *e, const std::vector<ocn_ens_group>
     return grouped;
 }
 
-// ocn_ens_step; with `call` the same call with the recorder (call->rec) or the forcing (call->frc) in its launches
+// ocn_ens_step; with `call` the same call with the recorder (call->rec), the forcing (call->frc) and / or the peak
+// update (call->peak) in its launches
 int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, const EnsCall *call)
 {
     const EnsRecCall *const rec = call ? call->rec : nullptr;
@@ -155,6 +157,14 @@ int ens_step_run(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every, co
             if (e->pk.use[(size_t)i] && !grouped[(size_t)i])
                 note(set_error(OCN_ERR_STATE, "ens_step: tracked member " + std::to_string(i) + " planned its call otherwise than its probe"));
         RC(ens_peak_slot(e, (size_t)M * sizeof(EnsPeakMember), (void **)&pk_h, (void **)&pk_d));
+    }
+    if (rec && (frc || peak)) {
+        // (ocn_ens_run) likewise every recorded member: one that planned otherwise has run its steps already with
+        // no record between them
+        const std::vector<char> grouped = ens_grouped(e, groups);
+        for (int i = 0; i < M; ++i)
+            if (rec->col[(size_t)i] >= 0 && !grouped[(size_t)i])
+                note(set_error(OCN_ERR_STATE, "ens_run: recorded member " + std::to_string(i) + " planned its call otherwise than its probe"));
     }
     size_t rec_off = 0;   // (members of the recording launches so far: their EnsRecMember in the call's stage)
     size_t pk_off = 0;    // (likewise the launches with the peak update and their EnsPeakMember)
@@ -423,6 +433,10 @@ int ocn_ens_set_option(ocn_ens *e, int32_t key, int64_t value)
     case OCN_ENS_OPT_PEAK_IN_LAUNCH:
         if (value != 0 && value != 1) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_PEAK_IN_LAUNCH: 0 or 1");
         e->pk_in_launch = value != 0;
+        return OCN_OK;
+    case OCN_ENS_OPT_RUN_IN_LAUNCH:
+        if (value != 0 && value != 1) return set_error(OCN_ERR_ARG, "OCN_ENS_OPT_RUN_IN_LAUNCH: 0 or 1");
+        e->run_in_launch = value != 0;
         return OCN_OK;
     default: return set_error(OCN_ERR_ARG, "unknown ensemble option");
     }

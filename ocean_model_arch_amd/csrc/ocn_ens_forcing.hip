@@ -136,6 +136,8 @@ static int frc_ready(const ocn_ens *e, const std::string &who)
     return OCN_OK;
 }
 
+int ens_frc_ready(const ocn_ens *e, const std::string &who) { return frc_ready(e, who); }
+
 }  // namespace ocn
 
 extern "C" {

@@ -87,6 +87,8 @@ static int peak_launch(ocn_ens *e, int32_t k)
     return OCN_OK;
 }
 
+int ens_peak_launch(ocn_ens *e, int32_t k) { return peak_launch(e, k); }
+
 // the tracked members' steps that pair launches deferred, run now as a call's tail runs them (the six state
 // fields are current after any call otherwise: no other tail is formed, the sequences stay open)
 static int peak_deferred(ocn_ens *e, const char *who)

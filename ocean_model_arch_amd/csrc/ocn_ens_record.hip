@@ -51,6 +51,30 @@ int ens_rec_obs(const ocn_ens *e, const std::string &who, int32_t nobs, const in
     return OCN_OK;
 }
 
+// The stage of one recording call: `need` bytes in the copy whose turn it is, read by the stream no more.
+// Growing it waits for the device (rare: a call with more than 16 gathers after ocn_ens_record_begin).
+int ens_rec_stage(ocn_ens *e, size_t need)
+{
+    EnsStage2 &st = e->rec.stage;
+    RC(st.reserve(need, 65536));
+    st.slot ^= 1;
+    return st.await(st.slot);
+}
+
+// record `index` gathered from the members in use as their field tables name the arrays now: the pointer table
+// at `at` of the call's stage up, then k_ens_sample_h into the record's slot.  No wait.
+int ens_rec_gather(ocn_ens *e, const std::vector<ocn_ctx *> &in, int32_t index, size_t at)
+{
+    const ocn_ens::Recorder &r = e->rec;
+    char *h = (char *)r.stage.h[r.stage.slot] + at, *dt = (char *)r.stage.d + at;
+    ens_obs_table(in, r.field, (const double **)h);
+    HIPCHK(hipMemcpyAsync(dt, h, r.tab_b, hipMemcpyHostToDevice, e->stream));
+    const char *d = (const char *)r.d_op;
+    const EnsObsOp op{(const double *const *)dt, (const int *)(d + r.start_at),
+                      (const EnsObsTerm *)(d + r.term_at)};
+    return launch_ens_sample_h(op, r.n, r.nobs, (double *)r.d_series + (size_t)index * (size_t)r.nobs * (size_t)r.n, e->stream);
+}
+
 }  // namespace ocn
 
 extern "C" {
@@ -147,30 +171,6 @@ int ocn_ens_record_download(ocn_ens *e, int32_t first, int32_t count, double *ho
     const size_t rb = (size_t)r.nobs * (size_t)r.n * sizeof(double);
     if (count) HIPCHK(hipMemcpy(host, (const char *)r.d_series + (size_t)first * rb, (size_t)count * rb, hipMemcpyDeviceToHost));
     return OCN_OK;
-}
-
-// The stage of one recording call: `need` bytes in the copy whose turn it is, read by the stream no more.
-// Growing it waits for the device (rare: a call with more than 16 gathers after ocn_ens_record_begin).
-static int ens_rec_stage(ocn_ens *e, size_t need)
-{
-    EnsStage2 &st = e->rec.stage;
-    RC(st.reserve(need, 65536));
-    st.slot ^= 1;
-    return st.await(st.slot);
-}
-
-// record `index` gathered from the members in use as their field tables name the arrays now: the pointer table
-// at `at` of the call's stage up, then k_ens_sample_h into the record's slot.  No wait.
-static int ens_rec_gather(ocn_ens *e, const std::vector<ocn_ctx *> &in, int32_t index, size_t at)
-{
-    const ocn_ens::Recorder &r = e->rec;
-    char *h = (char *)r.stage.h[r.stage.slot] + at, *dt = (char *)r.stage.d + at;
-    ens_obs_table(in, r.field, (const double **)h);
-    HIPCHK(hipMemcpyAsync(dt, h, r.tab_b, hipMemcpyHostToDevice, e->stream));
-    const char *d = (const char *)r.d_op;
-    const EnsObsOp op{(const double *const *)dt, (const int *)(d + r.start_at),
-                      (const EnsObsTerm *)(d + r.term_at)};
-    return launch_ens_sample_h(op, r.n, r.nobs, (double *)r.d_series + (size_t)index * (size_t)r.nobs * (size_t)r.n, e->stream);
 }
 
 int ocn_ens_step_record(ocn_ens *e, double tau, int32_t nsteps, int32_t check_every)

@@ -207,8 +207,8 @@ int launch_onepass_multi(const ocn_block *b, void *const *ptr, int nptr, const C
 // capacity: workgroups that may be resident (at most onepass_multi_b_capacity(), the occupancy of
 // every variant of both multi-step kernels x the device's CUs): n x tiles above it is an error.
 // launch_onepass_multi_ens is that launch; with `rec` the recorder is in it, with `frc` the forcing, with `peak`
-// the peak update (below; `rec` with either of the others: an error, there is no such kernel; `peak` with `frc`
-// is one kernel).
+// the peak update (below; `peak` with `frc` is one kernel, `rec` with either or both of the others is
+// k_march_multi_all).
 struct EnsMember {
     const ocn_block *b;
     void *const *ptr;
@@ -440,6 +440,12 @@ int launch_ens_exceed(const ocn_block *b, const double *const *pmax, int n, doub
 // onepass_multi_pk_capacity().
 struct EnsPeakLaunch { int32_t field; EnsPeakMember *h_mem, *d_mem; };
 long onepass_multi_pk_capacity();
+// The ensemble launch with everything in it (sw_kernels.hip k_march_multi_all; ocn_sw.h ocn_ens_run): `rec` together
+// with `frc` and / or `peak` -- the forcing fill ahead of each barrier, the peak update and the due records behind
+// it, each as in its own launch above.  The recorder's and the peak's tables are in the launch's member order, the
+// forcing's is indexed by EnsMember::index.  capacity: at most the least of the capacities of what the launch
+// carries and onepass_multi_all_capacity().
+long onepass_multi_all_capacity();
 // the known-constant precondition of launch_onepass over r (sw_kernels.hip FallbackCheck: the
 // fallback points and the forcing hold +0.0, h_r and mu are uniform): ORs 1 into *flag where it
 // does not hold; writes h_r and mu at (r.m0, r.n0) to kc[0], kc[1]

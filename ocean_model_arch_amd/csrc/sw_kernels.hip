@@ -3662,6 +3662,77 @@ __global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_pk(const 
     }
 }
 
+// k_march_multi_all: k_march_multi_pk's loop with k_march_multi_rec's hook behind the same barrier (ocn_sw.h
+// ocn_ens_run), for every body: the launch of a group that records and also forces or tracks.  Per step s but the
+// launch's last: march_tile; frc_fill(s + 1) (the general bodies; skipped workgroup-uniformly without a forcing
+// table or for a member that is not forced); member_barrier(s + 1); pk_update(s + 1) where a peak table is given
+// and the member is tracked; and, if step s + 1 is due and the member's column is >= 0, the stride loop over the
+// operator's rows with rec_apply, from the table of the parity of the steps done into the slot of that record.
+// The due test and the slot are computed from s behind the barrier (due0, every and slot0 are kernel arguments:
+// scalar registers), the member's column and base pointers are read there with scalar loads: nothing of the hooks
+// is live across march_tile.  The recorder's and the peak's member tables are indexed by the launch-local member,
+// the forcing's by EnsEntry::index.  frc_fill, pk_update, rec_apply and member_barrier are used unchanged.
+// No race: the union of the three arguments above.
+//   Record and peak loads sit between barrier s + 1 and this workgroup's arrival at barrier s + 2.  The state after
+//   step s + 1 is in memory and visible behind barrier s + 1 (write-through stores, vmcnt(0) before every arrival,
+//   the barrier's acquire); step s + 2 writes only the other buffer of each pair; step s + 3 does write these
+//   buffers, but no workgroup begins it before THIS workgroup has arrived at barrier s + 2, whose vmcnt(0) retires
+//   these loads first.
+//   The forcing buffer (s + 1) & 1 was last read by step s - 1, and no workgroup starts step s -- so none reaches
+//   the fill -- before all have finished step s - 1 and passed the barrier behind it; step s reads the other
+//   buffer.  Neither hook behind the barrier reads or writes a forcing buffer.
+//   P and S: a point's pair is read and written by one thread per launch (q -> (tile, tid) is the same at every
+//   step), in program order; the recorder's hook touches neither.
+//   Series slots: element (row j, column col) of a record is written by exactly one thread -- j's owner in the
+//   member that holds the column -- once, and read by nobody in the launch; the peak hook and the fill write
+//   elsewhere (P / S, RHSx / RHSy).
+// The call's last step has no barrier behind it: its forcing is at home or comes home by a k_ens_forcing launch,
+// its peak update is a k_ens_peak launch and its record a gather, behind this launch in that order.
+// No atomics, LDS or inline assembly beyond the barrier's; no scratch.
+template <class Body>
+__global__ __launch_bounds__(256, WavesOf<Body>::v) void k_march_multi_all(const EnsEntry<Body> *__restrict__ tab, int tiles,
+                                                                           int nsteps, const EnsFrcArgs frc,
+                                                                           const EnsPeakMember *__restrict__ pk,
+                                                                           const EnsRecArgs rec)
+{
+    typedef const EnsEntry<Body> __attribute__((address_space(4))) *ConstTab;
+    typedef const EnsRecMember __attribute__((address_space(4))) *ConstRec;
+    const int mem = __builtin_amdgcn_readfirstlane((int)blockIdx.x / tiles);
+    const int tile = (int)blockIdx.x - mem * tiles;
+    ConstTab e = (ConstTab)tab + mem;
+    const MarchRect R = *(const MarchRect *)&e->R;
+    unsigned *const bar = e->bar;
+    int32_t *const err = e->err;
+    const int spin = e->spin;
+    bool forced = false;
+    if constexpr (GeneralBody::has<Body>)
+        if (frc.tab) forced = ((ConstFrc)frc.tab + e->index)->forced != 0;
+    if constexpr (HasPrologue<Body>::v) ((const Body *)&e->b[0])->prologue(R, tile / R.ntx);   // the same rows every step
+    for (int s = 0; s < nsteps; ++s) {
+        march_tile<Body, false>(R, tile, *(const Body *)&e->b[__builtin_amdgcn_readfirstlane(s & 1)]);
+        if (s + 1 == nsteps) break;
+        if constexpr (GeneralBody::has<Body>)
+            if (forced) frc_fill((ConstFrc)frc.tab + e->index, frc, s + 1, tile, tiles);
+        if (!member_barrier(bar, [tiles] { return (unsigned)tiles; }, (unsigned)tile, (unsigned)(s + 1), err, spin)) return;
+        if (pk) {
+            ConstPk pm = (ConstPk)pk + mem;
+            if (pm->tracked) pk_update(pm, s + 1, tile, tiles);
+        }
+        const int past = s + 1 - rec.due0;   // (steps past the call's first due one)
+        if (past < 0 || past % rec.every) continue;
+        ConstRec rm = (ConstRec)rec.mem + mem;
+        const int col = rm->col;
+        if (col < 0) continue;
+        // state s + 1, in the table of its parity
+        const int par = __builtin_amdgcn_readfirstlane((s + 1) & 1);
+        const double *const f0 = rm->f[par][0], *const f1 = rm->f[par][1], *const f2 = rm->f[par][2],
+                     *const f3 = rm->f[par][3];
+        double *const slot = rec.slot0 + (long)(past / rec.every) * ((long)rec.nobs * rec.n);
+        for (int j = tile * 256 + (int)threadIdx.x; j < rec.nobs; j += tiles * 256)
+            slot[(long)j * rec.n + col] = rec_apply(f0, f1, f2, f3, rec.start, rec.term, j);
+    }
+}
+
 // the variant of a member's launch as the planner's id: 2 x (0 known-constant, 1 h_r-read, 2 general)
 // + (tau a power of two), + 6 with the per-step check; -1: no variant chosen on the host
 int onepass_multi_variant(int kc_mode, double tau, bool check)
@@ -3713,15 +3784,23 @@ long onepass_multi_pk_capacity()
                              [](auto tag) { return k_march_multi_pk<typename decltype(tag)::type>; });
 }
 
+// the resident capacity of the launch that records and also forces or tracks: onepass_multi_b_capacity() and those
+// kernels' own occupancy x CUs (kept apart, as the other three: no plan of a call that does not combine them changes)
+long onepass_multi_all_capacity()
+{
+    static CapacityCache cache;
+    return resident_capacity(cache, onepass_multi_b_capacity(),
+                             [](auto tag) { return k_march_multi_all<typename decltype(tag)::type>; });
+}
+
 // The ensemble launch (ocn_internal.h EnsLaunch): one table of entries, one launch -- the plain kernel, the
-// recording one with `rec`, the forcing one with `frc`, the one with the peak update with `peak` (and `frc`)
+// recording one with `rec`, the forcing one with `frc`, the one with the peak update with `peak` (and `frc`), the
+// one with everything with `rec` and `frc` and / or `peak`
 int launch_onepass_multi_ens(const EnsLaunch &L, const EnsRecLaunch *rec, const EnsFrcLaunch *frc, hipStream_t s,
                              const EnsPeakLaunch *peak)
 {
     const EnsMember *const m = L.m;
     const int n = L.n, variant = L.variant, rows = L.rows, nsteps = L.nsteps;
-    if (rec && frc) return set_error(OCN_ERR_ARG, "ensemble launch: a recorder and a forcing in one launch");
-    if (rec && peak) return set_error(OCN_ERR_ARG, "ensemble launch: a recorder and a peak update in one launch");
     if (peak && (!peak->h_mem || !peak->d_mem ||
                  (peak->field != OCN_SSH && peak->field != OCN_SSHP && peak->field != OCN_UBRTR && peak->field != OCN_UBRTRP &&
                   peak->field != OCN_VBRTR && peak->field != OCN_VBRTRP)))
@@ -3781,6 +3860,10 @@ int launch_onepass_multi_ens(const EnsLaunch &L, const EnsRecLaunch *rec, const 
         // residency from the grid size alone, as the single-member launch: every workgroup at once
         long resident = rec ? onepass_multi_rec_capacity() : frc ? onepass_multi_frc_capacity() : onepass_multi_b_capacity();
         if (peak) resident = std::min(resident, onepass_multi_pk_capacity());
+        if (rec && (frc || peak)) {   // (everything the launch carries)
+            if (frc) resident = std::min(resident, onepass_multi_frc_capacity());
+            resident = std::min(resident, onepass_multi_all_capacity());
+        }
         if ((long)n * tiles > L.capacity || L.capacity > resident)
             return set_error(OCN_ERR_ARG, "ensemble launch: grid larger than the resident capacity");
         if (rec) {   // the recorder's tables: per member the operator's fields in both parities' buffers, and the column
@@ -3822,7 +3905,7 @@ int launch_onepass_multi_ens(const EnsLaunch &L, const EnsRecLaunch *rec, const 
         count_launch();
         const dim3 grid((unsigned)(n * tiles)), block(256);
         const Entry *const d_tab = (const Entry *)L.d_tab;
-        if (peak) {
+        if (peak || (rec && frc)) {
             EnsFrcArgs fa{};   // (tab null: no forcing in this launch)
             if constexpr (GeneralBody::has<Body>) {
                 if (frc) {
@@ -3832,7 +3915,12 @@ int launch_onepass_multi_ens(const EnsLaunch &L, const EnsRecLaunch *rec, const 
                                     (unsigned)(g.pitch * (g.bnd_y2 - g.bnd_y1 + 1) * 8), (int)g.bnd_x1, (int)g.bnd_y1};
                 }
             }
-            k_march_multi_pk<Body><<<grid, block, 0, s>>>(d_tab, tiles, nsteps, fa, peak->d_mem);
+            if (rec) {
+                const EnsRecArgs ra{rec->d_mem, rec->d_start, rec->d_term, rec->slot0, rec->due0, rec->every, rec->nobs, rec->n};
+                k_march_multi_all<Body><<<grid, block, 0, s>>>(d_tab, tiles, nsteps, fa, peak ? peak->d_mem : nullptr, ra);
+            } else {
+                k_march_multi_pk<Body><<<grid, block, 0, s>>>(d_tab, tiles, nsteps, fa, peak->d_mem);
+            }
         } else if (rec) {
             const EnsRecArgs ra{rec->d_mem, rec->d_start, rec->d_term, rec->slot0, rec->due0, rec->every, rec->nobs, rec->n};
             k_march_multi_rec<Body><<<grid, block, 0, s>>>(d_tab, tiles, nsteps, ra);

@@ -978,6 +978,37 @@ class OceanEnsemble:
         check(lib().ocn_ens_set_option(self.ens, _lib.ENS_OPT_PEAK_IN_LAUNCH, int(bool(on))), "ocn_ens_set_option")
         return self
 
+    # ------------------------------------------------------------ everything that is active, in one call
+    def run(self, nsteps: int, tau: float = 1.0, t0=None, check_every: int = 1):
+        """nsteps steps of every member with everything that is active (ocn_ens_run): forced under the storms of
+        set_storms() from time `t0` on (None: unforced) as step_forced() steps them, the recorder's due records
+        written as step_record() defines them, the peaks of peak_begin() following every step.  Without a recorder
+        the call is step_forced() / step() itself, with a recorder alone step_record() itself; a recorder together
+        with a peak and / or a forced call runs as one marching launch per group where the call is one
+        (record_info(), peak_info() and forcing_info() show the route), else chunked per step; the same bits either
+        way.  TypeError for an argument of the wrong type; ValueError for nsteps < 0 or a tau or t0 that is not
+        finite."""
+        if isinstance(nsteps, bool) or not isinstance(nsteps, (int, np.integer)):
+            raise TypeError(f"run: nsteps = {nsteps!r}, not an integer")
+        if isinstance(check_every, bool) or not isinstance(check_every, (int, np.integer)):
+            raise TypeError(f"run: check_every = {check_every!r}, not an integer")
+        if nsteps < 0:
+            raise ValueError(f"run: nsteps = {nsteps} < 0")
+        for what, v in (("tau", tau),) + ((("t0", t0),) if t0 is not None else ()):
+            if isinstance(v, (str, bytes, bool)) or np.ndim(v) != 0:
+                raise TypeError(f"run: {what} = {v!r}, not a number")
+            if not np.isfinite(float(v)):
+                raise ValueError(f"run: a {what} that is not finite")
+        check(lib().ocn_ens_run(self.ens, float(tau), int(nsteps), int(check_every), 0 if t0 is None else 1,
+                                0.0 if t0 is None else float(t0)), "ocn_ens_run")
+        return self
+
+    def set_run_in_launch(self, on: bool = True):
+        """Tests and measurements: off, run() with a recorder and a peak and / or storms always takes the chunked
+        route."""
+        check(lib().ocn_ens_set_option(self.ens, _lib.ENS_OPT_RUN_IN_LAUNCH, int(bool(on))), "ocn_ens_set_option")
+        return self
+
     def set_record_in_launch(self, on: bool = True):
         """Tests and measurements: off, step_record() always takes the chunked route."""
         check(lib().ocn_ens_set_option(self.ens, _lib.ENS_OPT_RECORD_IN_LAUNCH, int(bool(on))), "ocn_ens_set_option")
